@@ -1,13 +1,17 @@
 #!/usr/bin/env python
 """Headline benchmark: GPT-ST pretraining steps/s on PEMS08-shaped synthetic input (B=32, T=12, N=170, C=64) on MI355X.
 
-    python bench.py --gpus 1 --steps 200 --warmup 20
+    python bench.py --gpus 1 --steps 200 --warmup 20 [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One step = zero_grad -> forward (mask generation included) -> masked-MAE + 0.1 KL -> backward -> clip -> Adam
-(reference BasicTrainer.py:72-103) at epoch 200 of 300 (adaptive masking + KL: the phase 290 of the 300 epochs run in).
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` (dominant kernel, measured with
-HIP events inside this run) and `cpu_baseline` (the oracle's op-for-op PyTorch-CPU restatement on the host cores).
+(reference BasicTrainer.py:72-103) at epoch 200 of 300 (adaptive masking + KL: the phase 290 of the 300 epochs run in), with the
+learning rate at 0 (BENCH_LR): every step does all of that arithmetic, Adam's included, but the weights keep their seeded initial values.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times --steps steps and reports them (`value`, `ms_per_step`);
+--dump-outputs DIR then writes what the last timed step returned (loss, gradient, parameters, Adam moments) as DIR/<name>.npy.
+--full adds everything else the benchmark measures: `value_exact_warmup`, the random-mask phase rate, per-collective
+durations, `roofline` (dominant kernel, measured with HIP events inside this run), the module path and `cpu_baseline`
+(the oracle's op-for-op PyTorch-CPU restatement on the host cores).
 """
 import argparse
 import json
@@ -28,6 +32,37 @@ import torch  # noqa: E402
 
 HBM_PEAK = 8.0e12          # B/s   (MI355X_MICROARCH.md: 8 TB/s spec)
 MFMA_F32_PEAK = 157.3e12   # FLOP/s fp32 matrix (same file)
+CLOCK_WARM_STEPS = 300     # untimed steps before the timed region: ~0.33 s at the headline shape's 1.1 ms per step
+# Learning rate of the benchmarked steps.  The default step reduces gradients with float atomics, so two runs differ by rounding; a training
+# trajectory grows that into real divergence (two runs of 520 steps at the conf's 3e-3: losses 1.5 % apart, weights 8e-3 apart).  At 0 the
+# Adam kernel still loads, updates and stores weights and moments (w - 0 * m / denom: the weights stay bit-identical), so a step costs the same
+# and what a run computes from its arguments is the same every run up to rounding.
+BENCH_LR = 0.0
+DUMP_LIMIT = 63 * 10**6    # array bytes written by --dump-outputs in all (< 64 MB with the .npy headers)
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: write `arrays` (what the timed path returned from its last step) as d/<name>.npy, float32 or float64.  Over
+    DUMP_LIMIT in all, the long arrays (parameters and their moments: one length) keep the same fixed, seeded sample of positions,
+    written beside them as sample_index.npy."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    out = {}
+    for k, v in arrays.items():
+        v = v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+        out[k] = v.reshape(-1).astype(np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in out.values())
+    if total > DUMP_LIMIT:
+        n = max(v.size for v in out.values())
+        big = [k for k, v in out.items() if v.size == n]
+        rest = total - sum(out[k].nbytes for k in big)
+        keep = (DUMP_LIMIT - rest) // (sum(out[k].itemsize for k in big) + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        for k in big:
+            out[k] = out[k][idx]
+        out["sample_index"] = idx.astype(np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
 
 
 def kernel_flops(name, tag, d):
@@ -198,14 +233,15 @@ def retime_kernel(name, tag, reps=50):
     return e0.elapsed_time(e1) * 1e-3 / reps
 
 
-def module_path(args, B, epoch, dev, steps=40, warmup=6, clip_adam=False):
+def module_path(args, B, epoch, dev, steps=40, warmup=6, clip_adam=False, dump=None):
     """The OTHER way into the HIP kernels, the one INTEGRATION.md section 1 advertises: the reference's own training loop
     (model/BasicTrainer.py:72-103) around the drop-in nn.Module — GPTST_Model.forward (one autograd node over the HIP forward / backward),
     the reference's torch loss closures (Run.py:91-101, lib/metrics.py:11-18, KLDivLoss(sum)), loss.backward(), clip_grad_norm_(5),
     torch.optim.Adam.step(), loss.item().  No fused step, no hipGraph, per-tensor optimiser: what a maintainer gets from the one-line
     import swap alone (r06: the node's forward and backward replay hipGraphs, gptst_amd/module_graph.py).
     clip_adam: the SECOND line a maintainer may change — Run.py:134's torch.optim.Adam -> gptst_amd.optim.ClipAdam(..., max_grad_norm=5), which does the
-    loop's clip_grad_norm_ + Adam.step() as the two launches of gptst_clip_adam (the clip_grad_norm_ line goes).  -> dict(steps_per_s, ms_per_step, ...)."""
+    loop's clip_grad_norm_ + Adam.step() as the two launches of gptst_clip_adam (the clip_grad_norm_ line goes).  -> dict(steps_per_s, ms_per_step, ...).
+    dump: directory for the loss and the parameters after the last timed step (--dump-outputs with --path module)."""
     from gptst_amd import synth
     from gptst_amd.model import GPTST_Model, xavier_init_
     model = xavier_init_(GPTST_Model(args)).to(dev)
@@ -242,6 +278,8 @@ def module_path(args, B, epoch, dev, steps=40, warmup=6, clip_adam=False):
         last = one()
     torch.cuda.synchronize()
     el = time.perf_counter() - t0
+    if dump:
+        dump_outputs(dump, dict(loss=[last], parameters=model.flat))
     from gptst_amd import module_graph
     return dict(steps_per_s=steps / el, ms_per_step=1e3 * el / steps, steps=steps, last_loss=last, graphs=bool(module_graph.ENABLED),
                 what="reference-style loop (BasicTrainer.py:72-103) over the drop-in GPTST_Model: autograd node on the HIP kernels (forward / backward "
@@ -332,11 +370,16 @@ def main():
                          "input buffer with its own optimiser update, behind ONE host-scalar copy and ONE graph launch (default: the trainer's "
                          "own setting, config.STEPS_PER_REPLAY = 4; 1 = one replay per step)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: value_exact_warmup, the random-mask phase rate, per-collective "
+                         "durations, the kernel roofline, the module path and the CPU baseline (each one can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned from its last step as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the per-kernel timing and roofline")
     ap.add_argument("--path", choices=["step", "module"], default="step",
                     help="step: the fused PretrainStep (headline); module: ONLY the reference-style loop over the drop-in nn.Module (its rate becomes `value`)")
-    ap.add_argument("--no-module-path", action="store_true", help="skip the short module-path measurement reported beside the headline")
+    ap.add_argument("--no-module-path", action="store_true", help="--full without the short module-path measurement reported beside the headline")
     a = ap.parse_args()
 
     from gptst_amd import synth
@@ -375,6 +418,7 @@ def main():
         over["hidden_dim"] = a.hidden
     if a.hs:
         over["HS"] = a.hs
+    over["lr_init"] = BENCH_LR
     args = make_args(a.dataset, scaler_zeros=synth.scaler_zeros(), device=str(dev), **over)
     init_seed(args.seed)
     B, T, N, C = a.batch, 12, args.num_nodes, args.hidden_dim
@@ -441,27 +485,22 @@ def main():
         e_ = time.perf_counter() - t_
         return dp.max_over_ranks(e_) if dp is not None else e_
 
-    # the contract command's LITERAL number: exactly --steps steps right behind exactly --warmup warm-up steps (a short run times the clock
-    # ramp: VERDICT r04) — reported as value_exact_warmup beside `value`, which is measured behind the clock warm-up below
+    # --full: the contract command's LITERAL number: exactly --steps steps right behind exactly --warmup warm-up steps (a short run times the
+    # clock ramp: VERDICT r04) — reported as value_exact_warmup beside `value`, which is measured behind the clock warm-up below
     el_exact = None
-    if not a.exact_warmup and a.shard == "batch":
+    if a.full and not a.exact_warmup and a.shard == "batch":
         el_exact = timed(a.steps)
         warm_run += a.steps
     if not a.exact_warmup and a.shard == "batch":
         # clock warm-up: the GPU reaches its steady clocks after ~0.25 s of load; a short run right behind import / capture otherwise times
         # the ramp (measured: --steps 20 reads 815 steps/s behind 5 warm-up steps and 833 behind 200).  Untimed, reported as warmup_steps_run.
-        torch.cuda.synchronize()
-        t_w = time.perf_counter()
-        run(4 * G, a.epoch)
-        torch.cuda.synchronize()
-        per = (time.perf_counter() - t_w) / (4 * G)
-        extra = int(max(0.0, 0.3 - warm_run * per) / max(per, 1e-6)) // G * G
-        extra = min(extra, 2000)
-        if dp is not None:                               # every rank must enqueue the SAME number of steps (their collectives pair up)
-            extra = int(dp.max_over_ranks(extra)) // G * G
+        # A fixed count (CLOCK_WARM_STEPS at the headline shape, fewer for larger steps), the same on every rank: the steps a run takes, and
+        # with them what its timed steps compute (--dump-outputs), depend on its arguments alone.
+        clock = min(CLOCK_WARM_STEPS, -(-CLOCK_WARM_STEPS * 32 * 170 * 64 // (B * N * C)))
+        extra = -(-max(0, clock - warm_run) // G) * G
         if extra > 0:
             run(extra, a.epoch)
-        warm_run += 4 * G + extra
+        warm_run += extra
     el = timed(a.steps)
     loss = stepper.losses()
     rep_rates = [a.steps / el]
@@ -478,10 +517,13 @@ def main():
         if dp is not None:
             elr = dp.max_over_ranks(elr)
         rep_rates.append(a.steps / elr)
+    last = stepper.losses() if a.repeats > 1 else loss            # (on every rank: a step re-run after a lost hand-off holds collectives)
+    if a.dump_outputs and a.path == "step" and rank == 0:         # (loss, loss_flow, loss_s) and gradient of the last timed step, weights and moments after it
+        dump_outputs(a.dump_outputs, dict(loss=last, grad=stepper.gflat, parameters=model.flat, adam_m=stepper.m, adam_v=stepper.v))
 
-    # random-mask phase (epochs 1..change_epoch) rate, informative
+    # --full: random-mask phase (epochs 1..change_epoch) rate, informative
     rnd_rate = None
-    if world == 1 and a.shard != "nodes":
+    if a.full and world == 1 and a.shard != "nodes":
         run(max(5, G), 1)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
@@ -489,11 +531,11 @@ def main():
         torch.cuda.synchronize()
         rnd_rate = max(a.steps // 4, 10) / (time.perf_counter() - t1)
 
-    # per-collective durations (HIP event pair around each RCCL enqueue of three eager steps, on the launch stream) — with the bucketed
+    # --full: per-collective durations (HIP event pair around each RCCL enqueue of three eager steps, on the launch stream) — with the bucketed
     # exchange: the decoder bucket (under the encoder's backward), the encoder bucket and [KL | statistics] behind the chain, the label gather.
     # EVERY rank runs these steps (they hold collectives: a rank that left early would hang the others — ADVICE r04); rank 0 reports.
     coll = {}
-    if dp is not None and getattr(dp, "native", None) is not None and a.shard != "nodes":
+    if a.full and dp is not None and getattr(dp, "native", None) is not None and a.shard != "nodes":
         from gptst_amd import dist as gdist
         graph_was = stepper.use_graph
         stepper.use_graph = False
@@ -535,7 +577,8 @@ def main():
                             if (a.shard == "batch" and a.scaling == "strong") else
                             ("batches of B=%d processed per second by the whole job (= optimizer steps/s x n_gpus under data parallelism)" % B),
         "optimizer_steps_per_s": steps_s,
-        "value_exact_warmup": (a.steps / el_exact * b32_per_step) if el_exact is not None else steps_s * b32_per_step,   # K steps right behind exactly W warm-up steps
+        "value_exact_warmup": (a.steps / el_exact * b32_per_step) if el_exact is not None else   # K steps right behind exactly W warm-up steps
+                              (steps_s * b32_per_step if (a.exact_warmup or a.shard != "batch") else None),     # (None: not measured, see --full)
         "n_gpus": a.gpus, "steps": a.steps, "warmup": a.warmup, "warmup_steps_run": warm_run, "ms_per_step": 1e3 * el / a.steps,
         "higher_is_better": True, "scaling": "strong" if strong else "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         "config": {"workload": "%s: %s-shape synthetic pretrain step, per-GPU B=%d T=%d N=%d C=%d base=%d, epoch %d/300 (%s), "
@@ -578,7 +621,7 @@ def main():
                             "t_mfma_us": 1e6 * flops_alg / MFMA_F32_PEAK, "hbm_frac": (bytes_alg / HBM_PEAK) / t_step,
                             "mfma_frac": (flops_alg / MFMA_F32_PEAK) / t_step}
 
-    if not a.no_kernel_timing and world == 1 and a.shard != "nodes":
+    if a.full and not a.no_kernel_timing and world == 1 and a.shard != "nodes":
         kt = time_kernels(stepper, a.epoch)
         tot = sum(v["total_s"] for v in kt.values())
         ranked = sorted(kt.items(), key=lambda kv: -kv[1]["total_s"])
@@ -628,17 +671,19 @@ def main():
         out["kernel_breakdown_us_per_step"] = {"%s[%s]" % k: round(1e6 * v["total_s"], 1) for k, v in top}
         out["kernel_time_sum_us_per_step_eager"] = round(1e6 * tot, 1)
     out.update(coll)
-    if world == 1 and a.shard != "nodes" and (a.path == "module" or not a.no_module_path):
+    if world == 1 and a.shard != "nodes" and (a.path == "module" or (a.full and not a.no_module_path)):
         stepper = None
         torch.cuda.empty_cache()
-        out["module_path"] = module_path(args, B, a.epoch, dev, steps=a.steps if a.path == "module" else 40)
-        torch.cuda.empty_cache()
-        out["module_path_clipadam"] = module_path(args, B, a.epoch, dev, steps=a.steps if a.path == "module" else 40, clip_adam=True)
+        out["module_path"] = module_path(args, B, a.epoch, dev, steps=a.steps if a.path == "module" else 40,
+                                         dump=a.dump_outputs if a.path == "module" else None)
+        if a.full:
+            torch.cuda.empty_cache()
+            out["module_path_clipadam"] = module_path(args, B, a.epoch, dev, steps=a.steps if a.path == "module" else 40, clip_adam=True)
         if a.path == "module":
             out["value"], out["ms_per_step"] = out["module_path"]["steps_per_s"], out["module_path"]["ms_per_step"]
             out["optimizer_steps_per_s"] = out["value"]
             out["config"]["workload"] += "; PATH = module (reference-style loop over the drop-in nn.Module, not the fused step)"
-    if not a.no_cpu_baseline and world == 1:
+    if a.full and not a.no_cpu_baseline and world == 1:
         out["cpu_baseline"] = cpu_baseline(args, B)
     print(json.dumps(out), flush=True)
     if dp is not None:

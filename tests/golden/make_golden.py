@@ -21,6 +21,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = "/root/reference"
 sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(HERE))
 sys.path.insert(0, REF)
 
 from gptst_amd.config import make_args          # noqa: E402
@@ -114,8 +115,8 @@ def npz(name, **arrs):
         if isinstance(v, torch.Tensor):
             v = v.detach().cpu().numpy()
         out[k] = v
-    np.savez_compressed(os.path.join(HERE, name), **out)
-    print("wrote", name, "%.1f KB" % (os.path.getsize(os.path.join(HERE, name)) / 1024))
+    from golden_util import save                   # shards of < 1 MiB, read back by golden_util.load
+    print("wrote", name, "in %d file(s)" % save(name, out, HERE))
 
 
 # --------------------------------------------------------------------------------------------
@@ -440,8 +441,7 @@ def gen_curve(nsteps=200, per_epoch=50, lr=None, name="curve_c2.npz", perturb_se
         return np.array(losses)
     A["losses"], A["seeds"], A["orders"], A["epoch"] = np.array(losses), np.array(seeds), np.array(orders), np.array(epochs)
     A["masks"] = np.stack(masks)                       # (nsteps, M/8) uint8: the reference's `1 - final_mask` (1 = masked cell)
-    np.savez_compressed(os.path.join(HERE, name), **A)
-    print("wrote", name)
+    npz(name, **A)
 
 
 def gen_curve_envelope(K=8, name="curve_c2_env.npz", perturb_rel=None):

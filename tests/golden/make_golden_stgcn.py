@@ -68,7 +68,9 @@ def main():
     out["fu.a"], out["fu.b"], out["fu.y"] = a.numpy(), b.numpy(), fu(a, b).detach().numpy()
     for k, v in fu.state_dict().items():
         out["fu.sd." + k] = v.numpy()
-    np.savez_compressed(os.path.join(HERE, "stgcn_small.npz"), **out)
+    sys.path.insert(0, os.path.dirname(HERE))
+    from golden_util import save                   # shards of < 1 MiB, read back by golden_util.load
+    save("stgcn_small.npz", out, HERE)
     print("wrote stgcn_small.npz:", len(out), "arrays, y", y.shape, float(y.abs().mean()))
 
 

@@ -9,11 +9,12 @@ import torch
 from gptst_amd import data as gdata, synth
 from gptst_amd.config import make_args
 from oracle import gptst_oracle as O
+from golden_util import load
 
 
 def test_oracle_tracks_reference_curve_first_steps():
     torch.set_num_threads(min(8, os.cpu_count() or 1))
-    fx = np.load(os.path.join(os.path.dirname(__file__), "golden", "curve_c2.npz"))
+    fx = load("curve_c2.npz")
     args = make_args("PEMS08", epochs=int(fx["epochs"]), change_epoch=int(fx["change_epoch"]), batch_size=32)
     raw = synth.make_series(args.num_nodes, 3, interval=5, seed=10)
     train, _, _, scaler, _, _ = gdata.get_dataloader(args, raw=raw)

@@ -53,7 +53,7 @@ def _worker(rank, world, port, q):
     n = buf.numel() - 8
     g = buf[:n] / max(float(buf[n + 1]), 1.0)
     if rank == 0:
-        q.put((g, float(buf[n] / buf[n + 1])))
+        q.put((g.tolist(), float(buf[n] / buf[n + 1])))             # plain lists: the worker may exit before the parent reads
     dp.barrier()
 
 
@@ -69,6 +69,7 @@ def test_dp_allreduce_equals_global_batch_gradient():
     for p in procs:
         p.start()
     g, loss = q.get(timeout=180)
+    g = torch.tensor(g, dtype=torch.float32)
     for p in procs:
         p.join(60)
         assert p.exitcode == 0

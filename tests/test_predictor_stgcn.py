@@ -1,6 +1,5 @@
 """Downstream STGCN predictor against golden vectors generated from the reference implementation
 (tests/golden/make_golden_stgcn.py: reference model/STGCN/stgcn.py, STGCN/args.py graph helpers, Model.py Fusion)."""
-import os
 import types
 
 import numpy as np
@@ -10,8 +9,9 @@ import torch
 from gptst_amd import graph
 from gptst_amd.enhance import Fusion
 from gptst_amd.predictors import STGCN
+from golden_util import load
 
-G = np.load(os.path.join(os.path.dirname(__file__), "golden", "stgcn_small.npz"))
+G = load("stgcn_small.npz")
 
 
 def _model(device="cpu"):

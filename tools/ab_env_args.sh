@@ -4,7 +4,7 @@
 rounds=$1; shift
 for r in $(seq $rounds); do
   for e in "$@"; do
-    v=$(env $e python bench.py $BENCH_ARGS --no-cpu-baseline --no-kernel-timing --no-module-path 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.2f steps/s  %.4f ms  random-mask %s' % (d['value'], d['ms_per_step'], d.get('steps_per_s_random_mask_phase')))")
+    v=$(env $e python bench.py --full $BENCH_ARGS --no-cpu-baseline --no-kernel-timing --no-module-path 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.2f steps/s  %.4f ms  random-mask %s' % (d['value'], d['ms_per_step'], d.get('steps_per_s_random_mask_phase')))")
     echo "[${e:-default}]: $v"
   done
 done

@@ -5,7 +5,7 @@
 rounds=$1; shift
 for r in $(seq $rounds); do
   for lib in "$@"; do
-    v=$(GPTST_LIB=$PWD/$lib python bench.py --steps 320 --warmup 24 --no-cpu-baseline --no-kernel-timing 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f steps/s  %.4f ms  random-mask %.1f' % (d['value'], d['ms_per_step'], d['steps_per_s_random_mask_phase']))")
+    v=$(GPTST_LIB=$PWD/$lib python bench.py --full --steps 320 --warmup 24 --no-cpu-baseline --no-kernel-timing 2>/dev/null | tail -1 | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.1f steps/s  %.4f ms  random-mask %.1f' % (d['value'], d['ms_per_step'], d['steps_per_s_random_mask_phase']))")
     echo "$lib: $v"
   done
 done

@@ -14,11 +14,11 @@ python tools/pmc_to_json.py gpurun_out/pmc_${tag}_FETCH_SIZE.txt gpurun_out/pmc_
 cp gpurun_out/${tag}_pmc_traffic.json profiles/pmc_traffic.json      # so that the bench runs below report `traffic`
 python tools/trace_to_json.py gpurun_out/${tag}_trace.txt gpurun_out/${tag}_graph_kernel_us.json
 cp gpurun_out/${tag}_graph_kernel_us.json profiles/graph_kernel_us.json   # ... and `avg_us_graph` (the graph-replay durations beside the eager event pairs)
-python bench.py --steps 200 --warmup 20 2>/dev/null | tail -1 > gpurun_out/${tag}_bench.json
-python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/${tag}_bench_driver_cmd.json
+python bench.py --full --steps 200 --warmup 20 2>/dev/null | tail -1 > profiles/${tag}_bench.json
+python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > profiles/${tag}_bench_driver_cmd.json
 head -4 gpurun_out/${tag}_trace.txt; tail -3 gpurun_out/${tag}_timeline.txt
 python -c "
 import json
 for f in ('${tag}_bench','${tag}_bench_driver_cmd'):
-    d=json.load(open('gpurun_out/%s.json'%f)); print(f, d['value'], d['ms_per_step'], d.get('roofline',{}).get('frac'), d.get('roofline',{}).get('traffic'))
+    d=json.load(open('profiles/%s.json'%f)); print(f, d['value'], d['ms_per_step'], d.get('roofline',{}).get('frac'), d.get('roofline',{}).get('traffic'))
 "
