@@ -8,6 +8,7 @@
 // forward: replaces gptst_lin_in + gptst_apply(MODE_NODE) (6.6 + 12.2 us, 3 x 16.7 MB) by one 16.7 MB write; backward: replaces
 // gptst_apply_wgrad(MODE_NODE) + gptst_rowouter_part (19.3 + 10.7 us) by one pass over dPre.  base = 1, C in {64, 128}.
 #include "mfma_tile.h"
+#include "kl_guest.h"         // guide_in_bwd_body (the backward also runs as a guest of the hyperTem forward chain)
 
 #define GI_CHUNKS 3       // row chunks per node in the forward (510 workgroups at N = 170)
 
@@ -63,55 +64,8 @@ template <int C>
 __global__ __launch_bounds__(256) void guide_in_bwd_kernel(const float* __restrict__ dPre, const float* __restrict__ src, int lda,
                                                            const float* __restrict__ w1, const float* __restrict__ b1, const float* __restrict__ Wn,
                                                            float* __restrict__ dWb, float* __restrict__ dinp, int BT, int N) {
-    constexpr int LPR = C / 4, RPP = 256 / LPR, U = 6, PP = 256 / C;
-    __shared__ __attribute__((aligned(16))) float red[RPP * 2 * C];
-    __shared__ __attribute__((aligned(16))) float vec[2 * C];
-    const int n = blockIdx.x, tid = threadIdx.x;
-    const int slot = tid / LPR, c4 = tid % LPR;
-    float4 P = f4zero(), Q = f4zero();
-    for (int rr = slot; rr < BT; rr += RPP * U) {             // U rows of loads in flight per thread (rows of node n: stride N*C floats)
-        float4 d[U];
-        float s[U];
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            const size_t r = (size_t)min(rr + u * RPP, BT - 1) * N + n;
-            d[u] = ld4(dPre + r * C + 4 * c4);
-            s[u] = src[r * lda];
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u)
-            if (rr + u * RPP < BT) { P = f4fma(s[u], d[u], P); Q = f4add(Q, d[u]); }
-    }
-    st4(red + (slot * 2 + 0) * C + 4 * c4, P); st4(red + (slot * 2 + 1) * C + 4 * c4, Q);
-    __syncthreads();
-    for (int i = tid; i < 2 * C; i += 256) {                 // fold the slots in order
-        float s = 0.f;
-#pragma unroll 4
-        for (int sl = 0; sl < RPP; ++sl) s += red[(sl * 2 + i / C) * C + i % C];
-        vec[i] = s;
-    }
-    __syncthreads();
-    float* row = dWb + (size_t)n * (C * C + C);
-    for (int f = tid; f < C * C / 4; f += 256) {             // dW_n = w1^T (x) p + b1^T (x) q
-        const int i = f / LPR, o4 = f % LPR;
-        const float wi = w1[i], bb = b1[i];
-        const float4 p4 = ld4(vec + 4 * o4), q4 = ld4(vec + C + 4 * o4);
-        st4(row + (size_t)i * C + 4 * o4, make_float4(fmaf(wi, p4.x, bb * q4.x), fmaf(wi, p4.y, bb * q4.y), fmaf(wi, p4.z, bb * q4.z), fmaf(wi, p4.w, bb * q4.w)));
-    }
-    if (tid < C) row[C * C + tid] = vec[C + tid];            // db_n
-    {   // [W_n p | W_n q]: thread (input channel i, part of the output channels)
-        const int i = tid / PP, pq = tid % PP;
-        const float* Wr = Wn + (size_t)n * C * C + (size_t)i * C + pq * (C / PP);
-        float r1 = 0.f, r2 = 0.f;
-#pragma unroll
-        for (int k = 0; k < C / PP / 4; ++k) {
-            const float4 x = ld4(Wr + 4 * k);
-            r1 += f4dot(x, ld4(vec + pq * (C / PP) + 4 * k));
-            r2 += f4dot(x, ld4(vec + C + pq * (C / PP) + 4 * k));
-        }
-        r1 = group_sum<PP>(r1); r2 = group_sum<PP>(r2);
-        if (pq == 0) { dinp[(size_t)n * 2 * C + i] = r1; dinp[(size_t)n * 2 * C + C + i] = r2; }
-    }
+    __shared__ __attribute__((aligned(16))) float lds[guide_in_bwd_lds_floats<C>()];     // (body: kl_guest.h)
+    guide_in_bwd_body<C>(dPre, src, lda, w1, b1, Wn, dWb, dinp, BT, N, blockIdx.x, lds);
 }
 
 // h1 (BT*N, C) = LReLU((s w1 + b1) W_n + b_n):  src rows (BT*N, lda) with the flow in column 0, w1 = MLP_RL.ln1.weight (C,1), b1 = its bias,

@@ -7,6 +7,7 @@
 //   LeakyReLU, stored as whole rows.  Replaces tmix_kernel + apply_kernel<TIME> (11 + 20 us -> one launch) and the R round trip.
 #include "mfma_tile.h"
 #include "wgrad64.h"
+#include "kl_guest.h"
 GPTST_STAMP_TABLES(hypertem)
 GPTST_HANDOFF_COUNTER(hypertem)      // -DGPTST_STAMPS: per-phase / per-workgroup wall-clock stamps of the pair launch (tools/phase_stamps.py ht_bwd_pair)
 
@@ -660,14 +661,21 @@ struct HtChain {
 #ifndef HTC_NW
 #define HTC_NW 4
 #endif
-template <int NSTAGE>
-__global__ __launch_bounds__(64 * HTC_NW, HTC_NW == 6 ? 3 : HT_OCC) void hypertem_chain_fwd_kernel(HtChain ch, int N, int B) {
+// GUEST 1..3 (gptst_hypertem_chain_fwd_kl): the workgroups from kg.base on are not the chain's — each runs one block of that stage of the KL
+// path (kl_guest.h) with the launch's dynamic LDS.  They come after the chain's own workgroups in dispatch order, so they fill the slots the
+// one-round grid leaves empty (352 workgroups on 512 slots at the bench shape) and the CUs whose chain workgroups finish early.
+template <int NSTAGE, int GUEST>
+__global__ __launch_bounds__(64 * HTC_NW, HTC_NW == 6 ? 3 : HT_OCC) void hypertem_chain_fwd_kernel(HtChain ch, int N, int B, KlGuest kg) {
     constexpr int C = 64, P = C + 4, GP = 145, NT = 16, NW = HTC_NW, NTH = 64 * NW, TPW = HT_T / NW;      // TPW time steps per wave
     static_assert(HT_T % NW == 0 && (HT_T * NT * (C / 4)) % NTH == 0 && (NT * 144) % NTH == 0, "waves must divide the steps and the staging loops");
     constexpr int GK = NT * 144 / NTH, XK = HT_T * NT * (C / 4) / NTH;                                     // staging trips per thread
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* Xs = smem;                               // [12][NT][P]
     float* Gs = Xs + HT_T * NT * P;                 // [NT][GP]
+    if constexpr (GUEST != 0) {
+        static_assert(NTH == 256, "the guest bodies are written for 256 threads");
+        if ((int)blockIdx.x >= kg.base) { kl_guest_run<GUEST>(kg, kg.v0 + (int)blockIdx.x - kg.base, smem); return; }
+    }
     int b, tile;
     if (!ht_work((N + NT - 1) / NT, B, b, tile)) return;
     const int n0 = tile * NT;
@@ -845,11 +853,10 @@ __global__ __launch_bounds__(64 * HTC_NW, HTC_NW == 6 ? 3 : HT_OCC) void hyperte
 
 // X: input of the first hyperTem layer;  Gs .. outs: HOST arrays of nstage device pointers (G (N,T,T), Wbt (BT,C,C), bbt (BT,C), R_out or NULL,
 // out), read at call time.  C = 64 only (GPTST_ESHAPE otherwise: use the per-layer entry points).
-extern "C" int gptst_hypertem_chain_fwd(const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs,
-                                        const void* outs, int B, int T, int N, int C, void* stream) {
+static int ht_chain_args(HtChain& ch, const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs, const void* outs,
+                         int B, int T, int N, int C) {
     if (!X || nstage < 1 || nstage > 3 || !Gs || !Wbts || !bbts || !Rs || !outs || T != HT_T || B <= 0 || N <= 0) return GPTST_EARG;
     if (C != 64) return GPTST_ESHAPE;
-    HtChain ch;
     ch.nstage = nstage; ch.X = X;
     for (int s = 0; s < 3; ++s) {
         const int k = s < nstage ? s : nstage - 1;
@@ -857,15 +864,86 @@ extern "C" int gptst_hypertem_chain_fwd(const float* X, int nstage, const void* 
                            ((float* const*)Rs)[k], ((float* const*)outs)[k]};
         if (!ch.st[s].G || !ch.st[s].Wbt || !ch.st[s].bbt || !ch.st[s].out) return GPTST_EARG;
     }
-    const dim3 grid(8 * ((B + 7) / 8) * ((N + 15) / 16));
+    return GPTST_OK;
+}
+
+static int ht_chain_grid(int B, int N) { return 8 * ((B + 7) / 8) * ((N + 15) / 16); }
+
+extern "C" int gptst_hypertem_chain_fwd(const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs,
+                                        const void* outs, int B, int T, int N, int C, void* stream) {
+    HtChain ch;
+    const int rc = ht_chain_args(ch, X, nstage, Gs, Wbts, bbts, Rs, outs, B, T, N, C);
+    if (rc != GPTST_OK) return rc;
+    const dim3 grid(ht_chain_grid(B, N));
     const int smem = (int)ht_smem(16);
     hipStream_t st = (hipStream_t)stream;
+    const KlGuest none{};
 #define HTC_LAUNCH(NS_) do {                                                                                                          \
         static int done_ = 0;                                                                                                          \
-        if (!done_) { (void)hipFuncSetAttribute((const void*)hypertem_chain_fwd_kernel<NS_>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); done_ = 1; } \
-        hipLaunchKernelGGL((hypertem_chain_fwd_kernel<NS_>), grid, dim3(64 * HTC_NW), smem, st, ch, N, B);                                     \
+        if (!done_) { (void)hipFuncSetAttribute((const void*)hypertem_chain_fwd_kernel<NS_, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); done_ = 1; } \
+        hipLaunchKernelGGL((hypertem_chain_fwd_kernel<NS_, 0>), grid, dim3(64 * HTC_NW), smem, st, ch, N, B, none);                          \
     } while (0)
     if (nstage == 1) HTC_LAUNCH(1); else if (nstage == 2) HTC_LAUNCH(2); else HTC_LAUNCH(3);
+#undef HTC_LAUNCH
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}
+
+GPTST_INTERNAL int gptst_tail_geometry(int rows, int* rows_per_block);
+GPTST_INTERNAL int gptst_apply_wgrad_geometry(int mode, int BT, int N, int* tpw);
+
+extern "C" int gptst_kl_guest_blocks(int stage, int B, int T, int N) {
+    if (B <= 0 || T <= 0 || N <= 0) return GPTST_EARG;
+    int aux;
+    if (stage == 1) return gptst_tail_geometry(B * T * N, &aux);
+    if (stage == 2) return B * T * gptst_apply_wgrad_geometry(0, B * T, N, &aux);
+    if (stage == 3) return N;
+    return GPTST_EARG;
+}
+
+// the two-layer chain with virtual blocks [v0, v1) of one KL-path stage as guest workgroups behind its own grid (kl_guest.h).  ops: HOST array of
+// the stage's device pointers —  1: h2, W3, prob, c, d_h2, part, sws (gptst_tail_kl with premul = 1);  2: d_h2, h1, W_bt, d_h1, dW, db
+// (gptst_apply_wgrad MODE_TIME, Y = NULL, premul = 1);  3: dPre, src, w1, b1, Wn, dWb, dinp (gptst_guide_in_bwd; src rows of lda floats).
+extern "C" int gptst_hypertem_chain_fwd_kl(const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs,
+                                           const void* outs, int B, int T, int N, int C, int stage, const void* ops, int v0, int v1, int HS,
+                                           int lda, float w, void* stream) {
+    HtChain ch;
+    const int rc = ht_chain_args(ch, X, nstage, Gs, Wbts, bbts, Rs, outs, B, T, N, C);
+    if (rc != GPTST_OK) return rc;
+    if (!ops || stage < 1 || stage > 3) return GPTST_EARG;
+    if (nstage != 2 || HTC_NW != 4 || HS <= 0 || HS > TL_MAXJ) return GPTST_ESHAPE;
+    const int nv = gptst_kl_guest_blocks(stage, B, T, N);
+    if (v0 < 0 || v1 <= v0 || v1 > nv) return GPTST_EARG;
+    const float* const* p = (const float* const*)ops;
+    const int np = stage == 1 ? 7 : stage == 2 ? 6 : 7;
+    for (int i = 0; i < np; ++i) if (!p[i]) return GPTST_EARG;
+    KlGuest kg{};
+    kg.base = ht_chain_grid(B, N);
+    kg.v0 = v0;
+    if (stage == 1) {
+        TailArgs& t = kg.tail;
+        t.X = p[0]; t.W = p[1]; t.prob = p[2]; t.c = p[3]; t.dX = (float*)p[4]; t.part = (float*)p[5]; t.sws = (float*)p[6];
+        t.rows = B * T * N; t.J = HS; t.N = N; t.w = w; t.premul = 1;
+        gptst_tail_geometry(t.rows, &t.rows_per_block);
+    } else if (stage == 2) {
+        kg.dOut = p[0]; kg.S = p[1]; kg.W = p[2]; kg.dS = (float*)p[3]; kg.dW = (float*)p[4]; kg.colsum = (float*)p[5];
+        kg.rm = make_rowmap(0, B * T, N);
+        gptst_apply_wgrad_geometry(0, B * T, N, &kg.tpw);
+    } else {
+        if (lda <= 0) return GPTST_EARG;
+        kg.dPre = p[0]; kg.src = p[1]; kg.lda = lda; kg.w1 = p[2]; kg.b1 = p[3]; kg.Wn = p[4]; kg.dWb = (float*)p[5]; kg.dinp = (float*)p[6];
+        kg.BT = B * T; kg.N = N;
+    }
+    const dim3 grid(kg.base + (v1 - v0));
+    const size_t sg = kl_guest_lds_bytes(stage), sh = ht_smem(16);
+    const int smem = (int)(sg > sh ? sg : sh);
+    hipStream_t st = (hipStream_t)stream;
+#define HTC_LAUNCH(G_) do {                                                                                                           \
+        static int done_ = 0;                                                                                                          \
+        if (!done_) { (void)hipFuncSetAttribute((const void*)hypertem_chain_fwd_kernel<2, G_>, hipFuncAttributeMaxDynamicSharedMemorySize, smem); done_ = 1; } \
+        hipLaunchKernelGGL((hypertem_chain_fwd_kernel<2, G_>), grid, dim3(64 * HTC_NW), smem, st, ch, N, B, kg);                           \
+    } while (0)
+    if (stage == 1) HTC_LAUNCH(1); else if (stage == 2) HTC_LAUNCH(2); else HTC_LAUNCH(3);
 #undef HTC_LAUNCH
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;

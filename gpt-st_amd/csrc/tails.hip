@@ -15,20 +15,9 @@
 // atomics, the result does not depend on scheduling.  (Measured: 510 same-address atomics at the end of a launch — the stats
 // themselves, or a "last workgroup folds" ticket — cost ~8 us; one extra 1-workgroup launch costs 2.5.)
 // C in {64, 128}, J <= TL_MAXJ; other shapes use the unfused ops.
-#include "common.h"
+#include "kl_guest.h"         // TailArgs, tail_mfma_body (the KL head also runs as a guest of the hyperTem forward chain)
 
 #define TL_NB 512
-#define TL_MAXJ 16
-
-struct TailArgs {
-    const float* X; const float* W; const float* b; float* dX; float* part; float* sws;
-    int rows, J, rows_per_block;
-    // mae tail
-    const float* src; const float* mask; float* out; int lda; float sigma, mu, thresh;
-    // kl head
-    const float* prob; const float* c; int N; float w;
-    int premul;          // dPre chain: dX is multiplied by lrelu'(X) (X = the output of a LeakyReLU layer), include/gptst_hip.h
-};
 
 template <int KIND, int C>      // KIND 0: mae tail, 1: kl head
 __global__ __launch_bounds__(256) void tail_kernel(TailArgs t) {
@@ -141,167 +130,11 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs t) {
     }
 }
 
-// ---- the same two heads on MFMA 16x16x4 (C = 64, r03) ------------------------------------------------------------------------------------
-// tail_kernel spends its time in J dot products per row (4 FMAs + a 4-step DPP reduction each), J rank-1 updates of the data gradient and J
-// of the weight gradient per row.  Here a wave takes 16-row tiles and the three products are matrix products with register operands:
-//   Z  (16 rows x 16 classes) = X . W^T          A = X rows straight from global (lane (j,kk): row j, channels 16q+4kk..), B = W[class j][..]
-//   dX (16 rows x 64)         = a . W            A = a through a wave-private LDS tile (D layout -> A layout), B = W[class][4j+ct] (float4)
-//   gW (16 classes x 64)     += a^T . X          A = a in the D layout as it is (step s <-> row 4kk+s), B = X rows in the D layout (float4)
-// D layout of Z / a: lane (j = class, kk), register r <-> row 4kk + r, so the per-row softmax terms run across the 16 lanes of a DPP row.
-// Same outputs as tail_kernel (out, dX, part[blk][J*C + J], sws[blk][4]); sums are accumulated in a different order (tolerance-checked).
-template <int KIND, int C>      // C = 128 (r05): the D-layout operands come in two 64-channel halves hf (channel 64 hf + 4j + ct)
+// ---- the same two heads on MFMA 16x16x4 (C = 64, r03): kl_guest.h, tail_mfma_body --------------------------------------------------------
+template <int KIND, int C>
 __global__ __launch_bounds__(256) void tail_mfma_kernel(TailArgs t) {
-    constexpr int Q = C / 16, HF = C / 64;
-    __shared__ float at[4][16][17];                     // per wave: a[row][class] (D layout -> A layout)
-    __shared__ __attribute__((aligned(16))) float fold[4][16 * C + 16];
-    __shared__ float reds[2][4];
-    const int J = t.J;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int j = lane & 15, kk = lane >> 4;
-    // W as B operand of Z (class j, channels 16q + 4kk ..) and of dX (class 4s + kk, channels 4j .. 4j+3)
-    float4 bz[Q], bd[HF][4];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) bz[q] = (KIND == 0 && j < J) ? ld4(t.W + (size_t)j * C + 16 * q + 4 * kk) : f4zero();
-#pragma unroll
-    for (int hf = 0; hf < HF; ++hf)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) bd[hf][q] = (4 * q + kk < J) ? ld4(t.W + (size_t)(4 * q + kk) * C + 64 * hf + 4 * j) : f4zero();
-    const float bj = (KIND == 0 && t.b != nullptr && j < J) ? t.b[j] : 0.f;
-    const int nks = (J + 3) / 4;                        // k-steps of the dX product
-    f32x4 gw[HF][4];
-#pragma unroll
-    for (int hf = 0; hf < HF; ++hf)
-#pragma unroll
-        for (int ct = 0; ct < 4; ++ct) gw[hf][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float gb = 0.f, s0 = 0.f, s1 = 0.f;
-    const size_t r0 = (size_t)blockIdx.x * t.rows_per_block;
-    const size_t r1 = min((size_t)t.rows, r0 + t.rows_per_block);
-    for (size_t tb = r0 + 16 * wave; tb < r1; tb += 64) {
-        // X tile in both layouts (the second read hits L1): A layout for Z, D layout for gW / the LeakyReLU sign
-        float4 xa[Q], xd[HF][4];
-        if (KIND == 0) {
-#pragma unroll
-            for (int q = 0; q < Q; ++q) xa[q] = ld4(t.X + min(tb + j, r1 - 1) * C + 16 * q + 4 * kk);
-        }
-#pragma unroll
-        for (int hf = 0; hf < HF; ++hf)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) xd[hf][q] = ld4(t.X + min(tb + 4 * kk + q, r1 - 1) * C + 64 * hf + 4 * j);
-        // the epilogue's per-row operands travel with the X tile (after the MFMAs they were a second, dependent round trip per tile)
-        float o0[4], o1[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t i = min(tb + 4 * kk + r, r1 - 1);
-            const int jc = min(j, J - 1);
-            if (KIND == 0) { o0[r] = t.mask[i * J + jc]; o1[r] = t.src[i * t.lda + jc]; }
-            else { const size_t bt = i / t.N, n = i % t.N; o0[r] = t.c[(bt * J + jc) * t.N + n]; o1[r] = t.prob[i * J + jc]; }
-        }
-        SB();
-        float a[4];
-        if (KIND == 0) {
-            f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int q = 0; q < Q; ++q) {
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q].x, bz[q].x, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q].y, bz[q].y, acc1, 0, 0, 0);
-                acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q].z, bz[q].z, acc0, 0, 0, 0);
-                acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(xa[q].w, bz[q].w, acc1, 0, 0, 0);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const size_t i = tb + 4 * kk + r;
-                a[r] = 0.f;
-                if (i < r1 && j < J) {
-                    const float o = acc0[r] + acc1[r] + bj;
-                    const size_t e = i * J + j;
-                    const float M = 1.f - o0[r];
-                    const float p = (o * t.sigma + t.mu) * M;
-                    const float y = (o1[r] * t.sigma + t.mu) * M;
-                    if (y > t.thresh) {
-                        const float d = p - y;
-                        s0 += fabsf(d); s1 += 1.f;
-                        a[r] = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * M * t.sigma;
-                    }
-                    t.out[e] = o;
-                }
-            }
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const size_t i = tb + 4 * kk + r;
-                const bool ok = i < r1 && j < J;
-                float e_ = 0.f, p_ = 1.f;
-                if (ok) { e_ = o0[r]; p_ = o1[r]; }
-                const float se = group_sum<16>(e_);
-                if (ok && e_ > 0.f) s0 += e_ * (logf(e_) - logf(p_));
-                a[r] = ok ? t.w * (p_ * se - e_) : 0.f;
-            }
-        }
-        // ---- gW += a^T X (step s <-> row 4kk + s on both operands), gb += column sums of a ----
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            gb += a[r];
-#pragma unroll
-            for (int hf = 0; hf < HF; ++hf) {
-                gw[hf][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], xd[hf][r].x, gw[hf][0], 0, 0, 0);
-                gw[hf][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], xd[hf][r].y, gw[hf][1], 0, 0, 0);
-                gw[hf][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], xd[hf][r].z, gw[hf][2], 0, 0, 0);
-                gw[hf][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[r], xd[hf][r].w, gw[hf][3], 0, 0, 0);
-            }
-        }
-        // ---- dX = a W: a from the D layout into the A layout (lane (i = row, kk): classes 4s + kk) through the wave's tile ----
-#pragma unroll
-        for (int r = 0; r < 4; ++r) at[wave][4 * kk + r][j] = a[r];
-        f32x4 dx[HF][4];
-#pragma unroll
-        for (int hf = 0; hf < HF; ++hf)
-#pragma unroll
-            for (int ct = 0; ct < 4; ++ct) dx[hf][ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            if (s < nks) {                                           // uniform
-                const float as = at[wave][j][4 * s + kk];
-#pragma unroll
-                for (int hf = 0; hf < HF; ++hf) {
-                    dx[hf][0] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bd[hf][s].x, dx[hf][0], 0, 0, 0);
-                    dx[hf][1] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bd[hf][s].y, dx[hf][1], 0, 0, 0);
-                    dx[hf][2] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bd[hf][s].z, dx[hf][2], 0, 0, 0);
-                    dx[hf][3] = __builtin_amdgcn_mfma_f32_16x16x4f32(as, bd[hf][s].w, dx[hf][3], 0, 0, 0);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const size_t i = tb + 4 * kk + r;
-#pragma unroll
-            for (int hf = 0; hf < HF; ++hf) {
-                float4 v = make_float4(dx[hf][0][r], dx[hf][1][r], dx[hf][2][r], dx[hf][3][r]);
-                if (t.premul) {
-                    v.x *= lrelu_grad_from_out(xd[hf][r].x); v.y *= lrelu_grad_from_out(xd[hf][r].y);
-                    v.z *= lrelu_grad_from_out(xd[hf][r].z); v.w *= lrelu_grad_from_out(xd[hf][r].w);
-                }
-                if (i < r1) st4(t.dX + i * C + 64 * hf + 4 * j, v);
-            }
-        }
-    }
-    // ---- fold the four waves: gW (D reg r of tile ct: class 4kk + r, channel 4j + ct), gb, loss statistics ----
-#pragma unroll
-    for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int hf = 0; hf < HF; ++hf) st4(&fold[wave][(4 * kk + r) * C + 64 * hf + 4 * j], make_float4(gw[hf][0][r], gw[hf][1][r], gw[hf][2][r], gw[hf][3][r]));
-    gb += __shfl_xor(gb, 16, 64); gb += __shfl_xor(gb, 32, 64);
-    if (kk == 0) fold[wave][16 * C + j] = gb;
-    s0 = group_sum<64>(s0); s1 = group_sum<64>(s1);
-    if (lane == 0) { reds[0][wave] = s0; reds[1][wave] = s1; }
-    __syncthreads();
-    float* mine = t.part + (size_t)blockIdx.x * (J * C + J);
-    for (int o = threadIdx.x; o < J * C; o += 256) mine[o] = (fold[0][o] + fold[1][o]) + (fold[2][o] + fold[3][o]);
-    if ((int)threadIdx.x < J) mine[J * C + threadIdx.x] = (fold[0][16 * C + threadIdx.x] + fold[1][16 * C + threadIdx.x]) + (fold[2][16 * C + threadIdx.x] + fold[3][16 * C + threadIdx.x]);
-    if (threadIdx.x == 0) {
-        float* w = t.sws + 4 * (size_t)blockIdx.x;
-        const float v0 = (reds[0][0] + reds[0][1]) + (reds[0][2] + reds[0][3]), v1 = (reds[1][0] + reds[1][1]) + (reds[1][2] + reds[1][3]);
-        if (KIND == 0) { w[0] = v0; w[1] = v1; } else { w[2] = v0; }
-    }
+    __shared__ __attribute__((aligned(16))) float lds[tail_mfma_lds_floats<C>()];
+    tail_mfma_body<KIND, C>(t, blockIdx.x, lds);
 }
 
 // stats[k] += sum over rows of sws[row][k], k < 3, in a fixed order (thread t: rows t, t+256, ...; then a fixed tree)
@@ -337,6 +170,8 @@ static void tl_geometry(int rows, int& nb, int& rpb) {
 
 // number of row-chunk partials that gptst_tail_mae / gptst_tail_kl write: part must hold that many x (J*C + J) floats
 extern "C" int gptst_tail_parts(int rows) { int nb, rpb; tl_geometry(rows, nb, rpb); return nb; }
+// ... and the rows per chunk, for a launch that carries the KL head as guests
+GPTST_INTERNAL int gptst_tail_geometry(int rows, int* rows_per_block) { int nb; tl_geometry(rows, nb, *rows_per_block); return nb; }
 
 GPTST_INTERNAL const unsigned* gptst_handoff_word_capmfma(void);
 GPTST_INTERNAL const unsigned* gptst_handoff_word_hypertem(void);

@@ -258,6 +258,7 @@ def hypertem_core_bwd(saved, dout, dG_out, dims, chain=False, premul=False):
 
 CARRY_RED = os.environ.get("GPTST_CARRY_RED", "1") == "1"        # queued weight-gradient reductions as role workgroups of the routing backward (r05, late)
 CARRY_MB = float(os.environ.get("GPTST_CARRY_MB", "25"))        # at most this much of them per launch
+CARRY_KL = os.environ.get("GPTST_CARRY_KL", "1") == "1"        # the KL path's backward as guests of the forward's chain launches (KlCarry; 0: after model_bwd)
 PAIR_UNDER_DP = os.environ.get("GPTST_PAIR_UNDER_DP", "1") == "1"    # the decoder-hyperTem1 / encoder-hyperTem4 pair also when the decoder's gradient bucket leaves early (r05)
 PAIR_BWD = os.environ.get("GPTST_PAIR_BWD", "1") == "1"        # two adjacent hyperTem layers' backward in one launch (r04)
 
@@ -369,10 +370,11 @@ def chain_fwd_ok(dims):
     return CHAIN_FWD and dims[3] == 64 and not DROP_R      # (node shards too: the chained layers are node-local, r05)
 
 
-def ht_chain_fwd(x, stages, dims):
-    """consecutive hyperTem layers in one launch -> [saved tuple per layer], last output.  stages: [(G, Wbt, bbt), ...]"""
+def ht_chain_fwd(x, stages, dims, kl=None):
+    """consecutive hyperTem layers in one launch -> [saved tuple per layer], last output.  stages: [(G, Wbt, bbt), ...]
+    kl: the step's KlCarry — the launch carries its next KL-path stage as guest workgroups, if one is due"""
     B, T, N, C = dims
-    res = ops.hypertem_chain_fwd(x.view(B, T, N, C), stages)
+    res = ops.hypertem_chain_fwd(x.view(B, T, N, C), stages, guest=kl.guest() if kl is not None else None)
     saved, xin = [], x
     for (G, Wbt, _b), (R, o) in zip(stages, res):
         o = o.view(-1, C)
@@ -456,13 +458,17 @@ def condlin_fwd(x, Wg, bg, mode, dims):
     return out, (x, out, Wg)
 
 
-def condlin_bwd(saved, dout, emb, wpool, bpool, g_wpool, g_bpool, d_emb, mode, dims, red, chain=False, premul=False):
-    """chain: dout already is dPre;  premul (chain only): dx is returned multiplied by lrelu'(x)."""
+def condlin_bwd(saved, dout, emb, wpool, bpool, g_wpool, g_bpool, d_emb, mode, dims, red, chain=False, premul=False, carried=None):
+    """chain: dout already is dPre;  premul (chain only): dx is returned multiplied by lrelu'(x).
+    carried: (dx, dW, db, ns) of the fused C = 64 pass already run by an earlier launch (KlCarry): only the reductions are queued."""
     B, T, N, C = dims
     x, out, Wg = saved
     R, K = emb.shape
     assert not chain or chain_ok(dims)
-    if C == 64:
+    if carried is not None:
+        dx, dW, db, ns = carried
+        nsb = ns
+    elif C == 64:
         dx, dW, db, ns = ops.apply_wgrad(dout, None if chain else out, x, Wg, mode, B * T, N, premul=chain and premul)
         nsb = ns
     elif chain:     # C = 128, dPre chain
@@ -557,9 +563,10 @@ def gen_all(p, tidx, dims, which=(ENC, DEC), guide=True, defer=False):
     return res
 
 
-def sthcn_fwd(p, pfx, tidx, x, dims, num_route, gen=None, head=None, next_gen=None):
+def sthcn_fwd(p, pfx, tidx, x, dims, num_route, gen=None, head=None, next_gen=None, kl=None):
     """head: (x after hyperTem1, its saved tuple) when the previous STHCN's last chain already ran this one's first layer;
-    next_gen: gen dict of the NEXT STHCN — its hyperTem1 then rides on this one's last chain; -> x, c1, saved[, next head]."""
+    next_gen: gen dict of the NEXT STHCN — its hyperTem1 then rides on this one's last chain; -> x, c1, saved[, next head].
+    kl: the step's KlCarry (the chain launches carry the KL path's backward; the encoder's first cap assignment is its last input)."""
     if gen is None:
         gen = gen_all(p, tidx, dims, which=(pfx,), guide=False)[pfx]
     A_all, hts, cps, d, Hm, ds, HS, HT = gen["gen"]
@@ -573,10 +580,12 @@ def sthcn_fwd(p, pfx, tidx, x, dims, num_route, gen=None, head=None, next_gen=No
     if chain_fwd_ok(dims):
         # hyperTem PAIRS on the slab (the caps' node layers stay on the node-grouped apply64)
         x, c1, sv["c1"] = cap_core_fwd(p, cps[0], x, dadj[0], dyn[0], Wn[0], Wn[1], dims, num_route, HS, HT)
-        (sv["h2"], sv["h3"]), x = ht_chain_fwd(x, [(G_all[1], Wb[2], Wb[3]), (G_all[2], Wb[4], Wb[5])], dims)
+        if kl is not None and kl.c1 is None:
+            kl.c1 = c1                                     # (the encoder's: GPTST.py:141, 426)
+        (sv["h2"], sv["h3"]), x = ht_chain_fwd(x, [(G_all[1], Wb[2], Wb[3]), (G_all[2], Wb[4], Wb[5])], dims, kl)
         x, _, sv["c2"] = cap_core_fwd(p, cps[1], x, dadj[1], dyn[1], Wn[2], Wn[3], dims, num_route, HS, HT)
         if next_gen is not None:
-            hs, xl = ht_chain_fwd(x, [(G_all[3], Wb[6], Wb[7]), (next_gen["G_all"][0], next_gen["Wb"][0], next_gen["Wb"][1])], dims)
+            hs, xl = ht_chain_fwd(x, [(G_all[3], Wb[6], Wb[7]), (next_gen["G_all"][0], next_gen["Wb"][0], next_gen["Wb"][1])], dims, kl)
             sv["h4"] = hs[0]
             x = hs[0][2]
             nhead = (xl, hs[1])
@@ -778,18 +787,19 @@ def loss_tail(p, g, dec, source, mask, base, sigma, mu, thresh, sws, red, chain=
     return out, dd
 
 
-def kl_head(p, g, sv_g, prob, c1, N, w, sws, red, chain=False):
+def kl_head(p, g, sv_g, prob, c1, N, w, sws, red, chain=False, carried=None):
     """0.1 KL(eb || prob) and the backward through softmax + MLP_RL.ln3 in one pass over h2 -> d_h2 (guide_bwd(dh2=...));
-    chain: multiplied by lrelu'(h2)."""
+    chain: multiplied by lrelu'(h2).  carried: (d_h2, part) already computed by an earlier launch (KlCarry): only the reduction is queued."""
     m = "encoder.MLP_RL."
-    dh2, part = ops.tail_kl(sv_g[3], p[m + "ln3.weight"], prob, c1, N, w, sws, premul=chain)
+    dh2, part = carried if carried is not None else ops.tail_kl(sv_g[3], p[m + "ln3.weight"], prob, c1, N, w, sws, premul=chain)
     red.jobs.bwd_pool(_ones(prob.device, part.shape[0]), part, _wb_view(g[m + "ln3.weight"], g[m + "ln3.bias"]))
     red.keep.append((part, dh2))
     return dh2
 
 
-def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chain=False):
-    """dlogit (BTN,HS): gradient of the logits — or dh2 (BTN,C) when kl_head already went through ln3 (chain: dh2 is dPre)."""
+def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chain=False, carried=(None, None)):
+    """dlogit (BTN,HS): gradient of the logits — or dh2 (BTN,C) when kl_head already went through ln3 (chain: dh2 is dPre).
+    carried: outputs of the time-conditioned layer's and of the low-rank input layers' launches already run by earlier launches (KlCarry)."""
     B, T, N, C = dims
     t4m, s1, s2, h2 = saved[:4]
     m = "encoder.MLP_RL."
@@ -799,12 +809,12 @@ def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chai
         ops.rowouter(dlogit, HS, HS, h2, g[m + "ln3.weight"], 1, asum=g[m + "ln3.bias"])
     d_t4m = _zeros(t4m, *t4m.shape)
     dh1 = condlin_bwd(s2, dh2, t4m, p[m + "weights_pool_tem"], p[m + "bias_pool_tem"], g[m + "weights_pool_tem"],
-                      g[m + "bias_pool_tem"], d_t4m, MODE_TIME, dims, red, chain, True)
+                      g[m + "bias_pool_tem"], d_t4m, MODE_TIME, dims, red, chain, True, carried=carried[0])
     if isinstance(s1[0], str):      # ("lowrank", Wspa): node layer + input projection on the low-rank form: p_n, q_n per node instead of dh0 / h0
         assert chain
         neb, wpool, bpool = p["encoder.neb4mask"], p[m + "weights_pool_spa"], p[m + "bias_pool_spa"]
         K = neb.shape[1]
-        dWb, dinp = ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1[1])
+        dWb, dinp = carried[1] if carried[1] is not None else ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1[1])
         dW, db = dWb[:, :C * C], dWb[:, C * C:]
         red.jobs.bwd_pool(neb, dW, g[m + "weights_pool_spa"].view(K, C * C))
         red.jobs.bwd_pool(neb, db, g[m + "bias_pool_spa"])
@@ -826,6 +836,60 @@ def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chai
     red.keep.append((saved, dlogit, dh2, dh1, dh0))
 
 
+def kl_carry_ok(dims, HS, sv_g):
+    """the guest form serves this step's KL path: the two-layer chain forward, the dPre chain, C = 64, T = 12, the low-rank guide input"""
+    B, T, N, C = dims
+    return (CARRY_KL and C == 64 and T == 12 and HS <= ops.TAIL_MAXJ and chain_fwd_ok(dims) and chain_ok(dims)
+            and sv_g is not None and isinstance(sv_g[1][0], str))
+
+
+class KlCarry:
+    """The KL term's backward (kl_head + guide_bwd: 0.1 KL + softmax / ln3 -> the time-conditioned layer -> node layer + ln1) run as GUEST
+    workgroups of the forward's two-layer hyperTem chain launches, one stage per launch in stage order (gptst_hypertem_chain_fwd_kl).  Its inputs —
+    the guide's forward and the encoder's first cap assignment (detached, GPTST.py:141) — exist before the first chain launch, and nothing in the
+    STHCNs reads its results, so it only fills slots the one-round chain grids leave idle.  The reductions are queued where the stand-alone launches
+    queue them (kl_head / guide_bwd carried=): the gradients' summation order does not change."""
+
+    def __init__(self, p, sv_g, prob, source, dims, w, sws):
+        self.p, self.sv_g, self.prob, self.source, self.dims, self.w, self.sws = p, sv_g, prob, source, dims, w, sws
+        self.c1 = None              # set by sthcn_fwd once the encoder's first cap has run
+        self.stage = 0              # stages launched so far
+        self.out = {}
+
+    def guest(self):
+        """-> the next stage as ops.hypertem_chain_fwd(guest=...), its outputs allocated; None when none is due (or every stage is out)"""
+        if self.c1 is None or self.stage == 3:
+            return None
+        B, T, N, C = self.dims
+        m = "encoder.MLP_RL."
+        p, sv_g, dev = self.p, self.sv_g, self.prob.device
+        HS = self.prob.shape[1]
+        st = self.stage + 1
+        f = dict(device=dev, dtype=torch.float32)
+        if st == 1:
+            h2, W3 = sv_g[3], p[m + "ln3.weight"]
+            dh2 = torch.empty_like(h2)
+            part = torch.empty(ops.tail_parts(B * T * N), HS * C + HS, **f)
+            self.out[1] = (dh2, part)
+            ts = [h2, W3, self.prob, self.c1, dh2, part, self.sws]
+        elif st == 2:
+            h1, _, Wtem = sv_g[2]
+            dh2 = self.out[1][0]
+            ns = _C.lib().value("gptst_apply_wgrad_nsplit", MODE_TIME, B * T, N)
+            dh1, dW, db = torch.empty_like(h1), torch.empty(ns * B * T, C * C, **f), torch.empty(ns * B * T, C, **f)
+            self.out[2] = (dh1, dW, db, ns)
+            ts = [dh2, h1, Wtem, dh1, dW, db]
+        else:
+            dWb, dinp = torch.empty(N, C * C + C, **f), torch.empty(N, 2 * C, **f)
+            self.out[3] = (dWb, dinp)
+            ts = [self.out[2][0], self.source, p[m + "ln1.weight"], p[m + "ln1.bias"], sv_g[1][1], dWb, dinp]
+        self.stage = st
+        return (st, ts, 0, ops.kl_guest_blocks(st, B, T, N), HS, self.source.shape[-1], self.w)
+
+    def carried(self, st):
+        return self.out.get(st)
+
+
 def _in_proj_grads(source, base, dY, gW, gb, mask, fill, red):
     """Weight / bias gradient of an input projection Linear(base -> C) on the (masked) raw flow (GPTST.py:22, :416-418): gW (C, base) +=
     dY^T a', gb += colsum(dY).  base = 1: the row-chunk partials [gW | gb] fold as ONE job of the step's reduction launch; else the
@@ -840,12 +904,12 @@ def _in_proj_grads(source, base, dY, gW, gb, mask, fill, red):
         ops.rowouter(source, base + 2, base, dY, gW, 0, csum=gb, mask=mask, fill=fill)
 
 
-def model_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, tidx=None, dec_gen=None, lowrank_in=False):
+def model_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, tidx=None, dec_gen=None, lowrank_in=False, kl=None):
     """Masked-autoencoder body — GPTST.py:415-421 + 453-456.  mask (BTN*base) fp32, 1 = visible; None -> no masking (eval).
     dec_gen: the decoder STHCN's gen dict — its first hyperTem layer then rides on the encoder's last chain launch and the result comes back
     as a fifth value, to be passed to decoder_fwd(dec_head=...) (None when the chain path does not serve the shape).
     lowrank_in: the caller's backward is the dPre chain (model_bwd(chain=True)) — the input projection + encoder hyperTem1 then run as the
-    rank-2 kernel pair of encin.hip where the shape allows."""
+    rank-2 kernel pair of encin.hip where the shape allows.  kl: the step's KlCarry (sthcn_fwd)."""
     B, T, N, C = dims
     if tidx is None:
         tidx = source[:, :, 0, base:base + 2].contiguous()
@@ -861,14 +925,14 @@ def model_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, ti
         x0 = ops.lin_in(source, base + 2, base, p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"], C,
                         mask=mask, fill=scaler_zeros)                                                      # :416-418
     if dec_gen is not None:
-        emb, c1, sv_e, dec_head = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, next_gen=dec_gen, head=head)
+        emb, c1, sv_e, dec_head = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, next_gen=dec_gen, head=head, kl=kl)
         return emb, c1, tidx, sv_e, dec_head
-    emb, c1, sv_e = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, head=head)                       # :421
+    emb, c1, sv_e = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, head=head, kl=kl)                # :421
     return emb, c1, tidx, sv_e
 
 
-def decoder_fwd(p, tidx, emb, dims, num_route, gen=None, head=True, dec_head=None):
-    dec, _, sv_d = sthcn_fwd(p, DEC, tidx, emb, dims, num_route, gen=gen, head=dec_head)                   # :454
+def decoder_fwd(p, tidx, emb, dims, num_route, gen=None, head=True, dec_head=None, kl=None):
+    dec, _, sv_d = sthcn_fwd(p, DEC, tidx, emb, dims, num_route, gen=gen, head=dec_head, kl=kl)            # :454
     if not head:
         return None, dec, sv_d
     out = ops.rowdot(dec, p["decoder.dim_flow_out.weight"], p["decoder.dim_flow_out.bias"])                 # :455

@@ -301,17 +301,31 @@ def hypertem_fwd(X, G, Wbt, bbt, want_R=True):
     return R, out
 
 
-def hypertem_chain_fwd(X, stages, want_R=True):
+def hypertem_chain_fwd(X, stages, want_R=True, guest=None):
     """Consecutive hyperTem layers in ONE launch on the (sample, 16-node) slab (gptst_hypertem_chain_fwd, C = 64).  X (B,T,N,C): input of the
-    first layer;  stages: [(G, Wbt, bbt), ...] (1..3)  ->  [(R or None, out), ...], all (B,T,N,C)."""
+    first layer;  stages: [(G, Wbt, bbt), ...] (1..3)  ->  [(R or None, out), ...], all (B,T,N,C).
+    guest: (stage, operand tensors, v0, v1, HS, lda, w) — virtual blocks [v0, v1) of one KL-path stage ride in the same launch
+    (gptst_hypertem_chain_fwd_kl, two layers only; engine.KlCarry)."""
     B, T, N, C = X.shape
     _chk(X, *[t for st in stages for t in st])
     f = lambda: torch.empty(B, T, N, C, device=X.device, dtype=torch.float32)
     Rs = [f() if want_R else None for _ in stages]
     outs = [f() for _ in stages]
-    _call("gptst_hypertem_chain_fwd", _p(X), len(stages), _ptrs0([st[0] for st in stages]), _ptrs0([st[1] for st in stages]),
-          _ptrs0([st[2] for st in stages]), _ptrs0(Rs), _ptrs0(outs), B, T, N, C, tag="x%d" % len(stages), nbytes=_nb(X, *Rs, *outs))
+    chain = (_p(X), len(stages), _ptrs0([st[0] for st in stages]), _ptrs0([st[1] for st in stages]), _ptrs0([st[2] for st in stages]),
+             _ptrs0(Rs), _ptrs0(outs), B, T, N, C)
+    if guest is None:
+        _call("gptst_hypertem_chain_fwd", *chain, tag="x%d" % len(stages), nbytes=_nb(X, *Rs, *outs))
+    else:
+        stage, ts, v0, v1, HS, lda, w = guest
+        _chk(*ts)
+        _call("gptst_hypertem_chain_fwd_kl", *chain, stage, _ptrs0(ts), v0, v1, HS, lda, float(w), tag="x%d+kl%d" % (len(stages), stage),
+              nbytes=_nb(X, *Rs, *outs))
     return list(zip(Rs, outs))
+
+
+def kl_guest_blocks(stage, B, T, N):
+    """workgroups of KL-path stage 1..3 at this shape (gptst_kl_guest_blocks)"""
+    return _C.lib().value("gptst_kl_guest_blocks", stage, B, T, N)
 
 
 def encin_ht1_fwd(source, base, mask, fill, w, bi, G, Wbt, bbt):

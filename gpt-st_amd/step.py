@@ -203,21 +203,27 @@ class PretrainStep:
         self.last_mask = mask
         dec_head = None
         lowrank = self.fused_tails and engine.chain_ok(dims)      # the backward below is the dPre chain: the low-rank first layer may run
+        kl, sws = None, None
+        if phase == 1 and self._carry_kl(sv_g):   # the KL path's backward rides on the forward's chain launches (engine.KlCarry)
+            sws = self.arena.zeros(ops.tail_parts(M), 4)
+            kl = engine.KlCarry(p, sv_g, prob, src, dims, 0.1, sws)
         if engine.chain_fwd_ok(dims):          # the decoder's first hyperTem layer rides on the encoder's last chain launch
             emb, c1, tidx, sv_e, dec_head = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                             dec_gen=gen[engine.DEC], lowrank_in=lowrank)
+                                                             dec_gen=gen[engine.DEC], lowrank_in=lowrank, kl=kl)
         else:
             emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
                                                    lowrank_in=lowrank)
         if self.fused_tails:
             # output head + masked MAE + their backward: one pass over dec (the mean's 1/#kept is applied by the optimiser)
-            _, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC], head=False, dec_head=dec_head)
-            sws = self.arena.zeros(ops.tail_parts(M), 4)                       # per-workgroup loss statistics of the two heads
+            _, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC], head=False, dec_head=dec_head, kl=kl)
+            if sws is None:
+                sws = self.arena.zeros(ops.tail_parts(M), 4)                   # per-workgroup loss statistics of the two heads
             chain = engine.chain_ok(dims)                                      # dPre chain: no backward kernel re-reads its layer's output
+            done = kl.carried if kl is not None else (lambda st: None)         # outputs of the stages the chain launches carried
 
             def kl_path():
-                dh2 = engine.kl_head(p, g, sv_g, prob, c1, self.N, 0.1, sws, red, chain=chain)
-                engine.guide_bwd(p, g, src, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain)
+                dh2 = engine.kl_head(p, g, sv_g, prob, c1, self.N, 0.1, sws, red, chain=chain, carried=done(1))
+                engine.guide_bwd(p, g, src, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=(done(2), done(3)))
             out, dd = engine.loss_tail(p, g, dec, src, mask, base, self.std, self.mean, a.mape_thresh, sws, red, chain=chain)
             engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, None, None, dims, base, mdl.scaler_zeros, red, dd=dd, chain=chain)
             if phase == 1:
@@ -245,6 +251,12 @@ class PretrainStep:
             else:
                 self._allreduce(self.gbuf)
             self._optim()
+
+    def _carry_kl(self, sv_g):
+        """the KL path as guests of the forward's chain launches (engine.KlCarry): the plain fused stepper only — not under data parallelism, node
+        shards, GPTST_ALWAYS_GUIDE, deterministic or safe mode (GPTST_CARRY_KL=0: never)"""
+        return (self.fused_tails and self.dp is None and not self.global_count_scale and not self.deterministic and not self.safe_mode
+                and not self.always_guide and engine.CTX.NODE_REDUCE is None and engine.kl_carry_ok(self.dims, self.HS, sv_g))
 
     def _mask_ws(self):
         """The selections' histogram scratch comes zeroed out of the step's arena (cleared by the step's first launch): no zeroing launch."""

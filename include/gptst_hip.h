@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 15  /* 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 16  /* 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -163,6 +163,18 @@ int gptst_hypertem_fwd(const float* X, const float* G, const float* Wbt, const f
  * measured slower than gptst_apply — left the signature.) */
 int gptst_hypertem_chain_fwd(const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs, const void* outs,
                              int B, int T, int N, int C, void* stream);
+/* The same two-layer chain (nstage = 2) carrying virtual blocks [v0, v1) of one stage of the KL term's backward (BasicTrainer.py:85 through
+ * MLP_RL, GPTST.py:21-33) as guest workgroups behind its own grid: the chain is one round of workgroups that leaves slots idle, and the KL path's
+ * inputs exist once the encoder's first cap has routed.  Each guest block runs the body of the stand-alone kernel (bit-identical results):
+ *   stage 1  gptst_tail_kl (premul = 1)                        ops = [h2, W3, prob, c, d_h2, part, sws], HS classes, weight w
+ *   stage 2  gptst_apply_wgrad (MODE_TIME, Y = NULL, premul)   ops = [d_h2, h1, W_bt, d_h1, dW, db]
+ *   stage 3  gptst_guide_in_bwd                                ops = [dPre, src, w1, b1, Wn, dWb, dinp], src rows of lda floats
+ * ops: HOST array of device pointers, read at call time.  v1 <= gptst_kl_guest_blocks(stage, B, T, N); a stage may be split over several
+ * launches.  C = 64, HS <= 16 (GPTST_ESHAPE otherwise). */
+int gptst_hypertem_chain_fwd_kl(const float* X, int nstage, const void* Gs, const void* Wbts, const void* bbts, const void* Rs, const void* outs,
+                                int B, int T, int N, int C, int stage, const void* ops, int v0, int v1, int HS, int lda, float w, void* stream);
+/* number of virtual blocks of stage 1..3 of the KL path at this shape (the workgroups of its stand-alone launch) */
+int gptst_kl_guest_blocks(int stage, int B, int T, int N);
 
 /* Encoder input projection + the encoder's first hyperTem layer on the low-rank structure of the input (encin.hip, r04).  For base = 1 the
  * first activation is x0 = m w + bi (m = mask ? flow : fill, a scalar per row), so hyperTem1 needs neither x0 nor a GEMM:
