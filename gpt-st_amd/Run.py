@@ -41,10 +41,14 @@ def main():
     dev = torch.device("cuda", int(os.environ.get("LOCAL_RANK", "0")) % max(torch.cuda.device_count(), 1))
     torch.cuda.set_device(dev)
     args = parse_args(str(dev))
+    if args.mode == "eval" and args.shard == "nodes":
+        raise SystemExit("-shard nodes applies to -mode pretrain only (-mode eval trains the predictor on one GPU)")
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
         raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN")
+    if args.shard == "nodes":
+        return main_shard(args, dev)
     dp = None
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         from gptst_amd.dist import DataParallel
@@ -64,6 +68,45 @@ def main():
 
     batches, nb = gdata.epoch_batches(train, args.batch_size, dp)      # under data parallelism the epoch's tail is kept as padded rounds
     Trainer(model, args, batches, mean, std, args.batch_size, dp=dp, batches_per_epoch=nb).train()
+    if dp is not None:
+        import torch.distributed as dist
+        dp.barrier()
+        dist.destroy_process_group()
+
+
+def main_shard(args, dev):
+    """``-mode pretrain -shard nodes``: every rank of the job owns a contiguous node range (shard.node_ranges) of every batch and of the
+    node-indexed parameters; all ranks step on the same global batches.  The checkpoint is the global, reference-format state dict."""
+    import copy
+    from gptst_amd.shard import DistNodeGroup, NativeNodeGroup, node_ranges, shard_state_dict
+    rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
+    ranges = node_ranges(args.num_nodes, world)          # (raises before any rendezvous when world > N)
+    dp, group = None, DistNodeGroup(0, 1)
+    if world > 1:
+        from gptst_amd.dist import DataParallel
+        # rendezvous as in the data-parallel branch; the collectives on the C-ABI communicator unless GPTST_NATIVE_COMM=0 / a gloo backend
+        dp = DataParallel("nccl", native=os.environ.get("GPTST_NATIVE_COMM", "1") != "0" and os.environ.get("GPTST_DIST_BACKEND", "nccl") == "nccl")
+        group = NativeNodeGroup(dp.native) if dp.native is not None else DistNodeGroup(rank, world)
+    init_seed(args.seed)
+    args.log_dir = os.path.join(os.path.dirname(os.path.realpath(__file__)), "SAVE", args.dataset)
+    _, (train, val, test, scaler, _, _) = load_series(args, dev)       # GLOBAL N: the scaler is the global train split's
+    mean, std = float(scaler.mean), float(scaler.std)
+    args.scaler_zeros = float(scaler.transform(0))
+    gmodel = GPTST_Model(args)                                          # the global initialisation, identical on every rank
+    if args.xavier:
+        xavier_init_(gmodel)
+    n0, n1 = ranges[rank]
+    largs = copy.copy(args)
+    largs.num_nodes, largs.node_capacity = n1 - n0, max(b - a for a, b in ranges)
+    model = GPTST_Model(largs)
+    model.load_state_dict(shard_state_dict(gmodel.state_dict(), n0, n1))
+    del gmodel
+    model = model.to(dev)
+    for ld in (train, val, test):                                       # the windows index time only: keep this rank's node columns
+        if ld is not None:
+            ld.series = ld.series[:, n0:n1].contiguous()
+    batches, nb = gdata.epoch_batches(train, args.batch_size)          # same permutation on every rank: the same global batches
+    Trainer(model, largs, batches, mean, std, args.batch_size, batches_per_epoch=nb, shard=(group, ranges)).train()
     if dp is not None:
         import torch.distributed as dist
         dp.barrier()

@@ -63,6 +63,8 @@ def parse_args(device, argv=None):
         ap.add_argument("-" + key, default=typ(cp[sec][key]), type=typ)
     ap.add_argument("-log_dir", default="./", type=str)
     ap.add_argument("-steps_per_replay", default=STEPS_PER_REPLAY, type=int)      # not a reference option: see STEPS_PER_REPLAY
+    # not a reference option: what the ranks of a torch.distributed.run job split — the batch (data parallel) or the nodes (shard.py)
+    ap.add_argument("-shard", default="batch", choices=["batch", "nodes"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args

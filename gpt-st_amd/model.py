@@ -154,6 +154,11 @@ class GPTST_Model(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.num_node = args.num_nodes
+        # node-sharded runs (shard.py): every node-local tensor's slot in the flat buffer is reserved for this many nodes, so that ranks whose
+        # shards differ in width lay out [flat gradient | statistics] alike; the tail of such a slot is zero in weights, gradients and moments
+        self.node_capacity = int(getattr(args, "node_capacity", args.num_nodes))
+        if self.node_capacity < self.num_node:
+            raise ValueError("node_capacity %d < num_nodes %d" % (self.node_capacity, self.num_node))
         self.input_base_dim = args.input_base_dim
         self.input_extra_dim = args.input_extra_dim
         self.hidden_dim = args.hidden_dim
@@ -179,21 +184,26 @@ class GPTST_Model(nn.Module):
     # ---- flat parameter storage ------------------------------------------------------------------------------------
     def _flatten(self):
         """(Re)build the flat buffer on the parameters' current device; segment order [path A | KL path | never]."""
+        from .shard import is_node_local
         self._named = None                       # (walk the module tree afresh)
         named = OrderedDict(self.named_parameters())
         dev = next(iter(named.values())).device
         order = sorted(named.keys(), key=lambda k: (_segment(k), self.param_keys.index(k)))
-        offs, n, seg_end = {}, 0, [0, 0, 0]
+        offs, n, seg_end, slots = {}, 0, [0, 0, 0], {}
         for k in order:
             offs[k] = n
-            n += (named[k].numel() + 3) // 4 * 4          # 16-byte aligned tensors
+            slot = named[k].numel()
+            if self.node_capacity != self.num_node and is_node_local(k):
+                slot = slot // self.num_node * self.node_capacity
+            slots[k] = slot                               # the tensor's reserved elements (its numel unless it is node-local padded)
+            n += (slot + 3) // 4 * 4                      # 16-byte aligned tensors
             seg_end[_segment(k)] = n
         flat = torch.zeros(n, device=dev, dtype=torch.float32)
         for k in order:
             t = named[k]
             flat[offs[k]:offs[k] + t.numel()].copy_(t.detach().reshape(-1))
             t.data = flat[offs[k]:offs[k] + t.numel()].view(t.shape)
-        self.flat, self._offs = flat, offs
+        self.flat, self._offs, self._slot_numel = flat, offs, slots
         import weakref
         GPTST_Model._OWNERS[flat.untyped_storage().data_ptr()] = weakref.ref(self)
         self.nA, self.nB = seg_end[0], seg_end[1] - seg_end[0]

@@ -10,6 +10,8 @@ by 1/world before the gradient all-reduce.  Gradients of shared parameters: one 
 are put back afterwards — they belong to this rank alone); the global gradient norm adds the other ranks' node-local squared
 norms (one scalar all-reduce).  Masks: the selection runs replicated over the GLOBAL (B,T,N) cells from identical noise and each
 rank keeps its node columns; the adaptive phase all-gathers the per-cell cluster labels and sums the class counts.
+Shards come from node_ranges() and may differ in width by one node: the label gather pads to the widest shard, and the models are built
+with node_capacity = that width (model.py), so that the flat gradient buffer has the same layout on every rank.
 Loss statistics (sum |e|, kept count, KL sum) travel in the tail of the gradient buffer, as in dist.py.
 
 The collectives go through a small group object: ``DistNodeGroup`` (torch.distributed, RCCL on GPUs), ``NativeNodeGroup`` (the C-ABI
@@ -35,6 +37,64 @@ def is_node_local(key):
 def is_replicated_compute(key):
     """Parameters whose gradient is computed identically on every rank (cross-time block on the all-reduced cluster capsules)."""
     return key.endswith(".t_adj") or ".time_feature2." in key
+
+
+def node_ranges(N, world):
+    """The node split of a sharded run: [(n0, n1)] per rank, contiguous and in rank order; the first N % world ranks own one node more
+    (170 over 8: 22, 22, 21, 21, 21, 21, 21, 21).  Every bound of a node shard comes from here."""
+    N, world = int(N), int(world)
+    if world < 1:
+        raise ValueError("node sharding needs at least one rank, got world = %d" % world)
+    if world > N:
+        raise ValueError("cannot split %d nodes over %d ranks: every rank needs at least one node" % (N, world))
+    q, r = divmod(N, world)
+    out, n0 = [], 0
+    for k in range(world):
+        n1 = n0 + q + (1 if k < r else 0)
+        out.append((n0, n1))
+        n0 = n1
+    return out
+
+
+def gather_node_columns(group, local, widths, pad=None):
+    """(..., n_rank) of every rank -> (..., N): the last axis zero-padded to the widest shard for the group's all-gather, then trimmed and
+    concatenated in rank (= node) order.  pad: a (..., max(widths)) buffer to reuse (its padding columns must be zero)."""
+    n = local.shape[-1]
+    if pad is None:
+        pad = local.new_zeros(tuple(local.shape[:-1]) + (max(widths),))
+    pad[..., :n].copy_(local)
+    g = group.all_gather(pad)                                             # (W, ..., wmax)
+    return torch.cat([g[r, ..., :w] for r, w in enumerate(widths)], dim=-1)
+
+
+def _pad_nodes(key, t, width):
+    """a node-local tensor zero-padded to `width` nodes along its node axis (the last one for cap*.adj, the first otherwise)"""
+    adj = key.endswith(".adj")
+    n = t.shape[-1] if adj else t.shape[0]
+    if n == width:
+        return t.contiguous()
+    shape = list(t.shape)
+    shape[-1 if adj else 0] = width
+    out = t.new_zeros(shape)
+    (out[..., :n] if adj else out[:n]).copy_(t)
+    return out
+
+
+def gather_state_dict(group, local_sd, ranges):
+    """Collective: every rank's node-local tensors (padded to the widest shard, all-gathered, trimmed) assembled with the shared ones into the
+    GLOBAL state dict — the keys, shapes and order of an unsharded model (the reference's checkpoint format).  Returned on every rank."""
+    widths = [n1 - n0 for n0, n1 in ranges]
+    wmax = max(widths)
+    parts = [dict() for _ in ranges]
+    for k, v in local_sd.items():
+        if is_node_local(k):
+            g = group.all_gather(_pad_nodes(k, v, wmax))                  # (W, ...)
+            for r, w in enumerate(widths):
+                parts[r][k] = g[r][..., :w] if k.endswith(".adj") else g[r][:w]
+        else:
+            for p_ in parts:
+                p_[k] = v
+    return unshard_state_dicts(parts)
 
 
 def shard_state_dict(sd, n0, n1):
@@ -103,6 +163,17 @@ class NativeNodeGroup:
                 self.comm.allreduce_(f)
                 t.copy_(f)
             return t
+        if t.dtype == torch.float64:
+            # (metric sums, once per run) each rank's values as hi + lo fp32 words in its own slot: every element of the reduced buffer has ONE
+            # nonzero contributor, so the fp32 all-reduce is exact, and the sum over the ranks is taken in float64 afterwards (~48-bit values)
+            flat = t.contiguous().view(-1)
+            buf = torch.zeros(self.world, 2, flat.numel(), dtype=torch.float32, device=t.device)
+            hi = flat.to(torch.float32)
+            buf[self.rank, 0].copy_(hi)
+            buf[self.rank, 1].copy_((flat - hi.to(torch.float64)).to(torch.float32))
+            self.comm.allreduce_(buf)
+            t.copy_(buf.to(torch.float64).sum(dim=(0, 1)).view(t.shape))
+            return t
         f = t.to(torch.float32)
         self.comm.allreduce_(f)
         t.copy_(f.to(t.dtype))
@@ -153,7 +224,8 @@ class ThreadNodeGroup:
 
 
 class ShardedPretrainStep(PretrainStep):
-    """One optimisation step of a rank that owns nodes [n0, n1) of N (all ranks: equal shard sizes)."""
+    """One optimisation step of a rank that owns nodes [n0, n1) of N (node_ranges: shard widths may differ by one).  Unequal shards
+    need models built with node_capacity = the widest shard, so that [flat gradient | statistics] has the same layout on every rank."""
 
     def __init__(self, model_local, args_local, n_global, group, scaler_mean, scaler_std, batch_size, seed=0, use_graph=None):
         """use_graph: None = capture the step in a hipGraph when the group's collectives are capturable (see the module docstring)."""
@@ -167,8 +239,19 @@ class ShardedPretrainStep(PretrainStep):
                             and engine.fused_tails_ok(model_local.param_views(), self.C, self.base, self.HS))
         self.group, self.Ng = group, n_global
         self.Nl = args_local.num_nodes
-        assert self.Nl * group.world == n_global, "equal node shards"
-        self.n0 = group.rank * self.Nl
+        self.ranges = node_ranges(n_global, group.world)
+        self.widths = [n1 - n0 for n0, n1 in self.ranges]
+        if self.ranges[0][0] != 0 or self.ranges[-1][1] != n_global or any(a[1] != b[0] for a, b in zip(self.ranges, self.ranges[1:])):
+            raise ValueError("node ranges %s do not cover the %d nodes" % (self.ranges, n_global))
+        self.n0, self.n1 = self.ranges[group.rank]
+        if self.n1 - self.n0 != self.Nl:
+            raise ValueError("rank %d owns nodes [%d, %d) of %d over %d ranks, but its model was built with num_nodes = %d"
+                             % (group.rank, self.n0, self.n1, n_global, group.world, self.Nl))
+        # adaptive phase, unequal shards: this rank's labels travel padded to the widest shard (gather_node_columns)
+        self.label_pad = (torch.zeros(self.B, self.T, max(self.widths), dtype=torch.int32, device=self.dev)
+                          if group.world > 1 and min(self.widths) != max(self.widths) else None)
+        self._eval_gen = None
+        self._check_agreement()
         Mg = self.B * self.T * self.Ng
         torch.cuda.manual_seed(7654321 + seed)              # identical global mask noise on every rank
         self.noise_g = torch.zeros(Mg * self.base, device=self.dev)
@@ -181,19 +264,64 @@ class ShardedPretrainStep(PretrainStep):
         self.repl_keys = [k for k in named if is_replicated_compute(k)]
         self.segA = {k: model_local._offs[k] < model_local.nA for k in self.local_keys}
         # node-local gradients are kept out of the gradient all-reduce by a save / restore around it: ONE flat buffer, [reconstruction-path keys |
-        # KL-path keys], moved by multi-tensor copies (r05: a clone, a copy and three norm launches PER KEY before — ~95 tiny launches per step)
+        # KL-path keys], moved by multi-tensor copies (r05: a clone, a copy and three norm launches PER KEY before — ~95 tiny launches per step).
+        # Each key's WHOLE slot travels (node_capacity, model.py): the all-reduce adds the wider ranks' node-local gradients into a narrower
+        # rank's padding, and the restore writes the padding's zeros back over them — the padding stays zero in gradients, moments and weights
+        # and every rank's clip norm sees the same set of values.
         ordered = [k for k in self.local_keys if self.segA[k]] + [k for k in self.local_keys if not self.segA[k]]
-        sizes = [named[k].numel() for k in ordered]
+        sizes = [model_local._slot_numel[k] for k in ordered]
         self.keep_flat = torch.zeros(sum(sizes), device=self.dev)
         self.keep_nA = sum(n for k, n in zip(ordered, sizes) if self.segA[k])
         offs = [sum(sizes[:i]) for i in range(len(sizes))]
-        self.keep_views = [self.keep_flat[o:o + n].view(named[k].shape) for k, o, n in zip(ordered, offs, sizes)]
-        self.keep_grads = [self.g[k] for k in ordered]
+        self.keep_views = [self.keep_flat[o:o + n] for o, n in zip(offs, sizes)]
+        self.keep_grads = [self.gflat[model_local._offs[k]:model_local._offs[k] + n] for k, n in zip(ordered, sizes)]
         self.repl_grads = [self.g[k] for k in self.repl_keys]
 
+    def _check_agreement(self):
+        """The collectives of a step assume the same flat layout, the same loss-head form and the same launch form on every rank; a rank that
+        disagrees would sum unrelated parameters or wait in a collective nobody else enters.  Checked once, collectively: every rank fills its
+        row of a small table (the fingerprint in 12-bit digits, exact in fp32 on every group) and ONE all-reduce gives every rank all rows; the
+        column-wise min and max then differ on every rank or on none."""
+        W = self.group.world
+        if W == 1:
+            return
+        mdl = self.model
+        order = sorted(mdl._offs, key=mdl._offs.get)
+        names = ["flat.numel()", "fused_tails", "shard_graph"]
+        fp = [mdl.flat.numel(), int(self.fused_tails), int(self.shard_graph)]
+        for i, k in enumerate(order):          # where the shared parameters resume after each node-local one (node_capacity)
+            if is_node_local(k):
+                nxt = next((q for q in order[i + 1:] if not is_node_local(q)), None)
+                names.append("offset of %s (after %s)" % (nxt, k))
+                fp.append(mdl._offs[nxt] if nxt is not None else -1)
+        L = 32
+        vals = ([v + 1 for v in fp] + [0] * L)[:L]
+        digits = [(v >> s) & 4095 for v in vals for s in (0, 12, 24)]
+        table = torch.zeros(W, 3 * L, device=self.dev)
+        table[self.group.rank] = torch.tensor(digits, dtype=torch.float32, device=self.dev)
+        self.group.all_reduce_(table)
+        bad = (table.amax(0) != table.amin(0)).view(L, 3).any(1).cpu()
+        if bool(bad.any()):
+            t = table.view(W, L, 3).cpu().to(torch.int64)
+            rows = t[..., 0] + (t[..., 1] << 12) + (t[..., 2] << 24) - 1
+            what = ["%s: %s" % (names[i] if i < len(names) else "entry %d" % i, rows[:, i].tolist()) for i in range(L) if bad[i]]
+            raise RuntimeError("node shards disagree on what their collectives depend on (values per rank) — %s.  Shards of unequal width "
+                               "need models built with node_capacity = the widest shard." % "; ".join(what))
+
+    def _gather_labels(self, label, B):
+        """this rank's cluster labels of (B,T,Nl) cells -> the (B,T,N) labels of the global cells, flat, node order"""
+        if self.group.world == 1:
+            return label.reshape(-1)
+        lab = label.view(B, self.T, self.Nl)
+        if self.label_pad is None:                                                     # equal shards
+            return self.group.all_gather(lab).permute(1, 2, 0, 3).contiguous().view(-1)   # (W,B,T,Nl) -> (B,T,N)
+        pad = self.label_pad if B == self.B else None
+        return gather_node_columns(self.group, lab, self.widths, pad=pad).reshape(-1)
+
     # global mask -> this rank's node columns
-    def _cols(self, flat_global, per_cell):
-        return flat_global.view(self.B, self.T, self.Ng, per_cell)[:, :, self.n0:self.n0 + self.Nl].contiguous().view(-1)
+    def _cols(self, flat_global, per_cell, B=None):
+        B = self.B if B is None else B
+        return flat_global.view(B, self.T, self.Ng, per_cell)[:, :, self.n0:self.n1].contiguous().view(-1)
 
     def _mask(self, phase, prob, label=None, jobs=None):
         """label: the guide's argmax labels of the local cells (rowdot's by-product) — else taken from prob;  jobs: the STHCNs' generation table
@@ -206,11 +334,7 @@ class ShardedPretrainStep(PretrainStep):
         else:
             if label is None:
                 label = ops.mask_labels(prob)[0]                                               # local cells (B,T,Nl)
-            if self.group.world == 1:
-                label_g = label.view(-1)
-            else:
-                lab = self.group.all_gather(label.view(self.B, self.T, self.Nl))               # (W,B,T,Nl)
-                label_g = lab.permute(1, 2, 0, 3).contiguous().view(-1)                        # (B,T,N) node-major within a cell row
+            label_g = self._gather_labels(label, self.B)
             mask_g = ops.mask_adaptive(label_g, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a_g, self.noise_r_g,
                                        a.ada_type == "all", base, ws=ws, u24=U24, jobs=jobs)[2]  # (class histogram of the gathered labels: taken inside)
         self.last_mask_global = mask_g
@@ -314,6 +438,9 @@ class ShardedPretrainStep(PretrainStep):
                 if phase == 1:
                     dlogit = ops.kl(prob, c1, self.Nl, 0.1, self.stats)
                     engine.guide_bwd(p, g, src, tidx, sv_g, dlogit, dims, base, red)
+                # (a zero row: only the fold's other job) stats[5] <- this rank's hand-off expiries, so that the all-reduce below carries them
+                # and every rank skips the update and re-runs the step together, as on the fused path
+                ops.stats_fold(self.arena.zeros(1, 4), self.stats)
             red.flush(tidx)
         finally:
             ctx.ARENA = ctx.NODE_REDUCE = None
@@ -339,3 +466,49 @@ class ShardedPretrainStep(PretrainStep):
 
     def _budgets(self, ada, rnd, epoch):
         return self.model.adaptive_counts(self.B * self.T * self.Ng, epoch)      # mask budgets over the GLOBAL cell count
+
+    def evaluate(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None):
+        """Forward only (the end-of-training report of a node-sharded run): guide, global mask, encoder, decoder with its head — the first half of
+        _sbody_impl in the form GPTST_Model.forward takes.  No backward, no optimiser step, no counter moves.  source: this rank's (B',T,Nl,base+2)
+        slice, any batch size.  Injected noise covers the GLOBAL cells; what is not injected is drawn from generators this evaluator owns, seeded
+        from the run's seed and identical on every rank (not the process-wide ones: ranks emulated by threads share those).
+        -> (out (B',T,Nl,base), visibility mask (B',T,Nl,base) fp32, 1 = visible) of this rank's cells."""
+        import random
+        mdl, a, base = self.model, self.args, self.base
+        src = source.to(self.dev).contiguous().float()
+        B, T = src.shape[0], src.shape[1]
+        dims = (B, T, self.Nl, self.C)
+        Mg = B * T * self.Ng
+        if self._eval_gen is None:
+            seed = int(getattr(a, "seed", 0))
+            self._eval_gen = torch.Generator(device=self.dev)
+            self._eval_gen.manual_seed(9876543 + seed)
+            self._eval_rng = random.Random(seed)
+        rand = lambda n: torch.rand(n, device=self.dev, generator=self._eval_gen)      # noqa: E731
+        p = mdl.param_views()
+        ctx = engine.CTX
+        ctx.NODE_REDUCE = self.group.all_reduce_
+        try:
+            with torch.no_grad():
+                tidx = mdl._tidx(src)
+                gen = engine.gen_all(p, tidx, dims)
+                prob, _ = engine.guide_fwd(p, src, tidx, dims, base, gen=gen["guide"])
+                if epoch <= a.change_epoch:
+                    noise = rand(Mg * base) if noise is None else noise.to(self.dev).reshape(-1).contiguous()
+                    mask_g = ops.mask_random(noise, int(Mg * base * a.mask_ratio))
+                else:
+                    label_g = self._gather_labels(ops.mask_labels(prob.reshape(B * T * self.Nl, -1))[0], B)
+                    if list_c is None:
+                        list_c = list(range(self.HS))
+                        self._eval_rng.shuffle(list_c)
+                    na = rand(Mg) if noise_a is None else noise_a.to(self.dev).reshape(-1).contiguous()
+                    nr = rand(Mg) if noise_r is None else noise_r.to(self.dev).reshape(-1).contiguous()
+                    lc = torch.tensor([int(v) for v in list_c], dtype=torch.int32, device=self.dev)
+                    nums = torch.tensor(mdl.adaptive_counts(Mg, epoch), dtype=torch.int32, device=self.dev)
+                    mask_g = ops.mask_adaptive(label_g, None, lc, nums, na, nr, a.ada_type == "all", base)[2]
+                mask = self._cols(mask_g, base, B)
+                emb, _, tidx, _ = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx)
+                out, _, _ = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC])
+        finally:
+            ctx.NODE_REDUCE = None
+        return out.view(B, T, self.Nl, base), mask.view(B, T, self.Nl, base)

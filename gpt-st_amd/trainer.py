@@ -29,22 +29,35 @@ def get_logger(log_dir, name="GPTST", debug=True):
 
 
 class Trainer:
-    def __init__(self, model, args, batches, scaler_mean, scaler_std, batch_size, dp=None, use_graph=True, batches_per_epoch=None):
+    def __init__(self, model, args, batches, scaler_mean, scaler_std, batch_size, dp=None, use_graph=True, batches_per_epoch=None, shard=None):
         """batches: a callable epoch -> iterable of (B,T,N,base+2) device tensors (ragged last batch allowed), consumed lazily — the
-        windowed dataset is 12x the series and is never materialised; batches_per_epoch: the 'i/n' of the log line when known."""
+        windowed dataset is 12x the series and is never materialised; batches_per_epoch: the 'i/n' of the log line when known.
+        shard: (group, ranges) — node-sharded run (shard.py): `model` / `args` are this rank's shard (num_nodes = its width), `batches` yields
+        its node columns [n0, n1) of the same global batches on every rank; the checkpoint and the closing report are global."""
         self.model, self.args, self.batches = model, args, batches
-        self.dp, self.nb_epoch = dp, batches_per_epoch
-        self.step = PretrainStep(model, args, scaler_mean, scaler_std, batch_size, use_graph=use_graph, dp=dp, seed=args.seed)
+        self.dp, self.nb_epoch, self.shard = dp, batches_per_epoch, shard
+        if shard is not None:
+            from .shard import ShardedPretrainStep
+            assert dp is None, "node sharding and batch data parallelism are separate run modes"
+            self.step = ShardedPretrainStep(model, args, shard[1][-1][1], shard[0], scaler_mean, scaler_std, batch_size, seed=args.seed,
+                                            use_graph=None if use_graph else False)
+        else:
+            self.step = PretrainStep(model, args, scaler_mean, scaler_std, batch_size, use_graph=use_graph, dp=dp, seed=args.seed)
         self.ragged = {}
         self.scaler = (scaler_mean, scaler_std)
         self.use_graph = use_graph
         os.makedirs(args.log_dir, exist_ok=True)
         self.logger = get_logger(args.log_dir, name=str(args.model), debug=args.debug)
-        if dp is not None and dp.rank != 0:              # one log stream per job (losses are global: every rank would print the same lines)
+        if self._rank() != 0:                            # one log stream per job (losses are global: every rank would print the same lines)
             self.logger.setLevel(logging.WARNING)
         self.best_path = os.path.join(args.log_dir, args.save_pretrain_path)
         self.lr_steps = [int(i) for i in str(args.lr_decay_step).split(",")] if args.lr_decay else []
         self.up_epoch = [int(i) for i in str(args.up_epoch).split(",")]
+
+    def _rank(self):
+        if self.shard is not None:
+            return self.shard[0].rank
+        return self.dp.rank if self.dp is not None else 0
 
     def _stepper_for(self, B, tail=False):
         """tail: an eager stepper even for the full batch size — the rounds of a data-parallel epoch in which some ranks step on padding
@@ -52,7 +65,12 @@ class Trainer:
         if B == self.step.B and not tail:
             return self.step
         if B not in self.ragged:                         # drop_last=False in the reference: the last batch is smaller
-            s = PretrainStep(self.model, self.args, self.scaler[0], self.scaler[1], B, use_graph=False, dp=self.dp, seed=self.args.seed)
+            if self.shard is not None:                   # (every rank reaches the ragged batch together: the constructor's check is collective)
+                from .shard import ShardedPretrainStep
+                s = ShardedPretrainStep(self.model, self.args, self.step.Ng, self.shard[0], self.scaler[0], self.scaler[1], B,
+                                        seed=self.args.seed, use_graph=False)
+            else:
+                s = PretrainStep(self.model, self.args, self.scaler[0], self.scaler[1], B, use_graph=False, dp=self.dp, seed=self.args.seed)
             s.m, s.v = self.step.m, self.step.v          # one optimiser state
             self.ragged[B] = s
         s = self.ragged[B]
@@ -143,7 +161,13 @@ class Trainer:
                 self.logger.info("Validation performance didn't improve for {} epochs. Training stops.".format(a.early_stop_patience))
                 break
         self.logger.info("Total training time: {:.4f}min, best loss: {:.6f}".format((time.time() - t0) / 60, best_loss))
-        if a.debug and best_state is not None and (self.dp is None or self.dp.rank == 0):   # :187-189 (flag is inverted in the reference too)
+        if a.debug and best_state is not None and self.shard is not None:
+            from .shard import gather_state_dict
+            full = gather_state_dict(self.shard[0], best_state, self.shard[1])     # collective; the global, reference-format dict
+            if self._rank() == 0:
+                torch.save(full, self.best_path)
+                self.logger.info("Saving current best model to " + self.best_path)
+        elif a.debug and best_state is not None and (self.dp is None or self.dp.rank == 0):   # :187-189 (flag is inverted in the reference too)
             torch.save(best_state, self.best_path)
             self.logger.info("Saving current best model to " + self.best_path)
         if best_state is not None:                       # :193-195: pretrain mode evaluates on the TRAIN loader
@@ -171,12 +195,29 @@ class Trainer:
                         continue
                 src = src.contiguous()
                 B, T, N, _ = src.shape
-                out, _, masked, _, _ = model(src, None, None, a.epochs)
+                if self.shard is not None:               # this rank's node columns; the mask is selected over the global cells
+                    out, vis = self.step.evaluate(src, a.epochs)
+                    vis = vis.reshape(-1)
+                else:
+                    out, _, masked, _, _ = model(src, None, None, a.epochs)
+                    vis = (1 - masked).to(torch.float32).reshape(-1).contiguous()
                 if sums is None:
                     sums = ops.metrics_new(T, N, src.device)
-                vis = (1 - masked).to(torch.float32).reshape(-1).contiguous()
                 ops.metrics_accum(out.reshape(-1, base).contiguous(), src, base + 2, vis, self.scaler[1], self.scaler[0],
                                   getattr(a, "mae_thresh", None), a.mape_thresh, B, T, N, base, *sums)
+        if self.shard is not None:
+            # per-(horizon, node) sums into this rank's rows of the global (T, N, 6) table, per-horizon sums added: ONE group all-reduce
+            group, ranges = self.shard
+            n0, n1 = ranges[group.rank]
+            T = self.step.T
+            if sums is None:
+                sums = ops.metrics_new(T, n1 - n0, self.step.dev)
+            nt = sums[0].numel()
+            buf = torch.zeros(nt + T * ranges[-1][1] * 6, dtype=torch.float64, device=sums[0].device)
+            buf[:nt].copy_(sums[0].reshape(-1))
+            buf[nt:].view(T, ranges[-1][1], 6)[:, n0:n1].copy_(sums[1])
+            group.all_reduce_(buf)
+            sums = (buf[:nt].view(sums[0].shape), buf[nt:].view(T, ranges[-1][1], 6))
         if self.dp is not None and self.dp.world > 1:
             import torch.distributed as dist
             if sums is None:                             # a rank whose whole share was padding still joins the reduction
