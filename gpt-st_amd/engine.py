@@ -7,6 +7,7 @@ state_dict keys to tensors.  Citations: reference model/Pretra
 import contextlib
 import os
 import threading
+from typing import Any, NamedTuple
 
 import torch
 
@@ -85,6 +86,10 @@ class Reductions:
         self.keep = []
         self.on_bucket = None    # callable(k): gradient bucket k is complete (k = 0: the decoder's) — called on the forked stream, right behind
         self.nbucket = 0         # the reductions that finish it, so a data-parallel step can enqueue that bucket's all-reduce under the rest of the backward
+        self.bucket_inline = False   # flush_async() runs the bucket's reductions on the calling stream and forks only on_bucket, onto fork_side
+        self.fork_side = None
+        self.forked = False          # a fork is open: flush() joins it
+        self._dG = self._dA = None   # graph / factor gradient buffers shared by the step's STHCNs (_grad_buffers)
 
     def take_carry(self, mb):
         """Up to `mb` MB of the queued reductions for a backward launch that carries them as role workgroups (ops.cap_cross_route_lin_bwd jobs=): the
@@ -124,7 +129,7 @@ class Reductions:
         """A gradient bucket is complete (a data-parallel step, GPTST_DP_OVERLAP=1; no-op otherwise): its reductions run HERE, on the calling
         stream (as a side branch their ~1300 bandwidth-bound workgroups slowed the chain they ran under by more than they hid: 717 vs 752
         steps/s at one rank), and only the bucket's all-reduce — a few RCCL workgroups — is forked under the rest of the backward."""
-        if getattr(self, "bucket_inline", False) and self.on_bucket is not None and self.nbucket == 0 and (self.jobs.jobs or self.late.jobs or self.grams or self.tf):
+        if self.bucket_inline and self.on_bucket is not None and self.nbucket == 0 and (self.jobs.jobs or self.late.jobs or self.grams or self.tf):
             self._run(tidx)
             self.fork_side.wait_stream(torch.cuda.current_stream())
             with torch.cuda.stream(self.fork_side):
@@ -134,7 +139,7 @@ class Reductions:
 
     def flush(self, tidx):
         self._run(tidx)
-        if getattr(self, "forked", False):
+        if self.forked:
             torch.cuda.current_stream().wait_stream(self.fork_side)
             self.forked = False
 
@@ -222,8 +227,18 @@ def chain_ok(dims):
     return _ht_fused_bwd(dims) or (CHAIN128 and dims[3] == 128)
 
 
+def _wb_cols(dWb, C):
+    """rows [dW | db] of a weight-gradient launch -> the two column windows"""
+    return dWb[:, :C * C], dWb[:, C * C:]
+
+
+def _wb_record(dWb, ns, C):
+    """-> (dW, split count, db): what the reductions of a generated layer are queued from"""
+    return dWb[:, :C * C], ns, dWb[:, C * C:]
+
+
 def hypertem_core_bwd(saved, dout, dG_out, dims, chain=False, premul=False):
-    """-> dx, (dWbt, nsplit, (dbias partials, their count)); the graph-gradient partials are written into dG_out (nsG, N, T, T).
+    """-> dx, (dWbt, nsplit, dbias partials); the graph-gradient partials are written into dG_out (nsG, N, T, T).
     chain: dout already is dPre (the layer's output is not read);  premul (chain only): dx is returned multiplied by lrelu'(x)."""
     B, T, N, C = dims
     x, R, out, G, Wbt = saved
@@ -233,27 +248,27 @@ def hypertem_core_bwd(saved, dout, dG_out, dims, chain=False, premul=False):
         # data / graph gradients and the weight + bias gradient side by side in one launch: rows [dW_bt | db_bt]
         dx, dWb, ns, _ = ops.hypertem_bwd_wgrad(dout.view(B, T, N, C), None if chain else out.view(B, T, N, C), x.view(B, T, N, C), G, Wbt,
                                                 R.view(B, T, N, C) if R is not None else None, dG=dG_out, premul=chain and premul)
-        dWbt, dbias, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dWbt, dbias = _wb_cols(dWb, C)
         dx = dx.view(-1, C)
     elif C == 64:
         # the weight-gradient kernel also emits the bias gradient (column sums of dPre per (b,t)): rows [dW_bt | db_bt]
         dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dWbt, dbias, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dWbt, dbias = _wb_cols(dWb, C)
         dx, _, _ = ops.hypertem_bwd(dout.view(B, T, N, C), out.view(B, T, N, C), x.view(B, T, N, C), G, Wbt, dG=dG_out, want_dbias=False)
         dx = dx.view(-1, C)
     elif chain:                                       # C = 128, dPre chain: no pass reads the layer's output
         dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, colsum_d=True)
-        dWbt, dbias, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dWbt, dbias = _wb_cols(dWb, C)
         dR = ops.apply(dout, Wbt, MODE_TIME, BT, N, transw=True)
         dx, _ = ops.tmix_bwd_chain(dR.view(B, T, N, C), x.view(B, T, N, C), G, dout.view(B, T, N, C), premul=premul, dG=dG_out[0])
         dx = dx.view(-1, C)
     else:
         dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dWbt, dbias, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dWbt, dbias = _wb_cols(dWb, C)
         dR = ops.apply(dout, Wbt, MODE_TIME, BT, N, A2=out, transw=True, pro=PRO_DPRE)
         dx, _ = ops.tmix_bwd(dR.view(B, T, N, C), x.view(B, T, N, C), G, dout.view(B, T, N, C), out.view(B, T, N, C), dG=dG_out[0])
         dx = dx.view(-1, C)
-    return dx, (dWbt, ns, (dbias, nsb))
+    return dx, (dWbt, ns, dbias)
 
 
 CARRY_RED = os.environ.get("GPTST_CARRY_RED", "1") == "1"        # queued weight-gradient reductions as role workgroups of the routing backward (r05, late)
@@ -326,7 +341,7 @@ def ht_pair_bwd(saved1, saved0, dout, dG1, dG0, dims, dWb1=None):
     if r is None:
         return None
     dmid, dx0, dWb1, dWb0, ns = r
-    return dx0.view(-1, C), (dWb1[:, :C * C], ns, (dWb1[:, C * C:], ns)), (dWb0[:, :C * C], ns, (dWb0[:, C * C:], ns))
+    return dx0.view(-1, C), _wb_record(dWb1, ns, C), _wb_record(dWb0, ns, C)
 
 
 # ---- cap (GPTST.py:100-141) ----------------------------------------------------------------------------------------
@@ -392,19 +407,17 @@ def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
     assert not chain or chain_ok(dims)
     if C == 64:     # data gradient, weight gradient and bias gradient of the node-conditioned layer in one pass
         drec, dWn, dbn, ns = ops.apply_wgrad(dout, None if chain else out, rec, Wn, MODE_NODE, BT, N)
-        nsb = ns
     elif chain:     # C = 128, dPre chain: neither pass reads the layer's output
         drec = ops.apply(dout, Wn, MODE_NODE, BT, N, transw=True)
         dWb, ns = ops.wgrad(rec, dout, MODE_NODE, BT, N, colsum_d=True)                                          # rows [dWn | dbn] per split
-        dWn, dbn, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dWn, dbn = _wb_cols(dWb, C)
     else:
         drec = ops.apply(dout, Wn, MODE_NODE, BT, N, A2=out, transw=True, pro=PRO_DPRE)
         dWb, ns = ops.wgrad(rec, dout, MODE_NODE, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)                    # rows [dWn | dbn] per split
-        dWn, dbn, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
-    fused = None
+        dWn, dbn = _wb_cols(dWb, C)
     dc1, dv = ops.cap_rec_bwd(drec, c, v, reduce_nodes=CTX.NODE_REDUCE)
     gw, gb = g[pfx + "ln_p.weight"], g[pfx + "ln_p.bias"]
-    if fused is None and FUSE_CROSS and CAP_LIN and C == 64 and CTX.NODE_REDUCE is None and Y is None:
+    if FUSE_CROSS and CAP_LIN and C == 64 and CTX.NODE_REDUCE is None and Y is None:
         # r05: cross-time backward (role) + routing backward + the entry Linear's backward and the residual branch in ONE launch; dY never leaves LDS
         # r05: queued reductions of the layers already behind us ride in this launch — where it has the role form (idle slots: B*T + 4B <= 512 workgroups)
         carry = red.take_carry(CARRY_MB) if cross_role() and _C.lib().value("gptst_cap_route_roles_ok", B, T, N, C, HS, HT) == 1 else None
@@ -416,8 +429,9 @@ def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
             dx, dWp, dbp, dlogit, ddyn = lin
             red.jobs.bwd_pool(_ones(dev, dWp.shape[0]), dWp, gw.view(1, C * C))      # B*T (+ the node halves' rows, r06) partials
             red.jobs.bwd_pool(_ones(dev, dbp.shape[0]), dbp, gb.view(1, C))
-            return dx, (dWn, ns, (dbn, nsb), ddyn, dlogit)
-    if fused is None and FUSE_CROSS and CTX.NODE_REDUCE is None and Y is None:
+            return dx, (dWn, ns, dbn, ddyn, dlogit)
+    fused = None
+    if FUSE_CROSS and CTX.NODE_REDUCE is None and Y is None:
         fused = ops.cap_cross_route_bwd(x.view(B, T, N, C), p[pfx + "ln_p.weight"], p[pfx + "ln_p.bias"], c, dc1, dv, s, Rt, Ht, dyn,
                                         p[pfx + "mask_template"], B, T, HS, HT, flags=_zeros(x, 4 * B) if cross_role() else None)
     if fused is not None:
@@ -436,9 +450,10 @@ def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
         else:
             dx = ops.apply(dY, p[pfx + "ln_p.weight"], MODE_SHARED, BT, N, resid=dout, resid2=out, epi=EPI_ADD_DPRE)
         dWp, ns2 = ops.wgrad(dY, x, MODE_SHARED, BT, N, colsum_a=True)                     # rows [dWp | colsum dY]
-        red.jobs.bwd_pool(_ones(dev, ns2), dWp[:, :C * C], gw.view(1, C * C))
-        red.jobs.bwd_pool(_ones(dev, ns2), dWp[:, C * C:], gb.view(1, C))
-    return dx, (dWn, ns, (dbn, nsb), ddyn, dlogit)
+        dWp, dbp = _wb_cols(dWp, C)
+        red.jobs.bwd_pool(_ones(dev, ns2), dWp, gw.view(1, C * C))
+        red.jobs.bwd_pool(_ones(dev, ns2), dbp, gb.view(1, C))
+    return dx, (dWn, ns, dbn, ddyn, dlogit)
 
 
 _ONES = {}
@@ -467,24 +482,22 @@ def condlin_bwd(saved, dout, emb, wpool, bpool, g_wpool, g_bpool, d_emb, mode, d
     assert not chain or chain_ok(dims)
     if carried is not None:
         dx, dW, db, ns = carried
-        nsb = ns
     elif C == 64:
         dx, dW, db, ns = ops.apply_wgrad(dout, None if chain else out, x, Wg, mode, B * T, N, premul=chain and premul)
-        nsb = ns
     elif chain:     # C = 128, dPre chain
         dx = (ops.apply(dout, Wg, mode, B * T, N, transw=True, resid2=x, epi=EPI_PREMUL) if premul
               else ops.apply(dout, Wg, mode, B * T, N, transw=True))
         dWb, ns = ops.wgrad(x, dout, mode, B * T, N, colsum_d=True)
-        dW, db, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dW, db = _wb_cols(dWb, C)
     else:
         dx = ops.apply(dout, Wg, mode, B * T, N, A2=out, transw=True, pro=PRO_DPRE)
         dWb, ns = ops.wgrad(x, dout, mode, B * T, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dW, db, nsb = dWb[:, :C * C], dWb[:, C * C:], ns
+        dW, db = _wb_cols(dWb, C)
     dW = dW if dW.dim() == 2 else dW.view(ns * R, C * C)
     red.jobs.bwd_pool(emb, dW, g_wpool.view(K, C * C), nsplit=ns)
-    red.jobs.bwd_pool(emb, db, g_bpool, nsplit=nsb)
+    red.jobs.bwd_pool(emb, db, g_bpool, nsplit=ns)
     red.jobs.bwd_emb(dW, wpool.view(K, C * C), d_emb, nsplit=ns)
-    red.jobs.bwd_emb(db, bpool, d_emb, nsplit=nsb)
+    red.jobs.bwd_emb(db, bpool, d_emb, nsplit=ns)
     return dx
 
 
@@ -565,44 +578,39 @@ def gen_all(p, tidx, dims, which=(ENC, DEC), guide=True, defer=False):
 
 def sthcn_fwd(p, pfx, tidx, x, dims, num_route, gen=None, head=None, next_gen=None, kl=None):
     """head: (x after hyperTem1, its saved tuple) when the previous STHCN's last chain already ran this one's first layer;
-    next_gen: gen dict of the NEXT STHCN — its hyperTem1 then rides on this one's last chain; -> x, c1, saved[, next head].
+    next_gen: gen dict of the NEXT STHCN — its hyperTem1 rides on this one's last chain launch where the chain serves the shape;
+    -> x, c1, saved, next head (None: nothing rode along).
     kl: the step's KlCarry (the chain launches carry the KL path's backward; the encoder's first cap assignment is its last input)."""
     if gen is None:
         gen = gen_all(p, tidx, dims, which=(pfx,), guide=False)[pfx]
     A_all, hts, cps, d, Hm, ds, HS, HT = gen["gen"]
-    G_all, Wb, Wn, dadj, dyn = gen["G_all"], gen["Wb"], gen["Wn"], gen["dadj"], gen["dyn"]
-    sv = {}
-    nhead = None
+    Wn, dadj, dyn = gen["Wn"], gen["dadj"], gen["dyn"]
+    ht = lambda i, gn=gen: (gn["G_all"][i], gn["Wb"][2 * i], gn["Wb"][2 * i + 1])      # noqa: E731  (G, Wbt, bbt) of hyperTem i+1
+    cap = lambda i, x: cap_core_fwd(p, cps[i], x, dadj[i], dyn[i], Wn[2 * i], Wn[2 * i + 1], dims, num_route, HS, HT)   # noqa: E731
+    pairs = chain_fwd_ok(dims)       # hyperTem PAIRS on the slab: [2, 3] and [4, next 1] (the caps' node layers stay on the node-grouped apply64)
+    sv, nhead = {}, None
     if head is not None:
         x, sv["h1"] = head
     else:
-        x, sv["h1"] = hypertem_core_fwd(x, G_all[0], Wb[0], Wb[1], dims)
-    if chain_fwd_ok(dims):
-        # hyperTem PAIRS on the slab (the caps' node layers stay on the node-grouped apply64)
-        x, c1, sv["c1"] = cap_core_fwd(p, cps[0], x, dadj[0], dyn[0], Wn[0], Wn[1], dims, num_route, HS, HT)
+        x, sv["h1"] = hypertem_core_fwd(x, *ht(0), dims)
+    x, c1, sv["c1"] = cap(0, x)
+    if pairs:
         if kl is not None and kl.c1 is None:
             kl.c1 = c1                                     # (the encoder's: GPTST.py:141, 426)
-        (sv["h2"], sv["h3"]), x = ht_chain_fwd(x, [(G_all[1], Wb[2], Wb[3]), (G_all[2], Wb[4], Wb[5])], dims, kl)
-        x, _, sv["c2"] = cap_core_fwd(p, cps[1], x, dadj[1], dyn[1], Wn[2], Wn[3], dims, num_route, HS, HT)
-        if next_gen is not None:
-            hs, xl = ht_chain_fwd(x, [(G_all[3], Wb[6], Wb[7]), (next_gen["G_all"][0], next_gen["Wb"][0], next_gen["Wb"][1])], dims, kl)
-            sv["h4"] = hs[0]
-            x = hs[0][2]
-            nhead = (xl, hs[1])
-        else:
-            x, sv["h4"] = hypertem_core_fwd(x, G_all[3], Wb[6], Wb[7], dims)
+        (sv["h2"], sv["h3"]), x = ht_chain_fwd(x, [ht(1), ht(2)], dims, kl)
     else:
-        x, c1, sv["c1"] = cap_core_fwd(p, cps[0], x, dadj[0], dyn[0], Wn[0], Wn[1], dims, num_route, HS, HT)
-        x, sv["h2"] = hypertem_core_fwd(x, G_all[1], Wb[2], Wb[3], dims)
-        x, sv["h3"] = hypertem_core_fwd(x, G_all[2], Wb[4], Wb[5], dims)
-        x, _, sv["c2"] = cap_core_fwd(p, cps[1], x, dadj[1], dyn[1], Wn[2], Wn[3], dims, num_route, HS, HT)
-        x, sv["h4"] = hypertem_core_fwd(x, G_all[3], Wb[6], Wb[7], dims)
+        x, sv["h2"] = hypertem_core_fwd(x, *ht(1), dims)
+        x, sv["h3"] = hypertem_core_fwd(x, *ht(2), dims)
+    x, _, sv["c2"] = cap(1, x)
+    if pairs and next_gen is not None:
+        (sv["h4"], h1n), xn = ht_chain_fwd(x, [ht(3), ht(0, next_gen)], dims, kl)
+        x, nhead = sv["h4"][2], (xn, h1n)
+    else:
+        x, sv["h4"] = hypertem_core_fwd(x, *ht(3), dims)
     sv["emb"] = gen["emb"]
     sv["gen"] = gen["gen"]
     sv["slot"] = gen.get("slot")
-    if next_gen is not None:
-        return x, c1, sv, nhead
-    return x, c1, sv
+    return x, c1, sv, nhead
 
 
 def _grad_buffers(red, slot, N, T, HmT, ref, nsG):
@@ -611,7 +619,7 @@ def _grad_buffers(red, slot, N, T, HmT, ref, nsG):
     if slot is None:
         return torch.empty(4, nsG, N, T, T, device=ref.device), torch.empty(4, N, HmT, device=ref.device)
     k, n = slot
-    if getattr(red, "_dG", None) is None or red._dG.shape[0] != 4 * n:
+    if red._dG is None or red._dG.shape[0] != 4 * n:
         red._dG = torch.empty(4 * n, nsG, N, T, T, device=ref.device)
         red._dA = torch.empty(4 * n, N, HmT, device=ref.device)
     return red._dG[4 * k:4 * k + 4], red._dA[4 * k:4 * k + 4]
@@ -636,19 +644,19 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
     CC, BT = C * C, B * T
 
     def queue_ht(h, hp):
-        dWbt, ns, (dbias, nsb) = hp                              # (ns*BT, CC), possibly a column window of [dW | db] rows
+        dWbt, ns, dbias = hp                                     # (ns*BT, CC), possibly a column window of [dW | db] rows
         J.bwd_pool(time_eb, dWbt, g[h + "weights_pool"].view(d, CC), nsplit=ns)
-        J.bwd_pool(time_eb, dbias, g[h + "bias_pool"], nsplit=nsb)
+        J.bwd_pool(time_eb, dbias, g[h + "bias_pool"], nsplit=ns)
         J.bwd_emb(dWbt, p[h + "weights_pool"].view(d, CC), d_te, nsplit=ns)
-        J.bwd_emb(dbias, p[h + "bias_pool"], d_te, nsplit=nsb)
+        J.bwd_emb(dbias, p[h + "bias_pool"], d_te, nsplit=ns)
 
     def queue_cap(c, cp):
-        dWn, ns, (dbn, nsb), ddyn, dlogit = cp
+        dWn, ns, dbn, ddyn, dlogit = cp
         dW2 = dWn if dWn.dim() == 2 else dWn.view(ns * N, CC)      # (ns*N, CC), possibly a column window of [dW | db] rows
         J.bwd_pool(nes, dW2, g[c + "weights_spa"].view(d, CC), nsplit=ns)
-        J.bwd_pool(nes, dbn, g[c + "bias_spa"], nsplit=nsb)
+        J.bwd_pool(nes, dbn, g[c + "bias_spa"], nsplit=ns)
         J.bwd_emb(dW2, p[c + "weights_spa"].view(d, CC), dnes, nsplit=ns)
-        J.bwd_emb(dbn, p[c + "bias_spa"], dnes, nsplit=nsb)
+        J.bwd_emb(dbn, p[c + "bias_spa"], dnes, nsplit=ns)
         dd2 = ddyn.view(B, HT * T * HS)
         J.bwd_pool(tes, dd2, g[c + "t_adj"].view(ds, HT * T * HS))
         J.bwd_emb(dd2, p[c + "t_adj"].view(ds, HT * T * HS), d_tes)
@@ -686,7 +694,7 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
         else:       # (C = 128: the other layers write ONE graph-gradient partial; this kernel writes one per sample)
             dWb, dGb, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv)
             torch.sum(dGb, 0, out=dG_all[0][0])
-        hp1 = (dWb[:, :C * C], 1, (dWb[:, C * C:], 1))
+        hp1 = _wb_record(dWb, 1, C)
         wb = _wb_view(g["encoder.dim_in_flow.weight"], g["encoder.dim_in_flow.bias"])
         if wb is not None:
             red.jobs.bwd_pool(_ones(dd.device, dinp.shape[0]), dinp, wb)
@@ -699,7 +707,7 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
         assert chain and premul_in
         ns = ops.wgrad_nsplit(MODE_TIME, B * T, N, C)
         dWb = torch.empty(ns * B * T, C * C + C, device=dd.device, dtype=torch.float32)
-        hp1 = (dWb[:, :C * C], ns, (dWb[:, C * C:], ns))
+        hp1 = _wb_record(dWb, ns, C)
         dd = PendingH1(sv["h1"], dd, dG_all[0], dWb)
     else:
         dd, hp1 = hypertem_core_bwd(sv["h1"], dd, dG_all[0], dims, chain, premul_in)
@@ -797,16 +805,29 @@ def kl_head(p, g, sv_g, prob, c1, N, w, sws, red, chain=False, carried=None):
     return dh2
 
 
+def _linear_out_bwd(p, g, pfx, h, dy, C, chain, d_h=None):
+    """Backward of an output Linear(C -> J) on the LeakyReLU output h (decoder.dim_flow_out, GPTST.py:455; MLP_RL.ln3, :33) from the gradient
+    dy (rows, J) of its result: weight / bias gradients into g, -> d_h [+ d_h, a gradient that reaches h directly];  chain: times lrelu'(h),
+    i.e. the dPre the layers below expect."""
+    J = dy.shape[1]
+    dh = ops.lin_in(dy, J, J, p[pfx + "weight"], None, C, wlayout=1)
+    ops.rowouter(dy, J, J, h, g[pfx + "weight"], 1, asum=g[pfx + "bias"])
+    if d_h is not None:
+        dh = dh + d_h
+    if chain:
+        dh = dh * torch.where(h > 0, 1.0, 0.01)
+    return dh
+
+
 def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chain=False, carried=(None, None)):
-    """dlogit (BTN,HS): gradient of the logits — or dh2 (BTN,C) when kl_head already went through ln3 (chain: dh2 is dPre).
+    """dlogit (BTN,HS): gradient of the logits — or dh2 (BTN,C) when kl_head already went through ln3 (chain: dh2 is dPre; from dlogit it is
+    made so here).
     carried: outputs of the time-conditioned layer's and of the low-rank input layers' launches already run by earlier launches (KlCarry)."""
     B, T, N, C = dims
     t4m, s1, s2, h2 = saved[:4]
     m = "encoder.MLP_RL."
     if dh2 is None:
-        HS = dlogit.shape[1]
-        dh2 = ops.lin_in(dlogit, HS, HS, p[m + "ln3.weight"], None, C, wlayout=1)
-        ops.rowouter(dlogit, HS, HS, h2, g[m + "ln3.weight"], 1, asum=g[m + "ln3.bias"])
+        dh2 = _linear_out_bwd(p, g, m + "ln3.", h2, dlogit, C, chain)
     d_t4m = _zeros(t4m, *t4m.shape)
     dh1 = condlin_bwd(s2, dh2, t4m, p[m + "weights_pool_tem"], p[m + "bias_pool_tem"], g[m + "weights_pool_tem"],
                       g[m + "bias_pool_tem"], d_t4m, MODE_TIME, dims, red, chain, True, carried=carried[0])
@@ -815,7 +836,7 @@ def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chai
         neb, wpool, bpool = p["encoder.neb4mask"], p[m + "weights_pool_spa"], p[m + "bias_pool_spa"]
         K = neb.shape[1]
         dWb, dinp = carried[1] if carried[1] is not None else ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1[1])
-        dW, db = dWb[:, :C * C], dWb[:, C * C:]
+        dW, db = _wb_cols(dWb, C)
         red.jobs.bwd_pool(neb, dW, g[m + "weights_pool_spa"].view(K, C * C))
         red.jobs.bwd_pool(neb, db, g[m + "bias_pool_spa"])
         red.jobs.bwd_emb(dW, wpool.view(K, C * C), g["encoder.neb4mask"])
@@ -904,54 +925,56 @@ def _in_proj_grads(source, base, dY, gW, gb, mask, fill, red):
         ops.rowouter(source, base + 2, base, dY, gW, 0, csum=gb, mask=mask, fill=fill)
 
 
-def model_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, tidx=None, dec_gen=None, lowrank_in=False, kl=None):
-    """Masked-autoencoder body — GPTST.py:415-421 + 453-456.  mask (BTN*base) fp32, 1 = visible; None -> no masking (eval).
-    dec_gen: the decoder STHCN's gen dict — its first hyperTem layer then rides on the encoder's last chain launch and the result comes back
-    as a fifth value, to be passed to decoder_fwd(dec_head=...) (None when the chain path does not serve the shape).
+class Forward(NamedTuple):
+    """what autoencoder_fwd returns, whichever launches it chose"""
+    emb: Any        # (BTN, C) encoder output
+    c1: Any         # (BT, HS, N) the encoder's first cap assignment
+    dec: Any        # (BTN, C) decoder STHCN output (None: encoder only)
+    out: Any        # (BTN, base) reconstruction (None: the head was not asked for)
+    sv_e: Any
+    sv_d: Any
+
+
+def autoencoder_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, tidx=None, lowrank_in=False, kl=None, head=True,
+                    decoder=True, join=True):
+    """Masked-autoencoder body — GPTST.py:415-421 + 453-456 -> Forward.  mask (BTN*base) fp32, 1 = visible; None -> no masking (eval).
+    gen: the step's gen_all() result (None: generated here).  decoder=False: the encoder alone (fine-tuning's embedding).  head: also
+    decoder.dim_flow_out (False: the caller's loss_tail goes through it).
     lowrank_in: the caller's backward is the dPre chain (model_bwd(chain=True)) — the input projection + encoder hyperTem1 then run as the
-    rank-2 kernel pair of encin.hip where the shape allows.  kl: the step's KlCarry (sthcn_fwd)."""
+    rank-2 kernel pair of encin.hip where the shape allows.  kl: the step's KlCarry (sthcn_fwd).
+    join: the decoder's first hyperTem layer rides on the encoder's last chain launch where the chain serves the shape (False: callers that
+    have always run the two layers as launches of their own)."""
     B, T, N, C = dims
     if tidx is None:
         tidx = source[:, :, 0, base:base + 2].contiguous()
-    head = None
-    if lowrank_in and gen is not None and encin_ok(dims, base):
+    gen_e, gen_d = (gen[ENC], gen[DEC] if decoder else None) if gen is not None else (None, None)
+    first = None
+    if lowrank_in and gen_e is not None and encin_ok(dims, base):
         # input projection + encoder hyperTem1 on the rank-2 structure of the input: no x0, no GEMM (ops.encin_ht1_fwd)
         w, bi = p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"]
-        G1, Wb = gen["G_all"][0], gen["Wb"]
+        G1, Wb = gen_e["G_all"][0], gen_e["Wb"]
         o1, ab, wv = ops.encin_ht1_fwd(source, base, mask, 0.0 if mask is None else scaler_zeros, w, bi, G1, Wb[0], Wb[1])
-        head = (o1.view(-1, C), EncIn(source, mask, 0.0 if mask is None else scaler_zeros, Wb[0], ab, wv))
+        first = (o1.view(-1, C), EncIn(source, mask, 0.0 if mask is None else scaler_zeros, Wb[0], ab, wv))
         x0 = None
     else:
         x0 = ops.lin_in(source, base + 2, base, p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"], C,
                         mask=mask, fill=scaler_zeros)                                                      # :416-418
-    if dec_gen is not None:
-        emb, c1, sv_e, dec_head = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, next_gen=dec_gen, head=head, kl=kl)
-        return emb, c1, tidx, sv_e, dec_head
-    emb, c1, sv_e = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen, head=head, kl=kl)                # :421
-    return emb, c1, tidx, sv_e
-
-
-def decoder_fwd(p, tidx, emb, dims, num_route, gen=None, head=True, dec_head=None, kl=None):
-    dec, _, sv_d = sthcn_fwd(p, DEC, tidx, emb, dims, num_route, gen=gen, head=dec_head, kl=kl)            # :454
-    if not head:
-        return None, dec, sv_d
-    out = ops.rowdot(dec, p["decoder.dim_flow_out.weight"], p["decoder.dim_flow_out.bias"])                 # :455
-    return out, dec, sv_d
+    emb, c1, sv_e, dec_h1 = sthcn_fwd(p, ENC, tidx, x0, dims, num_route, gen=gen_e, head=first, next_gen=gen_d if join else None, kl=kl)   # :421
+    if not decoder:
+        return Forward(emb, c1, None, None, sv_e, None)
+    dec, _, sv_d, _ = sthcn_fwd(p, DEC, tidx, emb, dims, num_route, gen=gen_d, head=dec_h1, kl=kl)         # :454
+    out = ops.rowdot(dec, p["decoder.dim_flow_out.weight"], p["decoder.dim_flow_out.bias"]) if head else None   # :455
+    return Forward(emb, c1, dec, out, sv_e, sv_d)
 
 
 def model_bwd(p, g, source, mask, tidx, sv_e, sv_d, dec, d_out, d_dec, dims, base, scaler_zeros, red, dd=None, chain=False):
-    """Backward of decoder_fwd . model_fwd given d_out (BTN, base) [and optional d_dec (BTN, C)] — or given dd, the gradient
+    """Backward of autoencoder_fwd given d_out (BTN, base) [and optional d_dec (BTN, C)] — or given dd, the gradient
     w.r.t. the decoder STHCN output, when loss_tail already went through dim_flow_out.  Parameter-gradient reductions are queued
     on ``red`` (Reductions): the caller runs red.flush(tidx) once the whole backward is enqueued.
-    chain (only with dd from loss_tail(chain=True)): the dPre chain, see chain_ok()."""
+    chain: the dPre chain, see chain_ok() (dd from loss_tail(chain=True), or made from d_out here)."""
     B, T, N, C = dims
-    wo = "decoder.dim_flow_out."
-    assert not chain or dd is not None
     if dd is None:
-        dd = ops.lin_in(d_out, base, base, p[wo + "weight"], None, C, wlayout=1)
-        if d_dec is not None:
-            dd = dd + d_dec
-        ops.rowouter(d_out, base, base, dec, g[wo + "weight"], 1, asum=g[wo + "bias"])
+        dd = _linear_out_bwd(p, g, "decoder.dim_flow_out.", dec, d_out, C, chain, d_h=d_dec)
     # the decoder's hyperTem1 and the encoder's hyperTem4 are adjacent (GPTST.py:271 -> :454): one pair launch, unless the decoder's gradient
     # bucket must be complete when its backward ends (data-parallel overlap / a side stream flush the decoder's reductions right here)
     # r05: also under the data-parallel bucket overlap — the decoder's bucket then closes ONE LAUNCH later, behind the pair launch that finishes its
@@ -967,3 +990,50 @@ def model_bwd(p, g, source, mask, tidx, sv_e, sv_d, dec, d_out, d_dec, dims, bas
     red.flush_async(tidx)                                   # ... and the encoder's with the guide's
     if d_x0 is not None:                                    # (None: the low-rank first layer produced the input-projection gradient itself)
         _in_proj_grads(source, base, d_x0, g["encoder.dim_in_flow.weight"], g["encoder.dim_in_flow.bias"], mask, scaler_zeros, red)
+
+
+def step_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, scaler_zeros, red, loss, stats, sws=None, with_kl=False, kl=None):
+    """The pretraining loss (masked MAE [+ 0.1 KL], Run.py:92-100) and the whole backward behind autoencoder_fwd / guide_fwd, for the steppers.
+    loss: (sigma, mu, mape threshold).  sws (the step's per-workgroup loss statistics, zeroed): the FUSED heads — loss_tail and kl_head go
+    through dim_flow_out / ln3 with their backward in one pass each (fw.out is not needed), on the dPre chain where chain_ok(dims); the caller
+    folds sws into the statistics.  sws None: the loss kernels on fw.out, sums straight into `stats`.  kl: the step's KlCarry, whose stages
+    the forward's chain launches already ran."""
+    B, T, N, C = dims
+    sigma, mu, thresh = loss
+    if sws is not None:
+        chain = chain_ok(dims)                                                 # dPre chain: no backward kernel re-reads its layer's output
+        done = kl.carried if kl is not None else (lambda st: None)             # outputs of the stages the chain launches carried
+        _, dd = loss_tail(p, g, fw.dec, source, mask, base, sigma, mu, thresh, sws, red, chain=chain)
+        model_bwd(p, g, source, mask, tidx, fw.sv_e, fw.sv_d, fw.dec, None, None, dims, base, scaler_zeros, red, dd=dd, chain=chain)
+        if with_kl:
+            dh2 = kl_head(p, g, sv_g, prob, fw.c1, N, 0.1, sws, red, chain=chain, carried=done(1))
+            guide_bwd(p, g, source, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=(done(2), done(3)))
+    else:
+        M = B * T * N
+        ops.mae_fwd(fw.out, source, base + 2, mask, sigma, mu, thresh, M, base, stats)
+        d_out = ops.mae_bwd(fw.out, source, base + 2, mask, sigma, mu, thresh, M, base, stats, normalize=False)
+        model_bwd(p, g, source, mask, tidx, fw.sv_e, fw.sv_d, fw.dec, d_out, None, dims, base, scaler_zeros, red)
+        if with_kl:
+            dlogit = ops.kl(prob, fw.c1, N, 0.1, stats)
+            guide_bwd(p, g, source, tidx, sv_g, dlogit, dims, base, red)
+
+
+def module_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, scaler_zeros, red, d_out, d_dec=None, d_prob=None, chain=False):
+    """The backward behind autoencoder_fwd / guide_fwd when the loss is the caller's (GPTST_Model under autograd): d_out (BTN, base),
+    d_dec (BTN, C) and d_prob (BTN, HS) are the gradients of the returned reconstruction, decoder state and guide probabilities (None:
+    did not enter the loss).  chain: on the dPre chain (the forward ran with lowrank_in=True)."""
+    model_bwd(p, g, source, mask, tidx, fw.sv_e, fw.sv_d, fw.dec, d_out, d_dec, dims, base, scaler_zeros, red, chain=chain)
+    if d_prob is not None:      # softmax backward: dlogit = prob * (d_prob - sum(d_prob * prob)), then MLP_RL.ln3 (GPTST.py:33)
+        dlogit = (prob * (d_prob - (d_prob * prob).sum(-1, keepdim=True))).contiguous()
+        guide_bwd(p, g, source, tidx, sv_g, dlogit, dims, base, red, chain=chain)
+
+
+def warm_up(fn):
+    """Before a graph capture: run fn twice on a side stream (allocator, lazy kernel attributes), then synchronise."""
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(2):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    torch.cuda.synchronize()

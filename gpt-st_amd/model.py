@@ -114,17 +114,17 @@ class _PretrainFn(torch.autograd.Function):
         # pre: (tidx, gen, prob, sv_g) of forward_pretrain — the generated parameters and the guide classifier's forward, which the mask
         # needed first, are computed ONCE per call (r03 review: the guide ran twice)
         tidx, gen, prob, sv_g = pre
-        emb, c1, tidx, sv_e = engine.model_fwd(p, source, mask, dims, base, model.num_route, model.scaler_zeros, gen=gen[engine.ENC], tidx=tidx)
-        out, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, model.num_route, gen=gen[engine.DEC])
-        ctx.model, ctx.saved = model, (source, mask, tidx, sv_g, sv_e, sv_d, dec, prob, dims)
+        # (join=False: the eager node has always run encoder hyperTem4 / decoder hyperTem1 as launches of their own)
+        fw = engine.autoencoder_fwd(p, source, mask, dims, base, model.num_route, model.scaler_zeros, gen=gen, tidx=tidx, join=False)
+        ctx.model, ctx.saved = model, (source, mask, tidx, sv_g, fw, prob, dims)
         B, T, N, C = dims
-        ctx.mark_non_differentiable(c1)
-        return out.view(B, T, N, base), dec.view(B, T, N, C), prob.view(B, T, N, -1), c1
+        ctx.mark_non_differentiable(fw.c1)
+        return fw.out.view(B, T, N, base), fw.dec.view(B, T, N, C), prob.view(B, T, N, -1), fw.c1
 
     @staticmethod
     def backward(ctx, d_out, d_dec, d_prob, _dc):
         model = ctx.model
-        source, mask, tidx, sv_g, sv_e, sv_d, dec, prob, dims = ctx.saved
+        source, mask, tidx, sv_g, fw, prob, dims = ctx.saved
         B, T, N, C = dims
         base = model.input_base_dim
         p = model.param_views()
@@ -134,12 +134,9 @@ class _PretrainFn(torch.autograd.Function):
         d_out = d_out.contiguous().view(-1, base)
         d_dec2 = None if d_dec is None or not bool(d_dec.any()) else d_dec.contiguous().view(-1, C)
         red = engine.Reductions()
-        engine.model_bwd(p, g, source, mask, tidx, sv_e, sv_d, dec, d_out, d_dec2, dims, base, model.scaler_zeros, red)
         has_kl = d_prob is not None and bool(d_prob.any())
-        if has_kl:      # softmax backward: dlogit = prob * (d_prob - sum(d_prob * prob))
-            dp = d_prob.contiguous().view(-1, prob.shape[1])
-            dlogit = (prob * (dp - (dp * prob).sum(-1, keepdim=True))).contiguous()
-            engine.guide_bwd(p, g, source, tidx, sv_g, dlogit, dims, base, red)
+        engine.module_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, model.scaler_zeros, red, d_out, d_dec2,
+                          d_prob.contiguous().view(-1, prob.shape[1]) if has_kl else None)
         red.flush(tidx)
         grads = []
         for k in model.param_keys:
@@ -354,8 +351,8 @@ class GPTST_Model(nn.Module):
     def forward_fune(self, source, label):
         source = source.contiguous().float()
         with torch.no_grad():
-            emb, _, _, _ = engine.model_fwd(self.param_views(), source, None, self._dims(source), self.input_base_dim,
-                                            self.num_route, self.scaler_zeros)
+            emb = engine.autoencoder_fwd(self.param_views(), source, None, self._dims(source), self.input_base_dim,
+                                         self.num_route, self.scaler_zeros, decoder=False).emb
         B, T, N, _ = source.shape
         e = emb.view(B, T, N, self.hidden_dim)
         return e, e, e, e, e

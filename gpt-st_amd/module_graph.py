@@ -126,75 +126,43 @@ class GraphedPretrain:
                 label, counts = ops.mask_labels(prob.reshape(self.M, -1))
                 mask = ops.mask_adaptive(label, counts, self.ctrl[:self.HS], self.ctrl[self.HS:], torch.rand(self.M, device=self.dev),
                                          torch.rand(self.M, device=self.dev), m.ada_type == "all", base)[2]
-            if engine.chain_fwd_ok(dims):
-                emb, c1, tidx, sv_e, dec_head = engine.model_fwd(p, src, mask, dims, base, m.num_route, m.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                                 dec_gen=gen[engine.DEC], lowrank_in=lowrank)
-            else:
-                emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, m.num_route, m.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                       lowrank_in=lowrank)
-                dec_head = None
-            out, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, m.num_route, gen=gen[engine.DEC], dec_head=dec_head)
+            fw = engine.autoencoder_fwd(p, src, mask, dims, base, m.num_route, m.scaler_zeros, gen=gen, tidx=tidx, lowrank_in=lowrank)
         finally:
             engine.CTX.ARENA = None
         B, T, N, C = dims
-        self.out, self.dec, self.prob, self.c1, self.mask = out.view(B, T, N, base), dec.view(B, T, N, C), prob.view(B, T, N, -1), c1, mask
-        self.saved = (tidx, gen, sv_g, sv_e, sv_d, dec, prob)
+        self.out, self.dec, self.prob, self.c1, self.mask = fw.out.view(B, T, N, base), fw.dec.view(B, T, N, C), prob.view(B, T, N, -1), fw.c1, mask
+        self.saved = (tidx, gen, sv_g, fw, prob)
 
     def _bwd_body(self, has_kl, d_dec=None):
         m, base, dims = self.model, self.base, self.dims
         B, T, N, C = dims
         p, g = m.param_views(), self.g
-        tidx, gen, sv_g, sv_e, sv_d, dec, prob = self.saved
+        tidx, gen, sv_g, fw, prob = self.saved
         engine.CTX.ARENA = self.arena_b
         self.arena_b.begin(zero=True)
         try:
             self.gflat.zero_()
             red = engine.Reductions()
-            chain = engine.chain_ok(dims)
-            wo = "decoder.dim_flow_out."
-            dd = ops.lin_in(self.d_out, base, base, p[wo + "weight"], None, C, wlayout=1)            # backward of dim_flow_out (GPTST.py:455)
-            ops.rowouter(self.d_out, base, base, dec, g[wo + "weight"], 1, asum=g[wo + "bias"])
-            if d_dec is not None:                                                                   # (eager only: flow_decode entered the loss)
-                dd = dd + d_dec
-            if chain:                                                                               # dPre chain: times lrelu'(dec), dec = a LeakyReLU output
-                dd = dd * torch.where(dec > 0, 1.0, 0.01)
-            engine.model_bwd(p, g, self.src, self.mask, tidx, sv_e, sv_d, dec, None, None, dims, base, m.scaler_zeros, red, dd=dd, chain=chain)
-            if has_kl:      # softmax backward: dlogit = prob * (d_prob - sum(d_prob * prob)), then MLP_RL.ln3 (GPTST.py:33)
-                dp = self.d_prob
-                dlogit = (prob * (dp - (dp * prob).sum(-1, keepdim=True))).contiguous()
-                mm = "encoder.MLP_RL."
-                h2, HS = sv_g[3], self.HS
-                dh2 = ops.lin_in(dlogit, HS, HS, p[mm + "ln3.weight"], None, C, wlayout=1)
-                ops.rowouter(dlogit, HS, HS, h2, g[mm + "ln3.weight"], 1, asum=g[mm + "ln3.bias"])
-                if chain:
-                    dh2 = dh2 * torch.where(h2 > 0, 1.0, 0.01)
-                engine.guide_bwd(p, g, self.src, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain)
+            # the forward ran with lowrank_in = chain_ok(dims): the backward is the dPre chain there (d_dec: eager only, flow_decode entered the loss)
+            engine.module_bwd(p, g, self.src, self.mask, tidx, fw, prob, sv_g, dims, base, m.scaler_zeros, red, self.d_out, d_dec,
+                              self.d_prob if has_kl else None, chain=engine.chain_ok(dims))
             red.flush(tidx)
             self._bwd_keep = red                                 # (the buffers its jobs point at live in the graph's pool)
         finally:
             engine.CTX.ARENA = None
 
     # ---- capture -----------------------------------------------------------------------------------------------------------------------------------
-    def _warm(self, fn):
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                fn()
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-
     def _capture_fwd(self):
         with torch.no_grad():
             self.ctrl.copy_(torch.tensor(list(range(self.HS)) + [self.M // 8, self.M // 8], dtype=torch.int32))      # plausible budgets for the warm-up
-            self._warm(self._fwd_body)
+            engine.warm_up(self._fwd_body)
             self.gf = torch.cuda.CUDAGraph()
             with torch.cuda.graph(self.gf, capture_error_mode="thread_local"):
                 self._fwd_body()
 
     def _capture_bwd(self, has_kl):
         with torch.no_grad():
-            self._warm(lambda: self._bwd_body(has_kl))
+            engine.warm_up(lambda: self._bwd_body(has_kl))
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local"):
                 self._bwd_body(has_kl)

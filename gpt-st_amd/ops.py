@@ -818,12 +818,6 @@ def mask_random(noise, k, ws=None, u24=False, jobs=None):
 MASK_SMALL = 1 << 13      # cells up to which the whole mask generation is one single-workgroup launch (masksel.hip MSS_MAXM)
 
 
-def labels_and_counts(prob, label):
-    """(label, counts) for mask_adaptive: the guide's rowdot already produced the argmax labels and gptst_mask_adaptive histograms
-    them itself (counts = None)."""
-    return label, None
-
-
 def mask_labels(prob):
     """prob (rows, HS) -> label int32 (rows), counts int32 (HS)."""
     _chk(prob)

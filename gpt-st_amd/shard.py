@@ -26,7 +26,7 @@ import threading
 import torch
 
 from . import engine, ops
-from .step import PretrainStep, U24, DEFER_GEN
+from .step import PretrainStep, U24
 
 
 def is_node_local(key):
@@ -226,6 +226,7 @@ class ThreadNodeGroup:
 class ShardedPretrainStep(PretrainStep):
     """One optimisation step of a rank that owns nodes [n0, n1) of N (node_ranges: shard widths may differ by one).  Unequal shards
     need models built with node_capacity = the widest shard, so that [flat gradient | statistics] has the same layout on every rank."""
+    DETERMINISTIC_MODE = False      # the sharded step has never taken the bit-reproducible launch forms: GPTST_DETERMINISTIC is not read here
 
     def __init__(self, model_local, args_local, n_global, group, scaler_mean, scaler_std, batch_size, seed=0, use_graph=None):
         """use_graph: None = capture the step in a hipGraph when the group's collectives are capturable (see the module docstring)."""
@@ -259,6 +260,9 @@ class ShardedPretrainStep(PretrainStep):
         self.noise_a_g, self.noise_r_g = self.noise_ar_g[:Mg], self.noise_ar_g[Mg:]
         self.tail = None                                    # single stream: collectives order against everything
         self.global_count_scale = True
+        # ---- where this step differs from PretrainStep's body besides the hooks below ----
+        self.node_reduce = group.all_reduce_                # cap's cluster aggregations sum over all ranks' nodes
+        self.join_enc_dec = self.fused_tails                # the unfused sharded step runs encoder hyperTem4 / decoder hyperTem1 as launches of their own
         named = dict(model_local.named_parameters())
         self.local_keys = [k for k in named if is_node_local(k)]
         self.repl_keys = [k for k in named if is_replicated_compute(k)]
@@ -323,22 +327,33 @@ class ShardedPretrainStep(PretrainStep):
         B = self.B if B is None else B
         return flat_global.view(B, self.T, self.Ng, per_cell)[:, :, self.n0:self.n1].contiguous().view(-1)
 
-    def _mask(self, phase, prob, label=None, jobs=None):
-        """label: the guide's argmax labels of the local cells (rowdot's by-product) — else taken from prob;  jobs: the STHCNs' generation table
-        (engine.gen_all(defer=True)), launched by the mask call — inside its launch where that is the cooperative one"""
+    def _noise_buffer(self, phase):
+        """the GLOBAL mask noise (Philox keyed by [seed, step]: identical on every rank)"""
+        return self.noise_g if phase == 0 else self.noise_ar_g
+
+    def _need_guide(self, phase):
+        """the fused form skips the classifier in the random-mask phase; the unfused form always runs it (GPTST_ALWAYS_GUIDE is not read here)"""
+        return phase == 1 or not self.fused_tails
+
+    def _make_mask(self, phase, prob, label, pend):
+        """The selection over the GLOBAL cells, cut to this rank's node columns.  label: the guide's argmax labels of the local cells;
+        pend: the STHCNs' generation table (engine.gen_all(defer=True)), launched by the mask call — inside its launch where that is the cooperative one"""
         a, base = self.args, self.base
         Mg = self.B * self.T * self.Ng
-        ws = self.arena.zeros(ops.mask_ws_floats())        # the selections' histogram scratch: zeroed by the step's first launch
+        ws = self._mask_ws()
         if phase == 0:
-            mask_g = ops.mask_random(self.noise_g, int(Mg * base * a.mask_ratio), ws=ws, u24=U24, jobs=jobs)
+            mask_g = ops.mask_random(self.noise_g, int(Mg * base * a.mask_ratio), ws=ws, u24=U24, jobs=pend)
         else:
-            if label is None:
-                label = ops.mask_labels(prob)[0]                                               # local cells (B,T,Nl)
             label_g = self._gather_labels(label, self.B)
             mask_g = ops.mask_adaptive(label_g, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a_g, self.noise_r_g,
-                                       a.ada_type == "all", base, ws=ws, u24=U24, jobs=jobs)[2]  # (class histogram of the gathered labels: taken inside)
+                                       a.ada_type == "all", base, ws=ws, u24=U24, jobs=pend)[2]  # (class histogram of the gathered labels: taken inside)
         self.last_mask_global = mask_g
         return self._cols(mask_g, base)
+
+    def _fold_stats(self, sws):
+        """always into the gradient buffer's tail, which the all-reduce moves.  Unfused (sws None): a zero row — only the fold's other job, stats[5] <-
+        this rank's hand-off expiries, so that every rank skips the update and re-runs the step together, as on the fused path"""
+        ops.stats_fold(sws if sws is not None else self.arena.zeros(1, 4), self.stats)
 
     def step(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None):
         """source: this rank's (B,T,Nl,base+2) slice; injected noise (tests) covers the GLOBAL (B,T,N[,base]) cells."""
@@ -361,89 +376,14 @@ class ShardedPretrainStep(PretrainStep):
             del self._unseen[:2048]
         if not self.shard_graph:
             self.inject_noise = inject
-            self._sbody(phase)
+            self._body(phase)
             return
-        key = (phase, inject)
+        key = (phase, inject, False)            # one hipGraph per (phase, injected noise), kernels and collectives: the base class's capture
         if key not in self.graphs:
-            self._scapture(key)
-        self.graphs[key].replay()
+            self._capture(key)
+        self.graphs[key][0].replay()
 
-    def _scapture(self, key):
-        """One hipGraph per (phase, injected noise): warm-up on a side stream, capture, undo the warm-up updates."""
-        phase, self.inject_noise = key
-        keep = (self.model.flat.clone(), self.m.clone(), self.v.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                self._sbody(phase)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            self._sbody(phase)
-        self.graphs[key] = g
-        self.model.flat.copy_(keep[0]); self.m.copy_(keep[1]); self.v.copy_(keep[2])
-        torch.cuda.synchronize()
-
-    def _sbody(self, phase):
-        if not self.safe_mode:
-            return self._sbody_impl(phase)
-        with engine.no_handoffs():
-            return self._sbody_impl(phase)
-
-    def _sbody_impl(self, phase):
-        """The device side of one step: kernels and collectives in stream order (eager, or inside a capture)."""
-        mdl, a, base, dims = self.model, self.args, self.base, self.dims
-        p, g = mdl.param_views(), self.g
-        M = self.B * self.T * self.Nl
-        ctx = engine.CTX
-        ctx.ARENA, ctx.NODE_REDUCE = self.arena, self.group.all_reduce_
-        try:
-            src = self.src
-            # zero_grad + the step's zero scratch + the time index (every node carries the same one, GPTST.py:256-257) + the GLOBAL mask noise
-            # (Philox keyed by [seed, step]: identical on every rank) in ONE launch
-            noise = None if self.inject_noise else (self.noise_g if phase == 0 else self.noise_ar_g)
-            tidx = ops.step_begin(self.gbuf, self.arena.begin(zero=False), src, base, noise=noise, rng=self.rng_words)
-            fused = self.fused_tails
-            chain = fused and engine.chain_ok(dims)                # dPre chain: no backward kernel re-reads its layer's output
-            need_guide = phase == 1 or not fused                   # (the fused form skips the classifier in the random-mask phase, as step.py does)
-            gen = engine.gen_all(p, tidx, dims, guide=need_guide, defer=DEFER_GEN)
-            red = engine.Reductions()
-            prob, sv_g = engine.guide_fwd(p, src, tidx, dims, base, gen=gen["guide"], lowrank_in=chain) if need_guide else (None, None)
-            mask = self._mask(phase, prob, sv_g[4] if sv_g is not None else None, jobs=gen.pop("pending", None))
-            self.last_mask = mask
-            if fused:
-                dec_head = None
-                if engine.chain_fwd_ok(dims):                      # the decoder's first hyperTem layer rides on the encoder's last chain launch
-                    emb, c1, tidx, sv_e, dec_head = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC],
-                                                                     tidx=tidx, dec_gen=gen[engine.DEC], lowrank_in=chain)
-                else:
-                    emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                           lowrank_in=chain)
-                _, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC], head=False, dec_head=dec_head)
-                sws = self.arena.zeros(ops.tail_parts(M), 4)       # per-workgroup loss statistics of the two heads
-                out, dd = engine.loss_tail(p, g, dec, src, mask, base, self.std, self.mean, a.mape_thresh, sws, red, chain=chain)
-                engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, None, None, dims, base, mdl.scaler_zeros, red, dd=dd, chain=chain)
-                if phase == 1:
-                    dh2 = engine.kl_head(p, g, sv_g, prob, c1, self.Nl, 0.1, sws, red, chain=chain)
-                    engine.guide_bwd(p, g, src, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain)
-                ops.stats_fold(sws, self.stats)                    # ordered sum -> stats[0..2], inside the buffer the all-reduce below moves
-            else:
-                emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx)
-                out, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC])
-                ops.mae_fwd(out, src, base + 2, mask, self.std, self.mean, a.mape_thresh, M, base, self.stats)
-                d_out = ops.mae_bwd(out, src, base + 2, mask, self.std, self.mean, a.mape_thresh, M, base, self.stats, normalize=False)
-                engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, d_out, None, dims, base, mdl.scaler_zeros, red)
-                if phase == 1:
-                    dlogit = ops.kl(prob, c1, self.Nl, 0.1, self.stats)
-                    engine.guide_bwd(p, g, src, tidx, sv_g, dlogit, dims, base, red)
-                # (a zero row: only the fold's other job) stats[5] <- this rank's hand-off expiries, so that the all-reduce below carries them
-                # and every rank skips the update and re-runs the step together, as on the fused path
-                ops.stats_fold(self.arena.zeros(1, 4), self.stats)
-            red.flush(tidx)
-        finally:
-            ctx.ARENA = ctx.NODE_REDUCE = None
+    def _after_backward(self, phase):
         # ---- gradients: replicated-compute parameters count once, node-local ones stay local, the rest is summed ----
         W = self.group.world
         if W > 1:
@@ -469,7 +409,7 @@ class ShardedPretrainStep(PretrainStep):
 
     def evaluate(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None):
         """Forward only (the end-of-training report of a node-sharded run): guide, global mask, encoder, decoder with its head — the first half of
-        _sbody_impl in the form GPTST_Model.forward takes.  No backward, no optimiser step, no counter moves.  source: this rank's (B',T,Nl,base+2)
+        the step's body in the form GPTST_Model.forward takes.  No backward, no optimiser step, no counter moves.  source: this rank's (B',T,Nl,base+2)
         slice, any batch size.  Injected noise covers the GLOBAL cells; what is not injected is drawn from generators this evaluator owns, seeded
         from the run's seed and identical on every rank (not the process-wide ones: ranks emulated by threads share those).
         -> (out (B',T,Nl,base), visibility mask (B',T,Nl,base) fp32, 1 = visible) of this rank's cells."""
@@ -507,8 +447,7 @@ class ShardedPretrainStep(PretrainStep):
                     nums = torch.tensor(mdl.adaptive_counts(Mg, epoch), dtype=torch.int32, device=self.dev)
                     mask_g = ops.mask_adaptive(label_g, None, lc, nums, na, nr, a.ada_type == "all", base)[2]
                 mask = self._cols(mask_g, base, B)
-                emb, _, tidx, _ = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx)
-                out, _, _ = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC])
+                out = engine.autoencoder_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen, tidx=tidx, join=False).out
         finally:
             ctx.NODE_REDUCE = None
         return out.view(B, T, self.Nl, base), mask.view(B, T, self.Nl, base)

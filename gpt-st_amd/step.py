@@ -5,6 +5,7 @@ adaptive-mask + KL phase).  Nothing in the step synchronises with the host: loss
 statistics block whenever the caller asks.  Data-parallel: one process per GPU, one RCCL all-reduce (sum) of
 [flat gradient | loss statistics] between backward and the optimiser (dist.py).
 """
+import contextlib
 import math
 import os
 import random
@@ -22,6 +23,7 @@ U24 = os.environ.get("GPTST_MASK_U24", "1") == "1"
 
 class PretrainStep:
     RING = 8                                  # pinned host slots in flight (see __init__)
+    DETERMINISTIC_MODE = True                 # the stepper sets the library's launch mode from self.deterministic (False: never touches it)
 
     def __init__(self, model, args, scaler_mean, scaler_std, batch_size, use_graph=True, dp=None, seed=0, global_mask=True,
                  deterministic=None):
@@ -37,7 +39,7 @@ class PretrainStep:
         self.use_graph, self.dp = use_graph, dp
         # bit-reproducible steps (GPTST_DETERMINISTIC=1): single-owner, fixed-order variants of the two reductions that end in float
         # atomics by default (ops.set_deterministic); with injected mask noise two runs of a step sequence are then bit-identical
-        self.deterministic = (os.environ.get("GPTST_DETERMINISTIC", "0") == "1") if deterministic is None else bool(deterministic)
+        self.deterministic = self.DETERMINISTIC_MODE and ((os.environ.get("GPTST_DETERMINISTIC", "0") == "1") if deterministic is None else bool(deterministic))
         n = model.flat.numel()
         self.gbuf = torch.zeros(n + 8, device=self.dev)             # [flat gradient | stats] -> one collective
         self.gflat, self.stats = self.gbuf[:n], self.gbuf[n:]
@@ -69,8 +71,15 @@ class PretrainStep:
         self.lr = args.lr_init
         self.rng = random.Random(seed)
         self.graphs = {}
+        self._g_graphs = {}                  # step_group(): phase -> graph of K steps
+        self._g_fallback = None              # step_group() fell back to single steps: their statistics snapshots (losses_group())
+        self._graph_comm_failed = False      # capturing the collectives failed once: they run between graph replays
+        self._ctx_keep = []                  # part 1's tensors of every two-graph capture (inputs of its second graph)
+        self._sws = None                     # fused loss statistics awaiting the optimiser's launch (_fold_stats)
         self.inject_noise = False
         self.global_count_scale = False      # set by subclasses that all-reduce [gradient | statistics] themselves (shard.py)
+        self.node_reduce = None              # node shards: completes a sum over nodes across the ranks (engine.CTX.NODE_REDUCE while a step is enqueued)
+        self.join_enc_dec = True             # the decoder's first hyperTem layer rides on the encoder's last chain launch (engine.autoencoder_fwd(join=))
         # r05, lost in-launch hand-offs (a bounded wait of the pair / role launches expired: the GPU was time-sliced away from the producer for
         # seconds): the optimiser skips the update of such a step (gptst_clip_adam's guard; stats_out[5] > 0), losses() / losses_group() notice,
         # switch this stepper to the launches WITHOUT hand-offs (safe_mode: graphs re-captured) and re-run the skipped steps from the untouched weights
@@ -146,20 +155,17 @@ class PretrainStep:
     def _dp_in_graph(self):
         """Data parallel on a capturable communicator (dist.DataParallel(native=True)): label gather, gradient all-reduce and optimiser are
         enqueued as part of the step body — one hipGraph per phase holds everything, as in the single-GPU case."""
-        return self.dp is not None and getattr(self.dp, "capturable", False) and not getattr(self, "_graph_comm_failed", False)
+        return self.dp is not None and getattr(self.dp, "capturable", False) and not self._graph_comm_failed
 
     def _part1(self, phase):
         p, dims, base = self.model.param_views(), self.dims, self.base
-        engine.CTX.ARENA = self.arena
+        engine.CTX.ARENA, engine.CTX.NODE_REDUCE = self.arena, self.node_reduce
         src = self.src
         # zero_grad + the step's zero scratch + the time index of node 0: one launch
-        noise = None                                              # the step's mask noise is drawn by the same launch (unless injected / forced)
-        if not self.inject_noise and not self.force_mask:
-            noise = (self.noise_g if phase == 0 else self.noise_ar_g) if self.gmask else (self.noise if phase == 0 else self.noise_ar)
+        # (the step's mask noise is drawn by the same launch, unless injected / forced)
+        noise = None if self.inject_noise or self.force_mask else self._noise_buffer(phase)
         tidx = ops.step_begin(self.gbuf, self.arena.begin(zero=False), src, base, noise=noise, rng=self.rng_words)
-        # the guide classifier (GPTST.py:325-332) feeds the adaptive mask and the KL term only: the random-mask phase of the FUSED step neither
-        # generates its parameters nor runs it (the reference computes and discards the logits there; GPTST_Model.forward still returns them)
-        need_guide = phase == 1 or self.always_guide
+        need_guide = self._need_guide(phase)
         # time embeddings + every generated parameter: 3 launches; r05: the STHCNs' forward jobs wait for the mask's launch (_part2_impl)
         gen = engine.gen_all(p, tidx, dims, guide=need_guide, defer=DEFER_GEN)
         red = engine.Reductions()
@@ -183,65 +189,66 @@ class PretrainStep:
     def _part2_impl(self, phase, ctx):
         mdl, p, g, dims, base = self.model, self.model.param_views(), self.g, self.dims, self.base
         a = self.args
-        M = self.B * self.T * self.N
         src, tidx, gen, red, prob, sv_g = self.src, ctx["tidx"], ctx["gen"], ctx["red"], ctx["prob"], ctx["sv_g"]
-        engine.CTX.ARENA = self.arena
+        engine.CTX.ARENA, engine.CTX.NODE_REDUCE = self.arena, self.node_reduce
         pend = gen.pop("pending", None)        # the STHCNs' generated-parameter jobs: inside the mask's launch where that is the cooperative one
-        if self.gmask:
-            mask = self._global_mask(phase, jobs=pend)
-        else:
-            if self.force_mask:
-                mask = self.mask_buf
-            elif phase == 0:
-                mask = ops.mask_random(self.noise, int(M * base * a.mask_ratio), ws=self._mask_ws(), u24=U24, jobs=pend)       # Philox / torch.rand noise: k * 2^-24
-            else:
-                label, counts = ops.labels_and_counts(prob, sv_g[4])
-                mask = ops.mask_adaptive(label, counts, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a, self.noise_r,
-                                         a.ada_type == "all", base, ws=self._mask_ws(), u24=U24, jobs=pend)[2]
+        mask = self._make_mask(phase, prob, sv_g[4] if sv_g is not None else None, pend)
         if pend is not None:
             pend.launch()                      # (forced mask: nothing carried them; a no-op after a mask call)
         self.last_mask = mask
-        dec_head = None
-        lowrank = self.fused_tails and engine.chain_ok(dims)      # the backward below is the dPre chain: the low-rank first layer may run
+        fused = self.fused_tails
         kl, sws = None, None
         if phase == 1 and self._carry_kl(sv_g):   # the KL path's backward rides on the forward's chain launches (engine.KlCarry)
-            sws = self.arena.zeros(ops.tail_parts(M), 4)
+            sws = self._tail_sws()
             kl = engine.KlCarry(p, sv_g, prob, src, dims, 0.1, sws)
-        if engine.chain_fwd_ok(dims):          # the decoder's first hyperTem layer rides on the encoder's last chain launch
-            emb, c1, tidx, sv_e, dec_head = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                             dec_gen=gen[engine.DEC], lowrank_in=lowrank, kl=kl)
-        else:
-            emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen[engine.ENC], tidx=tidx,
-                                                   lowrank_in=lowrank)
-        if self.fused_tails:
-            # output head + masked MAE + their backward: one pass over dec (the mean's 1/#kept is applied by the optimiser)
-            _, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC], head=False, dec_head=dec_head, kl=kl)
-            if sws is None:
-                sws = self.arena.zeros(ops.tail_parts(M), 4)                   # per-workgroup loss statistics of the two heads
-            chain = engine.chain_ok(dims)                                      # dPre chain: no backward kernel re-reads its layer's output
-            done = kl.carried if kl is not None else (lambda st: None)         # outputs of the stages the chain launches carried
-
-            def kl_path():
-                dh2 = engine.kl_head(p, g, sv_g, prob, c1, self.N, 0.1, sws, red, chain=chain, carried=done(1))
-                engine.guide_bwd(p, g, src, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=(done(2), done(3)))
-            out, dd = engine.loss_tail(p, g, dec, src, mask, base, self.std, self.mean, a.mape_thresh, sws, red, chain=chain)
-            engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, None, None, dims, base, mdl.scaler_zeros, red, dd=dd, chain=chain)
-            if phase == 1:
-                kl_path()
-            if self.dp is None and not self.global_count_scale:
-                self._sws = sws                                                # folded by the optimiser's first launch (one launch less)
-            else:
-                ops.stats_fold(sws, self.stats)                                # ordered sum -> stats[0..2]: the all-reduce must see them
-        else:
-            out, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, mdl.num_route, gen=gen[engine.DEC], dec_head=dec_head)
-            ops.mae_fwd(out, src, base + 2, mask, self.std, self.mean, a.mape_thresh, M, base, self.stats)
-            d_out = ops.mae_bwd(out, src, base + 2, mask, self.std, self.mean, a.mape_thresh, M, base, self.stats, normalize=False)
-            engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, d_out, None, dims, base, mdl.scaler_zeros, red)
-            if phase == 1:
-                dlogit = ops.kl(prob, c1, self.N, 0.1, self.stats)
-                engine.guide_bwd(p, g, src, tidx, sv_g, dlogit, dims, base, red)
+        # lowrank_in: the fused backward is the dPre chain, so the low-rank first layer may run; head: the fused loss tail goes through it itself
+        fw = engine.autoencoder_fwd(p, src, mask, dims, base, mdl.num_route, mdl.scaler_zeros, gen=gen, tidx=tidx,
+                                    lowrank_in=fused and engine.chain_ok(dims), kl=kl, head=not fused, join=self.join_enc_dec)
+        if fused and sws is None:
+            sws = self._tail_sws()
+        engine.step_bwd(p, g, src, mask, tidx, fw, prob, sv_g, dims, base, mdl.scaler_zeros, red, (self.std, self.mean, a.mape_thresh),
+                        self.stats, sws=sws, with_kl=phase == 1, kl=kl)
+        self._fold_stats(sws)
         red.flush(tidx)                                           # all parameter-gradient reductions: 3 launches
-        engine.CTX.ARENA = None
+        engine.CTX.ARENA = engine.CTX.NODE_REDUCE = None
+        self._after_backward(phase)
+
+    # ---- what a subclass with another partition of the work replaces (shard.py) ----------------------------------------
+    def _noise_buffer(self, phase):
+        """Hook: the buffer step_begin fills with the step's mask noise"""
+        if self.gmask:
+            return self.noise_g if phase == 0 else self.noise_ar_g
+        return self.noise if phase == 0 else self.noise_ar
+
+    def _need_guide(self, phase):
+        """Hook.  The guide classifier (GPTST.py:325-332) feeds the adaptive mask and the KL term only: the random-mask phase neither generates
+        its parameters nor runs it (the reference computes and discards the logits there; GPTST_Model.forward still returns them)"""
+        return phase == 1 or self.always_guide
+
+    def _make_mask(self, phase, prob, label, pend):
+        """Hook: the visibility mask of this rank's cells.  label: the guide's argmax labels (rowdot's by-product, None without the guide);
+        pend: the deferred generation jobs, which the mask's launch carries"""
+        a, base, M = self.args, self.base, self.B * self.T * self.N
+        if self.gmask:
+            return self._global_mask(phase, jobs=pend)
+        if self.force_mask:
+            return self.mask_buf
+        if phase == 0:
+            return ops.mask_random(self.noise, int(M * base * a.mask_ratio), ws=self._mask_ws(), u24=U24, jobs=pend)       # Philox / torch.rand noise: k * 2^-24
+        return ops.mask_adaptive(label, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a, self.noise_r,       # (class histogram: taken inside)
+                                 a.ada_type == "all", base, ws=self._mask_ws(), u24=U24, jobs=pend)[2]
+
+    def _fold_stats(self, sws):
+        """Hook: the fused heads' per-workgroup loss statistics -> stats[0..2] (sws None: the unfused loss kernels summed into stats themselves)"""
+        if sws is None:
+            return
+        if self.dp is None:
+            self._sws = sws                                                # folded by the optimiser's first launch (one launch less)
+        else:
+            ops.stats_fold(sws, self.stats)                                # ordered sum: the all-reduce must see them
+
+    def _after_backward(self, phase):
+        """Hook: from the finished gradient to the optimiser"""
         if self.dp is None:
             self._optim()
         elif self._dp_in_graph():           # gradient all-reduce + optimiser as the last nodes of the step's graph (no host gap behind the replay)
@@ -251,6 +258,10 @@ class PretrainStep:
             else:
                 self._allreduce(self.gbuf)
             self._optim()
+
+    def _tail_sws(self):
+        """per-workgroup loss statistics of the two fused heads, zeroed by the step's first launch"""
+        return self.arena.zeros(ops.tail_parts(self.B * self.T * self.N), 4)
 
     def _carry_kl(self, sv_g):
         """the KL path as guests of the forward's chain launches (engine.KlCarry): the plain fused stepper only — not under data parallelism, node
@@ -281,20 +292,32 @@ class PretrainStep:
         self.dp.gather_labels(self.label_l, out=self.label_g)
 
     def _optim(self):
-        sws, self._sws = getattr(self, "_sws", None), None
+        sws, self._sws = self._sws, None
         ops.clip_adam(self.model.flat, self.gflat, self.m, self.v, self.model.nA, self.model.nB, self.hyper, self.stats,
                       stats_out=self.stats_out, sws=sws)
 
-    def _body(self, phase):
-        """eager: part 1 [-> label exchange] -> part 2 (+ optimiser when there is no gradient all-reduce in between)"""
-        ops.set_deterministic(self.deterministic)           # thread-local launch mode of the library (captured into the graph)
+    @contextlib.contextmanager
+    def _launch_mode(self):
+        """while a step is enqueued or captured: the library's thread-local launch mode (captured into the graph)"""
+        if self.DETERMINISTIC_MODE:
+            ops.set_deterministic(self.deterministic)
         try:
-            ctx = self._part1(phase)
-            if self._needs_exchange(phase):
-                self._exchange_labels()
-            self._part2(phase, ctx)
+            yield
         finally:
-            ops.set_deterministic(False)
+            if self.DETERMINISTIC_MODE:
+                ops.set_deterministic(False)
+            engine.CTX.ARENA = engine.CTX.NODE_REDUCE = None
+
+    def _enqueue(self, phase):
+        """part 1 [-> label exchange] -> part 2 (+ optimiser when there is no gradient all-reduce in between)"""
+        ctx = self._part1(phase)
+        if self._needs_exchange(phase):
+            self._exchange_labels()
+        self._part2(phase, ctx)
+
+    def _body(self, phase):
+        with self._launch_mode():
+            self._enqueue(phase)
 
     # ---- host side of one step -------------------------------------------------------------------------------------
     def _views(self, hc):
@@ -402,7 +425,7 @@ class PretrainStep:
                   % (type(e).__name__, str(e).splitlines()[0][:200]), file=sys.stderr)
             self._graph_comm_failed = True
             self.graphs.clear()                         # graphs captured earlier hold the in-graph all-reduce + optimiser: replaying them next to
-            getattr(self, "_g_graphs", {}).clear()      # the eager collectives would reduce and step twice
+            self._g_graphs.clear()                      # the eager collectives would reduce and step twice
             torch.cuda.synchronize()
             return self._capture_impl(key)
 
@@ -410,33 +433,22 @@ class PretrainStep:
         phase, inject, forced = key
         self.inject_noise, self.force_mask = inject, forced
         keep = (self.model.flat.clone(), self.m.clone(), self.v.clone())
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                      # warm-up on a side stream (allocator, lazy kernel attributes)
-            for _ in range(2):
-                self._body(phase)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        ops.set_deterministic(self.deterministic)
+        engine.warm_up(lambda: self._body(phase))
         try:
-            g1 = torch.cuda.CUDAGraph()
-            if self._needs_exchange(phase) and not self._dp_in_graph():
-                with torch.cuda.graph(g1, capture_error_mode="thread_local"):      # other threads (RCCL watchdog) may call the runtime meanwhile
-                    ctx = self._part1(phase)
-                g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
-                    self._part2(phase, ctx)
-                self._ctx_keep = getattr(self, "_ctx_keep", []) + [ctx]            # part 1's tensors are inputs of graph 2
-            else:
-                g2 = None
-                with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                    ctx = self._part1(phase)
-                    if self._needs_exchange(phase):                                # capturable communicator: the label gather is a graph node
-                        self._exchange_labels()
-                    self._part2(phase, ctx)
+            with self._launch_mode():
+                g1 = torch.cuda.CUDAGraph()
+                if self._needs_exchange(phase) and not self._dp_in_graph():
+                    with torch.cuda.graph(g1, capture_error_mode="thread_local"):      # other threads (RCCL watchdog) may call the runtime meanwhile
+                        ctx = self._part1(phase)
+                    g2 = torch.cuda.CUDAGraph()
+                    with torch.cuda.graph(g2, pool=g1.pool(), capture_error_mode="thread_local"):
+                        self._part2(phase, ctx)
+                    self._ctx_keep.append(ctx)                                         # part 1's tensors are inputs of graph 2
+                else:
+                    g2 = None
+                    with torch.cuda.graph(g1, capture_error_mode="thread_local"):      # (capturable communicator: the label gather is a graph node)
+                        self._enqueue(phase)
         finally:
-            ops.set_deterministic(False)
-            engine.CTX.ARENA = None
             self.model.flat.copy_(keep[0]); self.m.copy_(keep[1]); self.v.copy_(keep[2])   # undo the warm-up updates (also when the capture failed)
             torch.cuda.synchronize()
         self.graphs[key] = (g1, g2)
@@ -547,17 +559,10 @@ class PretrainStep:
         torch.cuda.synchronize()
         self.tA, self.tB, self.phase_kl = st[:3]
         self.rng.setstate(st[3])
-        s = torch.cuda.Stream()
-        s.wait_stream(torch.cuda.current_stream())
-        torch.cuda.synchronize()
         base = torch.cuda.memory_allocated()
         torch.cuda.reset_peak_memory_stats()
-        with torch.cuda.stream(s):                      # warm-up on a side stream (allocator, lazy kernel attributes)
-            for j in range(min(K, 2)):
-                self._sub(j)
-                self._body(phase)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
+        subs = iter(range(K))
+        engine.warm_up(lambda: (self._sub(next(subs)), self._body(phase)))      # sub-steps 0 and 1 (a group has K >= 2)
         # Activations of the K sub-steps are NOT shared inside one capture (the graph-private pool grew K-fold at N = 4096, C = 128:
         # 4 x 56 GB): groups are for the shapes where the idle time between replays matters, i.e. small steps
         # (decided from the device's TOTAL memory, not from what happens to be free: every rank of a data-parallel job must take the same
@@ -573,19 +578,14 @@ class PretrainStep:
             self.model.flat.copy_(keep[0]); self.m.copy_(keep[1]); self.v.copy_(keep[2])
             torch.cuda.synchronize()
             raise RuntimeError("a group of %d steps would need ~%.0f GB of activations (device: %.0f GB)" % (K, per_step * K / 2**30, total / 2**30))
-        ops.set_deterministic(self.deterministic)
         try:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                for j in range(K):
-                    self._sub(j)
-                    ctx = self._part1(phase)
-                    if self._needs_exchange(phase):
-                        self._exchange_labels()
-                    self._part2(phase, ctx)
+            with self._launch_mode():
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                    for j in range(K):
+                        self._sub(j)
+                        self._enqueue(phase)
         finally:
-            ops.set_deterministic(False)
-            engine.CTX.ARENA = None
             self.model.flat.copy_(keep[0]); self.m.copy_(keep[1]); self.v.copy_(keep[2])   # undo the warm-up updates
             torch.cuda.synchronize()
         self._g_graphs[phase] = g
@@ -593,7 +593,7 @@ class PretrainStep:
     def losses_group(self):
         """[(loss, loss_flow, loss_s)] of the steps of the last step_group() — synchronises."""
         if self._g_last is None:
-            if getattr(self, "_g_fallback", None):      # step_group() fell back to single steps: one triple per step, as the grouped path
+            if self._g_fallback:                        # step_group() fell back to single steps: one triple per step, as the grouped path
                 snaps, self._g_fallback = self._g_fallback, None
                 rows = [(st.cpu(), kl) for st, kl, _, _, _ in snaps]
                 out = [self._stats_row(st, kl) for st, kl in rows]
@@ -655,7 +655,7 @@ class PretrainStep:
         self.lost_steps += nsteps
         self.safe_mode = True
         self.graphs.clear()
-        getattr(self, "_g_graphs", {}).clear()
+        self._g_graphs.clear()
         _C.lib().call("gptst_handoff_reset")
 
     # ---- results ---------------------------------------------------------------------------------------------------

@@ -51,8 +51,10 @@ plain, lost = res
 shared = torch.cat([v.reshape(-1) for k, v in m.state_dict().items() if not is_node_local(k)])
 both = group.all_gather(shared)
 shared_diff = float((both[0] - both[1]).abs().max())
-print(json.dumps({"rank": rank, "lost_steps": [plain["lost"], lost["lost"]], "safe_mode": [plain["safe"], lost["safe"]],
+# (one write per rank: both ranks share the parent's pipe, and print() writes the text and the newline separately — two records landed on one line)
+sys.stdout.write(json.dumps({"rank": rank, "lost_steps": [plain["lost"], lost["lost"]], "safe_mode": [plain["safe"], lost["safe"]],
                   "counters": [plain["t"], lost["t"]], "losses": [plain["losses"], lost["losses"]],
-                  "param_rel": float((plain["flat"] - lost["flat"]).norm() / plain["flat"].norm()), "shared_diff": shared_diff}), flush=True)
+                  "param_rel": float((plain["flat"] - lost["flat"]).norm() / plain["flat"].norm()), "shared_diff": shared_diff}) + "\n")
+sys.stdout.flush()
 dist.barrier()
 dist.destroy_process_group()

@@ -22,12 +22,12 @@ def chain(src, gen, tidx, dims, keep):
     M = dims[0] * T * N
     mask = (torch.rand(M * base, device=dev) > 0.25).float()
     red = engine.Reductions()
-    emb, c1, tidx, sv_e = engine.model_fwd(p, src, mask, dims, base, model.num_route, model.scaler_zeros, gen=gen[engine.ENC], tidx=tidx)
-    _, dec, sv_d = engine.decoder_fwd(p, tidx, emb, dims, model.num_route, gen=gen[engine.DEC], head=False)
+    fw = engine.autoencoder_fwd(p, src, mask, dims, base, model.num_route, model.scaler_zeros, gen=gen, tidx=tidx, head=False, join=False)
+    dec, sv_e, sv_d = fw.dec, fw.sv_e, fw.sv_d
     sws = torch.zeros(ops.tail_parts(M), 4, device=dev)
     out, dd = engine.loss_tail(p, g, dec, src, mask, base, synth.SCALER_STD, synth.SCALER_MEAN, args.mape_thresh, sws, red)
     engine.model_bwd(p, g, src, mask, tidx, sv_e, sv_d, dec, None, None, dims, base, model.scaler_zeros, red, dd=dd)
-    keep.append((red, sv_e, sv_d, out, dd, mask, sws, emb, dec))
+    keep.append((red, fw, out, dd, mask, sws))
 
 
 def run(K, B, steps=200):
