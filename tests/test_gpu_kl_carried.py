@@ -5,7 +5,7 @@ import torch
 
 from gptst_amd import synth
 from gptst_amd.config import make_args
-from oracle import gptst_oracle as O
+from step_grad_util import noise_inject, one_step
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -20,36 +20,16 @@ def _args(dataset, **over):
 
 
 def _step(args, B, carry, epoch, deterministic=False, record=False):
-    """one fused step from the seed-3 state with injected noise -> (gradient views, losses, mask, launch names, stepper)"""
-    from gptst_amd import engine, ops
-    from gptst_amd.model import GPTST_Model
-    from gptst_amd.step import PretrainStep
-    sd = O.init_state_dict(args, 3)
-    model = GPTST_Model(args); model.load_state_dict(sd); model = model.to(DEV)
-    st = PretrainStep(model, args, synth.SCALER_MEAN, synth.SCALER_STD, batch_size=B, use_graph=False, deterministic=deterministic)
-    N = args.num_nodes
-    M = B * 12 * N
-    src = synth.make_batch(B, 12, N, 1, seed=11).to(DEV)
+    """one fused step from the seed-3 state with injected noise (step_grad_util.one_step), the carried form switched by `carry`
+    -> (gradient views, losses, mask, launch names, stepper)"""
+    from gptst_amd import engine
     keep = engine.CARRY_KL
     engine.CARRY_KL = carry
     try:
-        for _ in range(2):                           # the first step sizes the zero arena; the second is the one compared
-            ops.TIMER = [] if record else None
-            if epoch <= args.change_epoch:
-                st.step(src, epoch, noise=synth.make_noise(M, 21).to(DEV))
-            else:
-                st.step(src, epoch, noise_a=synth.make_noise(M, 22).to(DEV), noise_r=synth.make_noise(M, 23).to(DEV),
-                        list_c=synth.class_order(args.HS, 4))
-            names = [r[0] for r in ops.TIMER] if record else None
-            ops.TIMER = None
-            model.load_state_dict(sd)                # (the second step starts from the same weights)
-            st.m.zero_(); st.v.zero_()
-        torch.cuda.synchronize()
+        grads, _, mask, names, st = one_step(args, B, epoch, deterministic=deterministic, sd_seed=3, inject=noise_inject(args, B, epoch))
     finally:
         engine.CARRY_KL = keep
-        ops.TIMER = None
-    grads = {k: v.detach().clone() for k, v in st.g.items()}
-    return grads, st.losses(), st.last_mask.clone(), names, st
+    return grads, st.losses(), mask, names if record else None, st
 
 
 SHAPES = [("PEMS08", 32, {}), ("METR_LA", 8, {}), ("PEMS08", 2, dict(num_nodes=24, embed_dim=8, HS=6, HT=8))]
