@@ -77,6 +77,7 @@ __global__ __launch_bounds__(256) void kl_kernel(const float* __restrict__ prob,
 // hyper (device float[16]), refreshed by the host before every step:
 //  [0] step_size_A = lr/(1-b1^tA)  [1] bc2sqrt_A = sqrt(1-b2^tA)  [2] step_size_B  [3] bc2sqrt_B  [4] beta1  [5] beta2  [6] eps
 //  [7] max_norm (<=0: no clipping)  [8] active_B (0/1)  [9] gscale_A mode: 0 -> 1, 1 -> 1/max(stats[1],1)   [10] gscale_B
+//  [11] 1 - beta1, [12] 1 - beta2 as the host rounds them (0: computed here)   [13] != 0: stats[3] holds the TOTAL squared norm (adam_kernel)
 // segment A = parameters on the reconstruction-loss path, B = MLP_RL / teb4mask / neb4mask (KL path; no gradient - hence no
 // Adam state, as in torch - until epoch > change_epoch);  parameters after nA+nB never receive gradients.
 __device__ __forceinline__ float seg_scale(const float* hyper, const float* stats, bool segA) {
@@ -142,8 +143,9 @@ GPTST_INTERNAL int gptst_adam_skipped_clear(void) {
     return hipMemcpyToSymbol(HIP_SYMBOL(g_adam_skipped), &z, sizeof(unsigned)) == hipSuccess ? 0 : 1;
 }
 
-// stats[3] on entry: squared-norm contributions that are not in g on this rank (node-sharded runs add the other ranks' node-local
-// parts there; otherwise 0); on exit (written by workgroup 0): the total squared gradient norm.
+// stats[3] on entry, hyper[13] == 0: squared-norm contributions that are not in g (normally 0), added to this launch's own sum over g;
+// hyper[13] != 0: the TOTAL squared gradient norm, taken as given and the sum over g ignored (node-sharded runs, shard.py: every rank forms
+// the same total).  The norm the step clipped by goes out in stats[4] (written by workgroup 0).
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                                    float* __restrict__ v, long nA, long nB, const float* __restrict__ hyper,
                                                    float* __restrict__ stats, const float* __restrict__ ws, int nws, float* __restrict__ stats_out,
@@ -163,7 +165,10 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         __syncthreads();
     }
     const float ua = seg_scale(hyper, stats, true), ub = seg_scale(hyper, stats, false);
-    const float gsq = stats[3] + (ua * ua * ((red[0] + red[1]) + (red[2] + red[3])) + ub * ub * ((redB[0] + redB[1]) + (redB[2] + redB[3])));
+    // hyper[13] != 0: stats[3] IS the total (node shards: every rank gets the same words, summed in the same order, so that the clip scale — and with
+    // it every shared weight — is bit-identical on the ranks; a rank's own sum over g has its node-local part mixed in and rounds differently)
+    const float gsq = hyper[13] != 0.f ? stats[3]
+                    : stats[3] + (ua * ua * ((red[0] + red[1]) + (red[2] + red[3])) + ub * ub * ((redB[0] + redB[1]) + (redB[2] + redB[3])));
     const bool actB = hyper[8] != 0.f;
     const long n = nA + (actB ? nB : 0);
     const float b1 = hyper[4], b2 = hyper[5], eps = hyper[6], maxn = hyper[7];
@@ -237,8 +242,9 @@ extern "C" int gptst_kl(const float* prob, const float* c, int rows, int N, int 
 
 extern "C" int gptst_clip_adam_ws_floats(void) { return 2 * GN_NB; }
 
-// ws: gptst_clip_adam_ws_floats() floats of scratch.  stats[3]: extra squared-norm terms (0 unless node-sharded), stats[4] <- the
-// total squared gradient norm (after scaling, before clipping).  No atomics: the norm is folded in a fixed order.
+// ws: gptst_clip_adam_ws_floats() floats of scratch.  stats[3]: extra squared-norm terms (normally 0), or with hyper[13] != 0 the total
+// squared norm itself (see adam_kernel); stats[4] <- the total squared gradient norm (after scaling, before clipping).  No atomics: the
+// norm is folded in a fixed order.
 // sws (may be NULL) / sws_rows: the step's per-workgroup loss statistics, folded into stats[0..2] (+=) by the first launch — replaces a
 // separate gptst_stats_fold when nothing (a gradient all-reduce) has to see the folded statistics in between.
 GPTST_INTERNAL const unsigned* gptst_handoff_word_capmfma(void);

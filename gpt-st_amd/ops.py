@@ -990,7 +990,8 @@ def step_begin(z0, z1, src, base, noise=None, rng=None):
 
 
 def clip_adam(p, g, m, v, nA, nB, hyper, stats, ws=None, stats_out=None, sws=None):
-    """clip_grad_norm_ + Adam over the flat buffers; stats[3] (in): extra squared-norm terms, stats[4] (out): total squared norm.
+    """clip_grad_norm_ + Adam over the flat buffers; stats[3] (in): extra squared-norm terms — with hyper[13] != 0 the total
+    squared norm itself, taken as given (node shards) —, stats[4] (out): total squared norm.
     ws: gptst_clip_adam_ws_floats() floats of scratch (default: one cached buffer per device — stream-ordered reuse).
     sws: the step's per-workgroup loss statistics (tail_sws): folded into stats[0..2] by the first launch instead of a separate stats_fold."""
     if ws is None:

@@ -7,8 +7,9 @@ cluster aggregations ``S = c . P`` of ``cap`` (R+2 = 4 per forward, 1 per backwa
 (ops._capbig_type1) followed by ONE all-reduce of (B*T, HS, C) floats.  The cross-time hyperedge block of ``cap`` runs replicated
 on the all-reduced ``s``, so the gradients it produces (``t_adj``, ``time_feature2``) are identical on every rank and are scaled
 by 1/world before the gradient all-reduce.  Gradients of shared parameters: one all-reduce of the flat buffer (node-local slices
-are put back afterwards — they belong to this rank alone); the global gradient norm adds the other ranks' node-local squared
-norms (one scalar all-reduce).  Masks: the selection runs replicated over the GLOBAL (B,T,N) cells from identical noise and each
+are zeroed before and put back afterwards — they belong to this rank alone); the global gradient norm is the reduced buffer's plus
+every rank's node-local squared norm (one scalar all-reduce), formed alike on every rank and handed to the optimiser as the total.
+Masks: the selection runs replicated over the GLOBAL (B,T,N) cells from identical noise and each
 rank keeps its node columns; the adaptive phase all-gathers the per-cell cluster labels and sums the class counts.
 Shards come from node_ranges() and may differ in width by one node: the label gather pads to the widest shard, and the models are built
 with node_capacity = that width (model.py), so that the flat gradient buffer has the same layout on every rank.
@@ -383,6 +384,10 @@ class ShardedPretrainStep(PretrainStep):
             self._capture(key)
         self.graphs[key][0].replay()
 
+    def _fill(self, sl, phase, epoch, list_c):
+        super()._fill(sl, phase, epoch, list_c)
+        sl["hyper"][13] = 1.0 if self.group.world > 1 else 0.0     # the optimiser clips by the norm _after_backward leaves in stats[3]
+
     def _after_backward(self, phase):
         # ---- gradients: replicated-compute parameters count once, node-local ones stay local, the rest is summed ----
         W = self.group.world
@@ -390,18 +395,28 @@ class ShardedPretrainStep(PretrainStep):
             if self.repl_grads:
                 torch._foreach_mul_(self.repl_grads, 1.0 / W)
             torch._foreach_copy_(self.keep_views, self.keep_grads)
+            torch._foreach_zero_(self.keep_grads)                  # (so that the reduced buffer is the shared gradient alone, the same bits on every rank)
         self.group.all_reduce_(self.gbuf)                          # [flat gradient | loss statistics]
         if W > 1:
+            # global gradient norm = shared part + every rank's node-local part (reconstruction-path gradients are still unnormalised sums: scaled by
+            # 1 / kept cells like the optimiser does).  Every rank adds the same words in the same order — the shared part from the reduced buffer
+            # while the node-local slots are still zero, the node-local parts through one scalar all-reduce — and hands the optimiser the TOTAL
+            # (hyper[13]): a rank that summed its own gradient buffer instead had its node-local part mixed in, rounded the total differently in
+            # the last bit, clipped by another scale and left the replicas one ulp apart after a single step (ragged shards, W = 3).
+            nA, nB = self.model.nA, self.model.nB
+            # (dot products: one pass over each segment, no temporaries — 3 launches in the random phase, 5 with the KL path)
+            sa2 = (1.0 / torch.clamp(self.stats[1], min=1.0)) ** 2
+            gA, kA = self.gflat[:nA], self.keep_flat[:self.keep_nA]
+            shared = (torch.dot(gA, gA) * sa2).view(1)
+            own = (torch.dot(kA, kA) * sa2).view(1)
+            if phase == 1:
+                gB, kB = self.gflat[nA:nA + nB], self.keep_flat[self.keep_nA:]
+                shared = shared + torch.dot(gB, gB)
+                if kB.numel():
+                    own = own + torch.dot(kB, kB)
+            self.group.all_reduce_(own)
+            self.stats[3] = (shared + own)[0]
             torch._foreach_copy_(self.keep_grads, self.keep_views)
-            # global gradient norm: the optimiser kernel sees the shared part + OWN node-local part; add the other ranks' local parts
-            # (reconstruction-path gradients are still unnormalised sums: scaled by 1 / kept cells like the optimiser does)
-            sa = 1.0 / torch.clamp(self.stats[1], min=1.0)
-            own = (self.keep_flat[:self.keep_nA] * sa).pow(2).sum().view(1)
-            if phase == 1 and self.keep_nA < self.keep_flat.numel():
-                own = own + self.keep_flat[self.keep_nA:].pow(2).sum()
-            tot = own.clone()
-            self.group.all_reduce_(tot)
-            self.stats[3] += (tot - own)[0]
         self._optim()
 
     def _budgets(self, ada, rnd, epoch):
