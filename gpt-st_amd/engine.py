@@ -82,7 +82,7 @@ class Reductions:
         self.late = ops.PoolJobs()   # reductions over dA, which gram_bwd writes in _run(): never carried by an earlier launch
         self.no_carry = False        # (deterministic steppers: one reduction launch, as the single-owner kind-2 launch groups by target)
         self.grams = []          # (A (L*N,Hm,T), dG (L*N,T,T), dA out)
-        self.tf = []             # (params, grads, dout, rows, K)
+        self.tf = []             # ops.TimefeatJob with grads and dout
         self.keep = []
         self.on_bucket = None    # callable(k): gradient bucket k is complete (k = 0: the decoder's) — called on the forked stream, right behind
         self.nbucket = 0         # the reductions that finish it, so a data-parallel step can enqueue that bucket's all-reduce under the rest of the backward
@@ -99,8 +99,8 @@ class Reductions:
             return None
         take, rest, nb = [], [], 0.0
         for j in self.jobs.jobs:
-            b = 4.0 * j[5] * j[7] * j[8] / 2 ** 20                # R * cols * nsplit floats
-            if j[0] in (ops.PoolJobs.BWD_POOL, ops.PoolJobs.BWD_EMB) and nb + b <= mb and len(take) < 100 and (j[7] | j[9]) % 4 == 0:     # (float4-shaped jobs only)
+            b = 4.0 * j.R * j.cols * j.nsplit / 2 ** 20
+            if j.kind in (ops.PoolJobs.BWD_POOL, ops.PoolJobs.BWD_EMB) and nb + b <= mb and len(take) < 100 and (j.cols | j.ldx) % 4 == 0:     # (float4-shaped jobs only)
                 take.append(j); nb += b
             else:
                 rest.append(j)
@@ -121,9 +121,7 @@ class Reductions:
         self.grams.append((A, dG, dA, N, nsG))
 
     def timefeat(self, p, g, pfx, tidx, dout, spg=False):
-        B, T = tidx.shape[0], tidx.shape[1]
-        rows, K = (B, T) if spg else (B * T, 1)
-        self.tf.append((_tf_tensors(p, pfx), _tf_tensors(g, pfx), dout, rows, K))
+        self.tf.append(_tf_job(p, pfx, tidx, spg)._replace(grads=_tf_tensors(g, pfx), dout=dout))
 
     def flush_async(self, tidx):
         """A gradient bucket is complete (a data-parallel step, GPTST_DP_OVERLAP=1; no-op otherwise): its reductions run HERE, on the calling
@@ -178,7 +176,7 @@ def _tf_tensors(d, pfx):
 def _tf_job(p, pfx, tidx, spg=False):
     B, T = tidx.shape[0], tidx.shape[1]
     rows, K = (B, T) if spg else (B * T, 1)
-    return (_tf_tensors(p, pfx), rows, K)
+    return ops.TimefeatJob(_tf_tensors(p, pfx), rows, K)
 
 
 # ---- hyperTem (GPTST.py:154-163) -----------------------------------------------------------------------------------
@@ -188,6 +186,23 @@ def _tf_job(p, pfx, tidx, spg=False):
 # bench shape (scratch/mb_ht5.py): forward 22.2 -> 18.8 us, backward 29.4 -> 37.9 us (the weight-gradient workgroups become the long pole: 565 KB
 # of L2 reads each) — a net loss of 5 us per layer although it removes 33 MB of HBM traffic, so R is kept.  GPTST_DROP_R=1 switches it on.
 DROP_R = os.environ.get("GPTST_DROP_R", "0") == "1"
+
+
+class HtSaved(NamedTuple):
+    """saved state of a hyperTem layer: input x, R = G (*) x (None: not kept), output, temporal graph, generated weights"""
+    x: Any
+    R: Any
+    out: Any
+    G: Any
+    Wbt: Any
+
+
+class WgradParts(NamedTuple):
+    """weight-gradient partials of a generated layer, what its reductions are queued from: dW (ns * groups, C*C) and db (ns * groups, C), possibly
+    column windows of [dW | db] rows; ns row splits"""
+    dW: Any
+    ns: int
+    db: Any
 
 
 def _ht_fused_bwd(dims):
@@ -205,7 +220,7 @@ def hypertem_core_fwd(x, G, Wbt, bbt, dims):
     else:
         R = ops.tmix(x.view(B, T, N, C), G).view(-1, C)                                 # :157-158
         out = ops.apply(R, Wbt, MODE_TIME, B * T, N, bias=bbt, resid=x, epi=EPI_RES_LRELU)  # :162-163
-    return out, (x, R, out, G, Wbt)
+    return out, HtSaved(x, R, out, G, Wbt)
 
 
 FUSE_HT_BWD = True         # hyperTem backward + its weight gradient in one launch (False: two launches)
@@ -227,48 +242,58 @@ def chain_ok(dims):
     return _ht_fused_bwd(dims) or (CHAIN128 and dims[3] == 128)
 
 
-def _wb_cols(dWb, C):
-    """rows [dW | db] of a weight-gradient launch -> the two column windows"""
-    return dWb[:, :C * C], dWb[:, C * C:]
+def _wb_parts(dWb, C, ns=1):
+    """rows [dW | db] of a weight-gradient launch with ns row splits -> WgradParts of the two column windows"""
+    return WgradParts(dWb[:, :C * C], ns, dWb[:, C * C:])
 
 
-def _wb_record(dWb, ns, C):
-    """-> (dW, split count, db): what the reductions of a generated layer are queued from"""
-    return dWb[:, :C * C], ns, dWb[:, C * C:]
+def _wgrad_parts(a, dout, out, mode, dims):
+    """the weight-gradient launch of a generated layer on the input a; it also emits the bias gradient (column sums of dPre per group): rows
+    [dW | db].  out None: dout already is dPre (chain); else dPre is made from the layer's output in the prologue."""
+    B, T, N, C = dims
+    dWb, ns = ops.wgrad(a, dout, mode, B * T, N, D2=out, pro=PRO_NONE if out is None else PRO_DPRE, colsum_d=True)
+    return _wb_parts(dWb, C, ns)
+
+
+def _genlin_bwd(dout, out, x, W, mode, dims, chain, premul=False):
+    """Backward of a generated linear layer LReLU(x W + b) -> dx, WgradParts.  C = 64: data, weight and bias gradient in one pass; C = 128: the
+    dPre chain (neither pass reads the layer's output) or the dPre prologue.  premul (chain only): dx is returned multiplied by lrelu'(x)."""
+    B, T, N, C = dims
+    BT = B * T
+    if C == 64:
+        dx, dW, db, ns = ops.apply_wgrad(dout, None if chain else out, x, W, mode, BT, N, premul=chain and premul)
+        return dx, WgradParts(dW, ns, db)
+    if chain:
+        dx = (ops.apply(dout, W, mode, BT, N, transw=True, resid2=x, epi=EPI_PREMUL) if premul
+              else ops.apply(dout, W, mode, BT, N, transw=True))
+        return dx, _wgrad_parts(x, dout, None, mode, dims)
+    dx = ops.apply(dout, W, mode, BT, N, A2=out, transw=True, pro=PRO_DPRE)
+    return dx, _wgrad_parts(x, dout, out, mode, dims)
 
 
 def hypertem_core_bwd(saved, dout, dG_out, dims, chain=False, premul=False):
-    """-> dx, (dWbt, nsplit, dbias partials); the graph-gradient partials are written into dG_out (nsG, N, T, T).
+    """-> dx, WgradParts (dWbt, nsplit, dbias partials); the graph-gradient partials are written into dG_out (nsG, N, T, T).
     chain: dout already is dPre (the layer's output is not read);  premul (chain only): dx is returned multiplied by lrelu'(x)."""
     B, T, N, C = dims
     x, R, out, G, Wbt = saved
     BT = B * T
+    v = lambda a: a.view(B, T, N, C)      # noqa: E731
     assert not chain or chain_ok(dims)
     if _ht_fused_bwd(dims):
         # data / graph gradients and the weight + bias gradient side by side in one launch: rows [dW_bt | db_bt]
-        dx, dWb, ns, _ = ops.hypertem_bwd_wgrad(dout.view(B, T, N, C), None if chain else out.view(B, T, N, C), x.view(B, T, N, C), G, Wbt,
-                                                R.view(B, T, N, C) if R is not None else None, dG=dG_out, premul=chain and premul)
-        dWbt, dbias = _wb_cols(dWb, C)
-        dx = dx.view(-1, C)
-    elif C == 64:
-        # the weight-gradient kernel also emits the bias gradient (column sums of dPre per (b,t)): rows [dW_bt | db_bt]
-        dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dWbt, dbias = _wb_cols(dWb, C)
-        dx, _, _ = ops.hypertem_bwd(dout.view(B, T, N, C), out.view(B, T, N, C), x.view(B, T, N, C), G, Wbt, dG=dG_out, want_dbias=False)
-        dx = dx.view(-1, C)
+        dx, dWb, ns, _ = ops.hypertem_bwd_wgrad(v(dout), None if chain else v(out), v(x), G, Wbt, v(R) if R is not None else None, dG=dG_out,
+                                                premul=chain and premul)
+        return dx.view(-1, C), _wb_parts(dWb, C, ns)
+    hp = _wgrad_parts(R, dout, None if chain else out, MODE_TIME, dims)
+    if C == 64:
+        dx, _, _ = ops.hypertem_bwd(v(dout), v(out), v(x), G, Wbt, dG=dG_out, want_dbias=False)
     elif chain:                                       # C = 128, dPre chain: no pass reads the layer's output
-        dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, colsum_d=True)
-        dWbt, dbias = _wb_cols(dWb, C)
         dR = ops.apply(dout, Wbt, MODE_TIME, BT, N, transw=True)
-        dx, _ = ops.tmix_bwd_chain(dR.view(B, T, N, C), x.view(B, T, N, C), G, dout.view(B, T, N, C), premul=premul, dG=dG_out[0])
-        dx = dx.view(-1, C)
+        dx, _ = ops.tmix_bwd_chain(v(dR), v(x), G, v(dout), premul=premul, dG=dG_out[0])
     else:
-        dWb, ns = ops.wgrad(R, dout, MODE_TIME, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dWbt, dbias = _wb_cols(dWb, C)
         dR = ops.apply(dout, Wbt, MODE_TIME, BT, N, A2=out, transw=True, pro=PRO_DPRE)
-        dx, _ = ops.tmix_bwd(dR.view(B, T, N, C), x.view(B, T, N, C), G, dout.view(B, T, N, C), out.view(B, T, N, C), dG=dG_out[0])
-        dx = dx.view(-1, C)
-    return dx, (dWbt, ns, dbias)
+        dx, _ = ops.tmix_bwd(v(dR), v(x), G, v(dout), v(out), dG=dG_out[0])
+    return dx.view(-1, C), hp
 
 
 CARRY_RED = os.environ.get("GPTST_CARRY_RED", "1") == "1"        # queued weight-gradient reductions as role workgroups of the routing backward (r05, late)
@@ -314,7 +339,7 @@ def _ht_pair_shape_ok(dims):
 
 
 def ht_pair_ok(saved1, saved0, dims):
-    return (pair_bwd_on() and dims[3] == 64 and not isinstance(saved1, EncIn) and saved1[1] is not None and saved0[1] is not None
+    return (pair_bwd_on() and dims[3] == 64 and not isinstance(saved1, EncIn) and saved1.R is not None and saved0.R is not None
             and _ht_fused_bwd(dims) and _ht_pair_shape_ok(dims))
 
 
@@ -333,15 +358,14 @@ def ht_pair_bwd(saved1, saved0, dout, dG1, dG0, dims, dWb1=None):
     if not ht_pair_ok(saved1, saved0, dims):
         assert dWb1 is None
         return None
-    x1, R1, _, G1, Wbt1 = saved1
-    x0, R0, _, G0, Wbt0 = saved0
+    s1, s0 = saved1, saved0
     v = lambda a: a.view(B, T, N, C)
-    r = ops.hypertem_bwd_pair(v(dout), v(x1), G1, Wbt1, v(R1), v(x0), G0, Wbt0, v(R0), dG1, dG0, _zeros(dout, B), dWb1=dWb1)
+    r = ops.hypertem_bwd_pair(v(dout), v(s1.x), s1.G, s1.Wbt, v(s1.R), v(s0.x), s0.G, s0.Wbt, v(s0.R), dG1, dG0, _zeros(dout, B), dWb1=dWb1)
     assert r is not None or dWb1 is None
     if r is None:
         return None
     dmid, dx0, dWb1, dWb0, ns = r
-    return dx0.view(-1, C), _wb_record(dWb1, ns, C), _wb_record(dWb0, ns, C)
+    return dx0.view(-1, C), _wb_parts(dWb1, C, ns), _wb_parts(dWb0, C, ns)
 
 
 # ---- cap (GPTST.py:100-141) ----------------------------------------------------------------------------------------
@@ -350,6 +374,29 @@ CAP_LIN = os.environ.get("GPTST_CAP_LIN", "1") == "1"           # ... and the en
 CROSS_ROLE = int(os.environ.get("GPTST_CROSS_ROLE", "1"))       # ... its backward as a ROLE of the routing backward's launch (r04; 0: replicated prologue —
                                                                 # what a stepper falls back to after a lost hand-off.  The rec backward as a THIRD role
                                                                 # measured 799 vs 814 steps/s, profiles/r04_roles3_stamps.txt, and left the library in r05)
+
+
+class CapSaved(NamedTuple):
+    """saved state of a cap: input, output, the node scatter's result rec, assignment c (BT,HS,N), cluster rows s, cross-time output v with its
+    Ht / Rt, the generated dyn and W_n, and the routing's Y (None: rebuilt in the backward)"""
+    x: Any
+    out: Any
+    rec: Any
+    c: Any
+    s: Any
+    v: Any
+    Ht: Any
+    Rt: Any
+    dyn: Any
+    Wn: Any
+    Y: Any
+
+
+class CapParts(NamedTuple):
+    """what cap_core_bwd leaves to the caller's batched reductions: the node layer's WgradParts, and the gradients of dyn and of the routing logits"""
+    wn: WgradParts
+    ddyn: Any
+    dlogit: Any
 
 
 def cap_head_fwd(p, pfx, x, dadj, dyn, dims, num_route, HS, HT):
@@ -371,7 +418,7 @@ def cap_core_fwd(p, pfx, x, dadj, dyn, Wn, bn, dims, num_route, HS, HT):
     B, T, N, C = dims
     rec, c, (s, v, Ht, Rt, Y) = cap_head_fwd(p, pfx, x, dadj, dyn, dims, num_route, HS, HT)
     out = ops.apply(rec, Wn, MODE_NODE, B * T, N, bias=bn, resid=x, epi=EPI_RES_LRELU)                                # :139-141
-    return out, c, (x, out, rec, c, s, v, Ht, Rt, dyn, Wn, Y)
+    return out, c, CapSaved(x, out, rec, c, s, v, Ht, Rt, dyn, Wn, Y)
 
 
 # Forward chains on the (sample, 16-node) slab (r04, gptst_hypertem_chain_fwd): consecutive hyperTem layers are node-local, so [hyperTem2, hyperTem3]
@@ -386,35 +433,26 @@ def chain_fwd_ok(dims):
 
 
 def ht_chain_fwd(x, stages, dims, kl=None):
-    """consecutive hyperTem layers in one launch -> [saved tuple per layer], last output.  stages: [(G, Wbt, bbt), ...]
+    """consecutive hyperTem layers in one launch -> [HtSaved per layer], last output.  stages: [(G, Wbt, bbt), ...]
     kl: the step's KlCarry — the launch carries its next KL-path stage as guest workgroups, if one is due"""
     B, T, N, C = dims
     res = ops.hypertem_chain_fwd(x.view(B, T, N, C), stages, guest=kl.guest() if kl is not None else None)
     saved, xin = [], x
     for (G, Wbt, _b), (R, o) in zip(stages, res):
         o = o.view(-1, C)
-        saved.append((xin, R.view(-1, C), o, G, Wbt))
+        saved.append(HtSaved(xin, R.view(-1, C), o, G, Wbt))
         xin = o
     return saved, xin
 
 
 def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
-    """-> dx and the pieces whose reductions are batched by the caller: (dWn, nsplit, dbn, ddyn, dlogit).
+    """-> dx and the pieces whose reductions are batched by the caller: CapParts.
     chain: dout already is dPre, and dx is returned multiplied by lrelu'(x) (x is a hyperTem output)."""
     B, T, N, C = dims
     x, out, rec, c, s, v, Ht, Rt, dyn, Wn, Y = saved
     BT, dev = B * T, x.device
     assert not chain or chain_ok(dims)
-    if C == 64:     # data gradient, weight gradient and bias gradient of the node-conditioned layer in one pass
-        drec, dWn, dbn, ns = ops.apply_wgrad(dout, None if chain else out, rec, Wn, MODE_NODE, BT, N)
-    elif chain:     # C = 128, dPre chain: neither pass reads the layer's output
-        drec = ops.apply(dout, Wn, MODE_NODE, BT, N, transw=True)
-        dWb, ns = ops.wgrad(rec, dout, MODE_NODE, BT, N, colsum_d=True)                                          # rows [dWn | dbn] per split
-        dWn, dbn = _wb_cols(dWb, C)
-    else:
-        drec = ops.apply(dout, Wn, MODE_NODE, BT, N, A2=out, transw=True, pro=PRO_DPRE)
-        dWb, ns = ops.wgrad(rec, dout, MODE_NODE, BT, N, D2=out, pro=PRO_DPRE, colsum_d=True)                    # rows [dWn | dbn] per split
-        dWn, dbn = _wb_cols(dWb, C)
+    drec, wn = _genlin_bwd(dout, out, rec, Wn, MODE_NODE, dims, chain)      # the node-conditioned layer
     dc1, dv = ops.cap_rec_bwd(drec, c, v, reduce_nodes=CTX.NODE_REDUCE)
     gw, gb = g[pfx + "ln_p.weight"], g[pfx + "ln_p.bias"]
     if FUSE_CROSS and CAP_LIN and C == 64 and CTX.NODE_REDUCE is None and Y is None:
@@ -429,7 +467,7 @@ def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
             dx, dWp, dbp, dlogit, ddyn = lin
             red.jobs.bwd_pool(_ones(dev, dWp.shape[0]), dWp, gw.view(1, C * C))      # B*T (+ the node halves' rows, r06) partials
             red.jobs.bwd_pool(_ones(dev, dbp.shape[0]), dbp, gb.view(1, C))
-            return dx, (dWn, ns, dbn, ddyn, dlogit)
+            return dx, CapParts(wn, ddyn, dlogit)
     fused = None
     if FUSE_CROSS and CTX.NODE_REDUCE is None and Y is None:
         fused = ops.cap_cross_route_bwd(x.view(B, T, N, C), p[pfx + "ln_p.weight"], p[pfx + "ln_p.bias"], c, dc1, dv, s, Rt, Ht, dyn,
@@ -450,10 +488,10 @@ def cap_core_bwd(p, g, pfx, saved, dout, dims, HS, HT, red, chain=False):
         else:
             dx = ops.apply(dY, p[pfx + "ln_p.weight"], MODE_SHARED, BT, N, resid=dout, resid2=out, epi=EPI_ADD_DPRE)
         dWp, ns2 = ops.wgrad(dY, x, MODE_SHARED, BT, N, colsum_a=True)                     # rows [dWp | colsum dY]
-        dWp, dbp = _wb_cols(dWp, C)
-        red.jobs.bwd_pool(_ones(dev, ns2), dWp, gw.view(1, C * C))
-        red.jobs.bwd_pool(_ones(dev, ns2), dbp, gb.view(1, C))
-    return dx, (dWn, ns, dbn, ddyn, dlogit)
+        wp = _wb_parts(dWp, C, ns2)
+        red.jobs.bwd_pool(_ones(dev, ns2), wp.dW, gw.view(1, C * C))
+        red.jobs.bwd_pool(_ones(dev, ns2), wp.db, gb.view(1, C))
+    return dx, CapParts(wn, ddyn, dlogit)
 
 
 _ONES = {}
@@ -467,33 +505,27 @@ def _ones(dev, n=1):
 
 
 # ---- LReLU(x W_g + b_g) with generated weights, no residual (MLP_RL, GPTST.py:24-32) --------------------------------
+class CondLinSaved(NamedTuple):
+    x: Any
+    out: Any
+    W: Any
+
+
 def condlin_fwd(x, Wg, bg, mode, dims):
     B, T, N, C = dims
     out = ops.apply(x, Wg, mode, B * T, N, bias=bg, epi=EPI_LRELU)
-    return out, (x, out, Wg)
+    return out, CondLinSaved(x, out, Wg)
 
 
 def condlin_bwd(saved, dout, emb, wpool, bpool, g_wpool, g_bpool, d_emb, mode, dims, red, chain=False, premul=False, carried=None):
     """chain: dout already is dPre;  premul (chain only): dx is returned multiplied by lrelu'(x).
-    carried: (dx, dW, db, ns) of the fused C = 64 pass already run by an earlier launch (KlCarry): only the reductions are queued."""
-    B, T, N, C = dims
-    x, out, Wg = saved
+    carried: (dx, WgradParts) of the fused C = 64 pass already run by an earlier launch (KlCarry): only the reductions are queued."""
+    C = dims[3]
     R, K = emb.shape
     assert not chain or chain_ok(dims)
-    if carried is not None:
-        dx, dW, db, ns = carried
-    elif C == 64:
-        dx, dW, db, ns = ops.apply_wgrad(dout, None if chain else out, x, Wg, mode, B * T, N, premul=chain and premul)
-    elif chain:     # C = 128, dPre chain
-        dx = (ops.apply(dout, Wg, mode, B * T, N, transw=True, resid2=x, epi=EPI_PREMUL) if premul
-              else ops.apply(dout, Wg, mode, B * T, N, transw=True))
-        dWb, ns = ops.wgrad(x, dout, mode, B * T, N, colsum_d=True)
-        dW, db = _wb_cols(dWb, C)
-    else:
-        dx = ops.apply(dout, Wg, mode, B * T, N, A2=out, transw=True, pro=PRO_DPRE)
-        dWb, ns = ops.wgrad(x, dout, mode, B * T, N, D2=out, pro=PRO_DPRE, colsum_d=True)
-        dW, db = _wb_cols(dWb, C)
-    dW = dW if dW.dim() == 2 else dW.view(ns * R, C * C)
+    dx, w = carried if carried is not None else _genlin_bwd(dout, saved.out, saved.x, saved.W, mode, dims, chain, premul)
+    ns, db = w.ns, w.db
+    dW = w.dW if w.dW.dim() == 2 else w.dW.view(ns * R, C * C)
     red.jobs.bwd_pool(emb, dW, g_wpool.view(K, C * C), nsplit=ns)
     red.jobs.bwd_pool(emb, db, g_bpool, nsplit=ns)
     red.jobs.bwd_emb(dW, wpool.view(K, C * C), d_emb, nsplit=ns)
@@ -510,10 +542,51 @@ def _sthcn_names(pfx):
     return [pfx + "hyperTem%d." % i for i in (1, 2, 3, 4)], [pfx + "cap1.", pfx + "cap2."]
 
 
-def _sthcn_gen_jobs(p, pfx, emb, jobs, A_all, dims, G_all=None, gjobs=None):
-    """Queue the generated-parameter problems of one STHCN (20 jobs); -> gen dict (tensors are filled by jobs.launch()).  gjobs: the table the
-    temporal-graph jobs go to (default: jobs)."""
-    gjobs = jobs if gjobs is None else gjobs
+class SthcnGen(NamedTuple):
+    """everything generated for one STHCN from the time index and the parameters, and the names / sizes its layers share"""
+    emb: Any        # (time_eb, teb, tes): the three time embeddings
+    A_all: Any      # (4, N, Hm*T) hyperTem factors, G_all (4, N, T, T) their temporal graphs
+    G_all: Any
+    Wb: Any         # [(Wbt, bbt)] per hyperTem layer
+    Wn: Any         # [(Wn, bn)] per cap
+    dadj: Any       # per cap
+    dyn: Any        # per cap
+    hts: Any        # parameter-name prefixes of the four hyperTem layers, cps: of the two caps
+    cps: Any
+    d: int
+    Hm: int
+    ds: int
+    HS: int
+    HT: int
+    slot: Any       # (k, n): the k-th of the n STHCNs generated together (their graph-gradient buffers are adjacent); None: on its own
+
+    def ht(self, i):
+        """(G, Wbt, bbt) of hyperTem i+1"""
+        return (self.G_all[i],) + self.Wb[i]
+
+
+class SthcnSaved(NamedTuple):
+    """saved state of an STHCN: HtSaved (h1: or EncIn) and CapSaved per layer, and what its backward needs of the SthcnGen"""
+    h1: Any
+    h2: Any
+    h3: Any
+    h4: Any
+    c1: Any
+    c2: Any
+    emb: Any
+    gen: SthcnGen
+    slot: Any
+
+
+class GenAll(NamedTuple):
+    """what gen_all returns"""
+    sthcn: Any      # {prefix: SthcnGen}
+    guide: Any      # (t4m, Wspa, bspa, Wtem, btem); None: not generated
+    pending: Any    # defer: the STHCNs' unlaunched ops.PoolJobs; else None
+
+
+def _sthcn_gen_jobs(p, pfx, emb, jobs, A_all, dims, G_all, slot=None):
+    """Queue the generated-parameter problems of one STHCN (20 jobs, and the 4 temporal graphs); -> SthcnGen (tensors are filled by jobs.launch())."""
     B, T, N, C = dims
     time_eb, teb, tes = emb
     ne, nes = p[pfx + "node_embeddings"], p[pfx + "node_embeddings_spg"]
@@ -524,21 +597,20 @@ def _sthcn_gen_jobs(p, pfx, emb, jobs, A_all, dims, G_all=None, gjobs=None):
     ds, HS, HT = cadj.shape[0], cadj.shape[1], tadj.shape[1]
     for i, h in enumerate(hts):
         jobs.fwd(ne, p[h + "adj"].view(d, Hm * T), out=A_all[i])                                          # :156
-        if G_all is not None:
-            gjobs.gram(ne, p[h + "adj"].view(d, Hm * T), out=G_all[i], A=A_all[i])                        # :156-158 G_n = A_n^T A_n, same launch
-    Wb = [jobs.fwd(time_eb, t) for h in hts for t in (p[h + "weights_pool"], p[h + "bias_pool"])]         # :160-161
-    Wn = [jobs.fwd(nes, t) for c in cps for t in (p[c + "weights_spa"], p[c + "bias_spa"])]               # :137-138
+        jobs.gram(ne, p[h + "adj"].view(d, Hm * T), out=G_all[i], A=A_all[i])                             # :156-158 G_n = A_n^T A_n, same launch
+    Wb = [(jobs.fwd(time_eb, p[h + "weights_pool"]), jobs.fwd(time_eb, p[h + "bias_pool"])) for h in hts]  # :160-161
+    Wn = [(jobs.fwd(nes, p[c + "weights_spa"]), jobs.fwd(nes, p[c + "bias_spa"])) for c in cps]            # :137-138
     dadj = [jobs.fwd(teb, p[c + "adj"].view(ds, HS * N)) for c in cps]                                    # :104
     dyn = [jobs.fwd(tes, p[c + "t_adj"].view(ds, HT * T * HS)).view(B, HT, T * HS) for c in cps]          # :129
-    return dict(emb=emb, gen=(A_all, hts, cps, d, Hm, ds, HS, HT), Wb=Wb, Wn=Wn, dadj=dadj, dyn=dyn)
+    return SthcnGen(emb, A_all, G_all, Wb, Wn, dadj, dyn, hts, cps, d, Hm, ds, HS, HT, slot)
 
 
 def gen_all(p, tidx, dims, which=(ENC, DEC), guide=True, defer=False):
     """Everything of a step that depends only on the time index and the parameters — the seven time embeddings (:256-261, :337)
     and every generated parameter of both STHCNs and of the guide MLP — in THREE launches (one time-feature job table, one
-    poolgen job table, one gram) instead of 23.  -> {prefix: gen dict, "guide": (t4m, Wspa, bspa, Wtem, btem)}
+    poolgen job table, one gram) instead of 23.  -> GenAll
     defer (r05): only the guide's parameters are generated here; the jobs of the STHCNs (parameters and temporal graphs) come back unlaunched as
-    res["pending"] (a PoolJobs) — the stepper hands them to the mask generation, whose cooperative launch runs them on the CUs it leaves idle
+    its pending (a PoolJobs) — the stepper hands them to the mask generation, whose cooperative launch runs them on the CUs it leaves idle
     (ops.mask_random / mask_adaptive jobs=); nothing before the mask reads their outputs."""
     B, T, N, C = dims
     tfj = []
@@ -550,67 +622,53 @@ def gen_all(p, tidx, dims, which=(ENC, DEC), guide=True, defer=False):
     embs = ops.timefeat_jobs_fwd(tfj, tidx)
     jobs = ops.PoolJobs()
     now = ops.PoolJobs() if defer else jobs
-    res = {}
+    sthcn, gd = {}, None
     L = 4 * len(which)
     if guide:
         gj = now
         m = "encoder.MLP_RL."
         t4m = embs[-1]
-        res["guide"] = (t4m, gj.fwd(p["encoder.neb4mask"], p[m + "weights_pool_spa"]), gj.fwd(p["encoder.neb4mask"], p[m + "bias_pool_spa"]),
-                        gj.fwd(t4m, p[m + "weights_pool_tem"]), gj.fwd(t4m, p[m + "bias_pool_tem"]))
+        gd = (t4m, gj.fwd(p["encoder.neb4mask"], p[m + "weights_pool_spa"]), gj.fwd(p["encoder.neb4mask"], p[m + "bias_pool_spa"]),
+              gj.fwd(t4m, p[m + "weights_pool_tem"]), gj.fwd(t4m, p[m + "bias_pool_tem"]))
     if L:
         adj0 = p[which[0] + "hyperTem1.adj"]
         Hm = adj0.shape[1]
         A_all = torch.empty(L, N, Hm * T, device=tidx.device)
         G_all = torch.empty(L, N, T, T, device=tidx.device)
         for k, pfx in enumerate(which):
-            res[pfx] = _sthcn_gen_jobs(p, pfx, embs[3 * k:3 * k + 3], jobs, A_all[4 * k:4 * k + 4], dims, G_all[4 * k:4 * k + 4])
-            res[pfx]["slot"] = (k, len(which))
-            res[pfx]["G_all"] = G_all[4 * k:4 * k + 4]
-
-    if defer:                                            # (a temporal graph beyond the job kernel's shapes: jobs.post — the table then launches on its own)
-        now.launch()
-        res["pending"] = jobs
-        return res
-    jobs.launch()                                        # generated parameters AND the temporal graphs: one launch
-    return res
+            sthcn[pfx] = _sthcn_gen_jobs(p, pfx, embs[3 * k:3 * k + 3], jobs, A_all[4 * k:4 * k + 4], dims, G_all[4 * k:4 * k + 4], (k, len(which)))
+    now.launch()    # generated parameters AND the temporal graphs: one launch (defer: the guide's alone; a deferred table with a temporal graph beyond
+    #                 the job kernel's shapes, jobs.post, later launches on its own)
+    return GenAll(sthcn, gd, jobs if defer else None)
 
 
 def sthcn_fwd(p, pfx, tidx, x, dims, num_route, gen=None, head=None, next_gen=None, kl=None):
-    """head: (x after hyperTem1, its saved tuple) when the previous STHCN's last chain already ran this one's first layer;
-    next_gen: gen dict of the NEXT STHCN — its hyperTem1 rides on this one's last chain launch where the chain serves the shape;
+    """head: (x after hyperTem1, its saved state) when the previous STHCN's last chain already ran this one's first layer;
+    next_gen: SthcnGen of the NEXT STHCN — its hyperTem1 rides on this one's last chain launch where the chain serves the shape;
     -> x, c1, saved, next head (None: nothing rode along).
     kl: the step's KlCarry (the chain launches carry the KL path's backward; the encoder's first cap assignment is its last input)."""
     if gen is None:
-        gen = gen_all(p, tidx, dims, which=(pfx,), guide=False)[pfx]
-    A_all, hts, cps, d, Hm, ds, HS, HT = gen["gen"]
-    Wn, dadj, dyn = gen["Wn"], gen["dadj"], gen["dyn"]
-    ht = lambda i, gn=gen: (gn["G_all"][i], gn["Wb"][2 * i], gn["Wb"][2 * i + 1])      # noqa: E731  (G, Wbt, bbt) of hyperTem i+1
-    cap = lambda i, x: cap_core_fwd(p, cps[i], x, dadj[i], dyn[i], Wn[2 * i], Wn[2 * i + 1], dims, num_route, HS, HT)   # noqa: E731
+        gen = gen_all(p, tidx, dims, which=(pfx,), guide=False).sthcn[pfx]
+    ht = gen.ht
+    cap = lambda i, x: cap_core_fwd(p, gen.cps[i], x, gen.dadj[i], gen.dyn[i], *gen.Wn[i], dims, num_route, gen.HS, gen.HT)   # noqa: E731
     pairs = chain_fwd_ok(dims)       # hyperTem PAIRS on the slab: [2, 3] and [4, next 1] (the caps' node layers stay on the node-grouped apply64)
-    sv, nhead = {}, None
-    if head is not None:
-        x, sv["h1"] = head
-    else:
-        x, sv["h1"] = hypertem_core_fwd(x, *ht(0), dims)
-    x, c1, sv["c1"] = cap(0, x)
+    nhead = None
+    x, h1 = head if head is not None else hypertem_core_fwd(x, *ht(0), dims)
+    x, c1, sc1 = cap(0, x)
     if pairs:
         if kl is not None and kl.c1 is None:
             kl.c1 = c1                                     # (the encoder's: GPTST.py:141, 426)
-        (sv["h2"], sv["h3"]), x = ht_chain_fwd(x, [ht(1), ht(2)], dims, kl)
+        (h2, h3), x = ht_chain_fwd(x, [ht(1), ht(2)], dims, kl)
     else:
-        x, sv["h2"] = hypertem_core_fwd(x, *ht(1), dims)
-        x, sv["h3"] = hypertem_core_fwd(x, *ht(2), dims)
-    x, _, sv["c2"] = cap(1, x)
+        x, h2 = hypertem_core_fwd(x, *ht(1), dims)
+        x, h3 = hypertem_core_fwd(x, *ht(2), dims)
+    x, _, sc2 = cap(1, x)
     if pairs and next_gen is not None:
-        (sv["h4"], h1n), xn = ht_chain_fwd(x, [ht(3), ht(0, next_gen)], dims, kl)
-        x, nhead = sv["h4"][2], (xn, h1n)
+        (h4, h1n), xn = ht_chain_fwd(x, [ht(3), next_gen.ht(0)], dims, kl)
+        x, nhead = h4.out, (xn, h1n)
     else:
-        x, sv["h4"] = hypertem_core_fwd(x, *ht(3), dims)
-    sv["emb"] = gen["emb"]
-    sv["gen"] = gen["gen"]
-    sv["slot"] = gen.get("slot")
-    return x, c1, sv, nhead
+        x, h4 = hypertem_core_fwd(x, *ht(3), dims)
+    return x, c1, SthcnSaved(h1, h2, h3, h4, sc1, sc2, gen.emb, gen, gen.slot), nhead
 
 
 def _grad_buffers(red, slot, N, T, HmT, ref, nsG):
@@ -631,70 +689,70 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
     defer_h1 (chain, premul_in): hyperTem1's backward is NOT run — a PendingH1 is returned and the STHCN below runs it in the pair launch
     with its own hyperTem4 (dout: that PendingH1)."""
     B, T, N, C = dims
-    time_eb, teb, tes = sv["emb"]
-    A_all, hts, cps, d, Hm, ds, HS, HT = sv["gen"]
+    time_eb, teb, tes = sv.emb
+    gn = sv.gen
+    A_all, hts, cps, d, Hm, ds, HS, HT = gn.A_all, gn.hts, gn.cps, gn.d, gn.Hm, gn.ds, gn.HS, gn.HT
     ne, nes = p[pfx + "node_embeddings"], p[pfx + "node_embeddings_spg"]
     dne, dnes = g[pfx + "node_embeddings"], g[pfx + "node_embeddings_spg"]
     d_te, d_teb, d_tes = _zeros(time_eb, *time_eb.shape), _zeros(teb, *teb.shape), _zeros(tes, *tes.shape)
     nsG = graph_grad_splits(dims)
-    dG_all, dA_all = _grad_buffers(red, sv.get("slot"), N, T, Hm * T, dout, nsG)
+    dG_all, dA_all = _grad_buffers(red, sv.slot, N, T, Hm * T, dout, nsG)
     # ---- gradient reductions of the generated parameters: queued as soon as a layer's partials have been launched (r05: the routing backward launches
     # further down the chain carry them as role workgroups, red.take_carry), executed by red.flush() at the latest ----
     J = red.jobs
     CC, BT = C * C, B * T
 
-    def queue_ht(h, hp):
-        dWbt, ns, dbias = hp                                     # (ns*BT, CC), possibly a column window of [dW | db] rows
-        J.bwd_pool(time_eb, dWbt, g[h + "weights_pool"].view(d, CC), nsplit=ns)
-        J.bwd_pool(time_eb, dbias, g[h + "bias_pool"], nsplit=ns)
-        J.bwd_emb(dWbt, p[h + "weights_pool"].view(d, CC), d_te, nsplit=ns)
-        J.bwd_emb(dbias, p[h + "bias_pool"], d_te, nsplit=ns)
+    def queue_ht(h, hp):                                         # hp.dW (ns*BT, CC), possibly a column window of [dW | db] rows
+        J.bwd_pool(time_eb, hp.dW, g[h + "weights_pool"].view(d, CC), nsplit=hp.ns)
+        J.bwd_pool(time_eb, hp.db, g[h + "bias_pool"], nsplit=hp.ns)
+        J.bwd_emb(hp.dW, p[h + "weights_pool"].view(d, CC), d_te, nsplit=hp.ns)
+        J.bwd_emb(hp.db, p[h + "bias_pool"], d_te, nsplit=hp.ns)
 
     def queue_cap(c, cp):
-        dWn, ns, dbn, ddyn, dlogit = cp
-        dW2 = dWn if dWn.dim() == 2 else dWn.view(ns * N, CC)      # (ns*N, CC), possibly a column window of [dW | db] rows
+        w, ns = cp.wn, cp.wn.ns
+        dW2 = w.dW if w.dW.dim() == 2 else w.dW.view(ns * N, CC)   # (ns*N, CC), possibly a column window of [dW | db] rows
         J.bwd_pool(nes, dW2, g[c + "weights_spa"].view(d, CC), nsplit=ns)
-        J.bwd_pool(nes, dbn, g[c + "bias_spa"], nsplit=ns)
+        J.bwd_pool(nes, w.db, g[c + "bias_spa"], nsplit=ns)
         J.bwd_emb(dW2, p[c + "weights_spa"].view(d, CC), dnes, nsplit=ns)
-        J.bwd_emb(dbn, p[c + "bias_spa"], dnes, nsplit=ns)
-        dd2 = ddyn.view(B, HT * T * HS)
+        J.bwd_emb(w.db, p[c + "bias_spa"], dnes, nsplit=ns)
+        dd2 = cp.ddyn.view(B, HT * T * HS)
         J.bwd_pool(tes, dd2, g[c + "t_adj"].view(ds, HT * T * HS))
         J.bwd_emb(dd2, p[c + "t_adj"].view(ds, HT * T * HS), d_tes)
-        dl2 = dlogit.view(BT, HS * N)
+        dl2 = cp.dlogit.view(BT, HS * N)
         J.bwd_pool(teb, dl2, g[c + "adj"].view(ds, HS * N))
         J.bwd_emb(dl2, p[c + "adj"].view(ds, HS * N), d_teb)
 
     if isinstance(dout, PendingH1):                 # the STHCN above left its first layer to the pair launch with this one's last layer
         up = dout
-        dd, _, hp4 = ht_pair_bwd(up.saved, sv["h4"], up.dd, up.dG, dG_all[3], dims, dWb1=up.dWb)
+        dd, _, hp4 = ht_pair_bwd(up.saved, sv.h4, up.dd, up.dG, dG_all[3], dims, dWb1=up.dWb)
         red.keep.append(up)
         if after_pending is not None:               # the STHCN above is complete only now (data parallel: its gradient bucket closes here)
             after_pending()
     else:
-        dd, hp4 = hypertem_core_bwd(sv["h4"], dout, dG_all[3], dims, chain, True)
+        dd, hp4 = hypertem_core_bwd(sv.h4, dout, dG_all[3], dims, chain, True)
     queue_ht(hts[3], hp4)
-    dd, cp2 = cap_core_bwd(p, g, cps[1], sv["c2"], dd, dims, HS, HT, red, chain)
+    dd, cp2 = cap_core_bwd(p, g, cps[1], sv.c2, dd, dims, HS, HT, red, chain)
     queue_cap(cps[1], cp2)
-    pair = ht_pair_bwd(sv["h3"], sv["h2"], dd, dG_all[2], dG_all[1], dims) if chain and pair_bwd_on() else None
+    pair = ht_pair_bwd(sv.h3, sv.h2, dd, dG_all[2], dG_all[1], dims) if chain and pair_bwd_on() else None
     if pair is not None:                            # hyperTem3 + hyperTem2: nothing in between (GPTST.py:267-268) -> one launch on the slab
         dd, hp3, hp2 = pair
     else:
-        dd, hp3 = hypertem_core_bwd(sv["h3"], dd, dG_all[2], dims, chain, True)
-        dd, hp2 = hypertem_core_bwd(sv["h2"], dd, dG_all[1], dims, chain, True)
+        dd, hp3 = hypertem_core_bwd(sv.h3, dd, dG_all[2], dims, chain, True)
+        dd, hp2 = hypertem_core_bwd(sv.h2, dd, dG_all[1], dims, chain, True)
     queue_ht(hts[2], hp3)
     queue_ht(hts[1], hp2)
-    dd, cp1 = cap_core_bwd(p, g, cps[0], sv["c1"], dd, dims, HS, HT, red, chain)
+    dd, cp1 = cap_core_bwd(p, g, cps[0], sv.c1, dd, dims, HS, HT, red, chain)
     queue_cap(cps[0], cp1)
-    if isinstance(sv["h1"], EncIn):                 # the encoder's first layer on the low-rank input form: no input gradient tensor
+    if isinstance(sv.h1, EncIn):                 # the encoder's first layer on the low-rank input form: no input gradient tensor
         assert chain
-        e = sv["h1"]
+        e = sv.h1
         w, bi = p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"]
         if nsG == B:
             dWb, _, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv, dG=dG_all[0])
         else:       # (C = 128: the other layers write ONE graph-gradient partial; this kernel writes one per sample)
             dWb, dGb, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv)
             torch.sum(dGb, 0, out=dG_all[0][0])
-        hp1 = _wb_record(dWb, 1, C)
+        hp1 = _wb_parts(dWb, C)
         wb = _wb_view(g["encoder.dim_in_flow.weight"], g["encoder.dim_in_flow.bias"])
         if wb is not None:
             red.jobs.bwd_pool(_ones(dd.device, dinp.shape[0]), dinp, wb)
@@ -707,10 +765,10 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
         assert chain and premul_in
         ns = ops.wgrad_nsplit(MODE_TIME, B * T, N, C)
         dWb = torch.empty(ns * B * T, C * C + C, device=dd.device, dtype=torch.float32)
-        hp1 = _wb_record(dWb, ns, C)
-        dd = PendingH1(sv["h1"], dd, dG_all[0], dWb)
+        hp1 = _wb_parts(dWb, C, ns)
+        dd = PendingH1(sv.h1, dd, dG_all[0], dWb)
     else:
-        dd, hp1 = hypertem_core_bwd(sv["h1"], dd, dG_all[0], dims, chain, premul_in)
+        dd, hp1 = hypertem_core_bwd(sv.h1, dd, dG_all[0], dims, chain, premul_in)
     queue_ht(hts[0], hp1)                           # (a deferred hyperTem1: its partials are written by the pair launch that opens the STHCN below)
     red.gram(A_all.view(4 * N, Hm, T), dG_all, dA_all.view(4 * N, Hm, T), N, nsG)
     for i, h in enumerate(hts):                                  # (dA_all is written by gram_bwd at flush time: the late table)
@@ -743,13 +801,26 @@ GUIDEIN = os.environ.get("GPTST_GUIDEIN", "1") == "1"
 GUIDE_HEAD = os.environ.get("GPTST_GUIDE_HEAD", "1") == "1"     # r06: the classifier's forward as node vectors + ONE (b,t)-grouped pass (gptst_guide_head_fwd)
 
 
+class LowRankIn(NamedTuple):
+    """saved state of the guide's input projection + node layer when they ran on the low-rank form (ops.guide_in_fwd / guide_head_fwd)"""
+    Wspa: Any
+
+
+class GuideSaved(NamedTuple):
+    t4m: Any        # the guide's time embedding
+    spa: Any        # node-conditioned layer: CondLinSaved, or LowRankIn
+    tem: Any        # time-conditioned layer: CondLinSaved
+    h2: Any         # its output, the classifier's input
+    label: Any      # int32 argmax of the probabilities per row
+
+
 def guide_fwd(p, source, tidx, dims, base, gen=None, lowrank_in=False):
-    """softmax(MLP_RL(raw flow, teb4mask(t), neb4mask)) — GPTST.py:326-332 / 337-343.  -> prob (BTN,HS), saved.
+    """softmax(MLP_RL(raw flow, teb4mask(t), neb4mask)) — GPTST.py:326-332 / 337-343.  -> prob (BTN,HS), GuideSaved.
     lowrank_in (the caller's backward is the dPre chain): input projection + node-conditioned layer as the elementwise low-rank form of
-    guidein.hip (base = 1): saved[1] is then the tuple ("lowrank", Wspa) instead of the layer's (x, out, W)."""
+    guidein.hip (base = 1): saved.spa is then a LowRankIn instead of the layer's CondLinSaved."""
     B, T, N, C = dims
     if gen is None:
-        gen = gen_all(p, tidx, dims, which=(), guide=True)["guide"]
+        gen = gen_all(p, tidx, dims, which=(), guide=True).guide
     t4m, Wspa, bspa, Wtem, btem = gen
     m = "encoder.MLP_RL."
     if lowrank_in and GUIDEIN and GUIDE_HEAD and base == 1 and C == 64:
@@ -757,16 +828,16 @@ def guide_fwd(p, source, tidx, dims, base, gen=None, lowrank_in=False):
         r = ops.guide_head_fwd(source, p[m + "ln1.weight"], p[m + "ln1.bias"], Wspa, bspa, Wtem, btem, p[m + "ln3.weight"], p[m + "ln3.bias"])
         if r is not None:
             h1, h2, prob, label = r
-            return prob, (t4m, ("lowrank", Wspa), (h1, h2, Wtem), h2, label)
+            return prob, GuideSaved(t4m, LowRankIn(Wspa), CondLinSaved(h1, h2, Wtem), h2, label)
     if lowrank_in and GUIDEIN and base == 1 and C in (64, 128):
         h1 = ops.guide_in_fwd(source, p[m + "ln1.weight"], p[m + "ln1.bias"], Wspa, bspa)                 # :22 + :24-27, elementwise
-        s1 = ("lowrank", Wspa)
+        s1 = LowRankIn(Wspa)
     else:
         h0 = ops.lin_in(source, base + 2, base, p[m + "ln1.weight"], p[m + "ln1.bias"], C)                # :22
         h1, s1 = condlin_fwd(h0, Wspa, bspa, MODE_NODE, dims)                                             # :24-27
     h2, s2 = condlin_fwd(h1, Wtem, btem, MODE_TIME, dims)                                                 # :29-32
     prob, label = ops.rowdot(h2, p[m + "ln3.weight"], p[m + "ln3.bias"], softmax=True, want_label=True)   # :33, :332, :344-345
-    return prob, (t4m, s1, s2, h2, label)
+    return prob, GuideSaved(t4m, s1, s2, h2, label)
 
 
 def _wb_view(gw, gb):
@@ -799,7 +870,7 @@ def kl_head(p, g, sv_g, prob, c1, N, w, sws, red, chain=False, carried=None):
     """0.1 KL(eb || prob) and the backward through softmax + MLP_RL.ln3 in one pass over h2 -> d_h2 (guide_bwd(dh2=...));
     chain: multiplied by lrelu'(h2).  carried: (d_h2, part) already computed by an earlier launch (KlCarry): only the reduction is queued."""
     m = "encoder.MLP_RL."
-    dh2, part = carried if carried is not None else ops.tail_kl(sv_g[3], p[m + "ln3.weight"], prob, c1, N, w, sws, premul=chain)
+    dh2, part = carried if carried is not None else ops.tail_kl(sv_g.h2, p[m + "ln3.weight"], prob, c1, N, w, sws, premul=chain)
     red.jobs.bwd_pool(_ones(prob.device, part.shape[0]), part, _wb_view(g[m + "ln3.weight"], g[m + "ln3.bias"]))
     red.keep.append((part, dh2))
     return dh2
@@ -819,28 +890,29 @@ def _linear_out_bwd(p, g, pfx, h, dy, C, chain, d_h=None):
     return dh
 
 
-def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chain=False, carried=(None, None)):
+def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chain=False, carried=None):
     """dlogit (BTN,HS): gradient of the logits — or dh2 (BTN,C) when kl_head already went through ln3 (chain: dh2 is dPre; from dlogit it is
     made so here).
-    carried: outputs of the time-conditioned layer's and of the low-rank input layers' launches already run by earlier launches (KlCarry)."""
+    carried: KlOut — outputs of the time-conditioned layer's and of the low-rank input layers' launches already run by earlier launches (KlCarry)."""
     B, T, N, C = dims
-    t4m, s1, s2, h2 = saved[:4]
+    carried = carried or KlOut()
+    t4m, s1, s2, h2 = saved.t4m, saved.spa, saved.tem, saved.h2
     m = "encoder.MLP_RL."
     if dh2 is None:
         dh2 = _linear_out_bwd(p, g, m + "ln3.", h2, dlogit, C, chain)
     d_t4m = _zeros(t4m, *t4m.shape)
     dh1 = condlin_bwd(s2, dh2, t4m, p[m + "weights_pool_tem"], p[m + "bias_pool_tem"], g[m + "weights_pool_tem"],
-                      g[m + "bias_pool_tem"], d_t4m, MODE_TIME, dims, red, chain, True, carried=carried[0])
-    if isinstance(s1[0], str):      # ("lowrank", Wspa): node layer + input projection on the low-rank form: p_n, q_n per node instead of dh0 / h0
+                      g[m + "bias_pool_tem"], d_t4m, MODE_TIME, dims, red, chain, True, carried=carried.tem)
+    if isinstance(s1, LowRankIn):   # node layer + input projection on the low-rank form: p_n, q_n per node instead of dh0 / h0
         assert chain
         neb, wpool, bpool = p["encoder.neb4mask"], p[m + "weights_pool_spa"], p[m + "bias_pool_spa"]
         K = neb.shape[1]
-        dWb, dinp = carried[1] if carried[1] is not None else ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1[1])
-        dW, db = _wb_cols(dWb, C)
-        red.jobs.bwd_pool(neb, dW, g[m + "weights_pool_spa"].view(K, C * C))
-        red.jobs.bwd_pool(neb, db, g[m + "bias_pool_spa"])
-        red.jobs.bwd_emb(dW, wpool.view(K, C * C), g["encoder.neb4mask"])
-        red.jobs.bwd_emb(db, bpool, g["encoder.neb4mask"])
+        dWb, dinp = carried.inp if carried.inp is not None else ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1.Wspa)
+        w = _wb_parts(dWb, C)
+        red.jobs.bwd_pool(neb, w.dW, g[m + "weights_pool_spa"].view(K, C * C))
+        red.jobs.bwd_pool(neb, w.db, g[m + "bias_pool_spa"])
+        red.jobs.bwd_emb(w.dW, wpool.view(K, C * C), g["encoder.neb4mask"])
+        red.jobs.bwd_emb(w.db, bpool, g["encoder.neb4mask"])
         wb = _wb_view(g[m + "ln1.weight"], g[m + "ln1.bias"])
         if wb is not None:
             red.jobs.bwd_pool(_ones(dh1.device, N), dinp, wb)
@@ -861,7 +933,16 @@ def kl_carry_ok(dims, HS, sv_g):
     """the guest form serves this step's KL path: the two-layer chain forward, the dPre chain, C = 64, T = 12, the low-rank guide input"""
     B, T, N, C = dims
     return (CARRY_KL and C == 64 and T == 12 and HS <= ops.TAIL_MAXJ and chain_fwd_ok(dims) and chain_ok(dims)
-            and sv_g is not None and isinstance(sv_g[1][0], str))
+            and sv_g is not None and isinstance(sv_g.spa, LowRankIn))
+
+
+class KlOut:
+    """outputs of the KlCarry stages launched so far, as the stand-alone launches return them (None: not carried)"""
+
+    def __init__(self):
+        self.head = None    # (dh2, part): kl_head(carried=)
+        self.tem = None     # (dh1, WgradParts) of the time-conditioned layer: condlin_bwd(carried=)
+        self.inp = None     # (dWb, dinp) of the low-rank input layers
 
 
 class KlCarry:
@@ -875,7 +956,7 @@ class KlCarry:
         self.p, self.sv_g, self.prob, self.source, self.dims, self.w, self.sws = p, sv_g, prob, source, dims, w, sws
         self.c1 = None              # set by sthcn_fwd once the encoder's first cap has run
         self.stage = 0              # stages launched so far
-        self.out = {}
+        self.out = KlOut()
 
     def guest(self):
         """-> the next stage as ops.hypertem_chain_fwd(guest=...), its outputs allocated; None when none is due (or every stage is out)"""
@@ -888,27 +969,25 @@ class KlCarry:
         st = self.stage + 1
         f = dict(device=dev, dtype=torch.float32)
         if st == 1:
-            h2, W3 = sv_g[3], p[m + "ln3.weight"]
+            h2, W3 = sv_g.h2, p[m + "ln3.weight"]
             dh2 = torch.empty_like(h2)
             part = torch.empty(ops.tail_parts(B * T * N), HS * C + HS, **f)
-            self.out[1] = (dh2, part)
+            self.out.head = (dh2, part)
             ts = [h2, W3, self.prob, self.c1, dh2, part, self.sws]
         elif st == 2:
-            h1, _, Wtem = sv_g[2]
-            dh2 = self.out[1][0]
+            h1, Wtem = sv_g.tem.x, sv_g.tem.W
+            dh2, _ = self.out.head
             ns = _C.lib().value("gptst_apply_wgrad_nsplit", MODE_TIME, B * T, N)
             dh1, dW, db = torch.empty_like(h1), torch.empty(ns * B * T, C * C, **f), torch.empty(ns * B * T, C, **f)
-            self.out[2] = (dh1, dW, db, ns)
+            self.out.tem = (dh1, WgradParts(dW, ns, db))
             ts = [dh2, h1, Wtem, dh1, dW, db]
         else:
+            dh1, _ = self.out.tem
             dWb, dinp = torch.empty(N, C * C + C, **f), torch.empty(N, 2 * C, **f)
-            self.out[3] = (dWb, dinp)
-            ts = [self.out[2][0], self.source, p[m + "ln1.weight"], p[m + "ln1.bias"], sv_g[1][1], dWb, dinp]
+            self.out.inp = (dWb, dinp)
+            ts = [dh1, self.source, p[m + "ln1.weight"], p[m + "ln1.bias"], sv_g.spa.Wspa, dWb, dinp]
         self.stage = st
         return (st, ts, 0, ops.kl_guest_blocks(st, B, T, N), HS, self.source.shape[-1], self.w)
-
-    def carried(self, st):
-        return self.out.get(st)
 
 
 def _in_proj_grads(source, base, dY, gW, gb, mask, fill, red):
@@ -938,7 +1017,7 @@ class Forward(NamedTuple):
 def autoencoder_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=None, tidx=None, lowrank_in=False, kl=None, head=True,
                     decoder=True, join=True):
     """Masked-autoencoder body — GPTST.py:415-421 + 453-456 -> Forward.  mask (BTN*base) fp32, 1 = visible; None -> no masking (eval).
-    gen: the step's gen_all() result (None: generated here).  decoder=False: the encoder alone (fine-tuning's embedding).  head: also
+    gen: the step's GenAll (None: generated here).  decoder=False: the encoder alone (fine-tuning's embedding).  head: also
     decoder.dim_flow_out (False: the caller's loss_tail goes through it).
     lowrank_in: the caller's backward is the dPre chain (model_bwd(chain=True)) — the input projection + encoder hyperTem1 then run as the
     rank-2 kernel pair of encin.hip where the shape allows.  kl: the step's KlCarry (sthcn_fwd).
@@ -947,14 +1026,14 @@ def autoencoder_fwd(p, source, mask, dims, base, num_route, scaler_zeros, gen=No
     B, T, N, C = dims
     if tidx is None:
         tidx = source[:, :, 0, base:base + 2].contiguous()
-    gen_e, gen_d = (gen[ENC], gen[DEC] if decoder else None) if gen is not None else (None, None)
+    gen_e, gen_d = (gen.sthcn[ENC], gen.sthcn[DEC] if decoder else None) if gen is not None else (None, None)
     first = None
     if lowrank_in and gen_e is not None and encin_ok(dims, base):
         # input projection + encoder hyperTem1 on the rank-2 structure of the input: no x0, no GEMM (ops.encin_ht1_fwd)
         w, bi = p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"]
-        G1, Wb = gen_e["G_all"][0], gen_e["Wb"]
-        o1, ab, wv = ops.encin_ht1_fwd(source, base, mask, 0.0 if mask is None else scaler_zeros, w, bi, G1, Wb[0], Wb[1])
-        first = (o1.view(-1, C), EncIn(source, mask, 0.0 if mask is None else scaler_zeros, Wb[0], ab, wv))
+        G1, Wbt1, bbt1 = gen_e.ht(0)
+        o1, ab, wv = ops.encin_ht1_fwd(source, base, mask, 0.0 if mask is None else scaler_zeros, w, bi, G1, Wbt1, bbt1)
+        first = (o1.view(-1, C), EncIn(source, mask, 0.0 if mask is None else scaler_zeros, Wbt1, ab, wv))
         x0 = None
     else:
         x0 = ops.lin_in(source, base + 2, base, p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"], C,
@@ -979,8 +1058,8 @@ def model_bwd(p, g, source, mask, tidx, sv_e, sv_d, dec, d_out, d_dec, dims, bas
     # bucket must be complete when its backward ends (data-parallel overlap / a side stream flush the decoder's reductions right here)
     # r05: also under the data-parallel bucket overlap — the decoder's bucket then closes ONE LAUNCH later, behind the pair launch that finishes its
     # first layer (the bucket's reductions and its forked all-reduce still run under the rest of the encoder's backward)
-    defer = (chain and (red.on_bucket is None or PAIR_UNDER_DP) and not isinstance(sv_d["h1"], EncIn)
-             and ht_pair_ok(sv_d["h1"], sv_e["h4"], dims))
+    defer = (chain and (red.on_bucket is None or PAIR_UNDER_DP) and not isinstance(sv_d.h1, EncIn)
+             and ht_pair_ok(sv_d.h1, sv_e.h4, dims))
     late = defer and red.on_bucket is not None
     d_emb = sthcn_bwd(p, g, DEC, tidx, sv_d, dd, dims, red, chain, True, defer_h1=defer)     # the decoder's input is the encoder's last LeakyReLU output
     if not late:
@@ -1002,12 +1081,12 @@ def step_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, scaler_zeros,
     sigma, mu, thresh = loss
     if sws is not None:
         chain = chain_ok(dims)                                                 # dPre chain: no backward kernel re-reads its layer's output
-        done = kl.carried if kl is not None else (lambda st: None)             # outputs of the stages the chain launches carried
+        done = kl.out if kl is not None else KlOut()                           # outputs of the stages the chain launches carried
         _, dd = loss_tail(p, g, fw.dec, source, mask, base, sigma, mu, thresh, sws, red, chain=chain)
         model_bwd(p, g, source, mask, tidx, fw.sv_e, fw.sv_d, fw.dec, None, None, dims, base, scaler_zeros, red, dd=dd, chain=chain)
         if with_kl:
-            dh2 = kl_head(p, g, sv_g, prob, fw.c1, N, 0.1, sws, red, chain=chain, carried=done(1))
-            guide_bwd(p, g, source, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=(done(2), done(3)))
+            dh2 = kl_head(p, g, sv_g, prob, fw.c1, N, 0.1, sws, red, chain=chain, carried=done.head)
+            guide_bwd(p, g, source, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=done)
     else:
         M = B * T * N
         ops.mae_fwd(fw.out, source, base + 2, mask, sigma, mu, thresh, M, base, stats)

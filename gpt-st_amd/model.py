@@ -340,7 +340,7 @@ class GPTST_Model(nn.Module):
             # outputs and saved activations are handed to the autograd node together with every generated parameter of the step
             dims, tidx = self._dims(source), self._tidx(source)
             gen = engine.gen_all(p, tidx, dims)
-            prob0, sv_g = engine.guide_fwd(p, source, tidx, dims, base, gen=gen["guide"])
+            prob0, sv_g = engine.guide_fwd(p, source, tidx, dims, base, gen=gen.guide)
             mask = self.make_mask(source, prob0, epoch)
         params = [t for _, t in self._named]
         out, dec, prob, c1 = _PretrainFn.apply(self, source, mask, (tidx, gen, prob0, sv_g), *params)

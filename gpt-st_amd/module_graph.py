@@ -119,7 +119,7 @@ class GraphedPretrain:
             tidx = m._tidx(src)
             gen = engine.gen_all(p, tidx, dims)
             lowrank = engine.chain_ok(dims)
-            prob, sv_g = engine.guide_fwd(p, src, tidx, dims, base, gen=gen["guide"], lowrank_in=lowrank)
+            prob, sv_g = engine.guide_fwd(p, src, tidx, dims, base, gen=gen.guide, lowrank_in=lowrank)
             if self.phase == 0:                                                                # GPTST.py:314-323
                 mask = ops.mask_random(torch.rand(self.M * base, device=self.dev), int(self.M * base * m.mask_ratio))
             else:                                                                              # :344-413

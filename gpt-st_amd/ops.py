@@ -3,6 +3,9 @@
 All tensors are contiguous fp32 CUDA tensors; calls enqueue on torch's current stream and never synchronise,
 so they are hipGraph-capturable.  No CPU path exists here by design.
 """
+import ctypes
+from typing import Any, NamedTuple
+
 import torch
 
 from . import _C
@@ -84,12 +87,10 @@ def poolgen_bwd_emb(dW, pool, demb, dW2=None, pool2=None, nsplit=1):
 
 
 def _ptrs(ts):
-    import ctypes
     return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
 
 
 def _ints(vs):
-    import ctypes
     return (ctypes.c_int * len(vs))(*[int(v) for v in vs])
 
 
@@ -124,6 +125,20 @@ def poolgen_bwd_emb_multi(dWs, pools, demb, nsplits=None):
           nbytes=_nb(demb, *dWs, *pools))
 
 
+class PoolJob(NamedTuple):
+    """one row of a PoolJobs table: the fields are the columns of the C ABI's job table (gptst_pool_jobs), in its order"""
+    kind: int
+    emb: Any
+    dW: Any
+    pool: Any
+    out: Any
+    R: int
+    K: int
+    cols: int
+    nsplit: int
+    ldx: int
+
+
 class PoolJobs:
     """A list of independent poolgen problems (forward generation and/or gradient reductions, each with its own embedding) that
     run as ONE launch per 112 jobs (gptst_pool_jobs).  Tensors are kept referenced until launch()."""
@@ -139,7 +154,7 @@ class PoolJobs:
         R, K = emb.shape
         if out is None:
             out = torch.empty((R,) + tuple(pool.shape[1:]), device=emb.device, dtype=torch.float32)
-        self.jobs.append((self.FWD, emb, None, pool, out, R, K, pool.numel() // K, 1, 0))
+        self.jobs.append(PoolJob(self.FWD, emb, None, pool, out, R, K, pool.numel() // K, 1, 0))
         return out
 
     def gram(self, emb, pool, out, A=None):
@@ -154,7 +169,7 @@ class PoolJobs:
             assert A is not None and A.numel() == R * cols, "gram job does not fit and no forward output was given"
             self.post.append((A, out, R, cols // 12))
             return out
-        self.jobs.append((self.GRAM, emb, None, pool, out, R, K, cols, 1, 0))
+        self.jobs.append(PoolJob(self.GRAM, emb, None, pool, out, R, K, cols, 1, 0))
         return out
 
     @staticmethod
@@ -168,28 +183,31 @@ class PoolJobs:
         _chk(emb, dpool)
         R, K = emb.shape
         cols = dpool.numel() // K
-        self.jobs.append((self.BWD_POOL, emb, dW, None, dpool, R, K, cols, nsplit, self._ldx(dW, cols)))
+        self.jobs.append(PoolJob(self.BWD_POOL, emb, dW, None, dpool, R, K, cols, nsplit, self._ldx(dW, cols)))
 
     def bwd_emb(self, dW, pool, demb, nsplit=1):
         """demb (R,K) += (sum of nsplit row blocks of dW) @ pool^T"""
         _chk(pool, demb)
         R, K = demb.shape
         cols = pool.numel() // K
-        self.jobs.append((self.BWD_EMB, None, dW, pool, demb, R, K, cols, nsplit, self._ldx(dW, cols)))
+        self.jobs.append(PoolJob(self.BWD_EMB, None, dW, pool, demb, R, K, cols, nsplit, self._ldx(dW, cols)))
+
+    @staticmethod
+    def columns(js, fields=PoolJob._fields):
+        """-> the ctypes arguments of a job table: the job count, then one array per field of `fields`, in the ABI's column order"""
+        return [len(js)] + [(_ptrs0 if f in ("emb", "dW", "pool", "out") else _ints)([getattr(j, f) for j in js])
+                            for f in PoolJob._fields if f in fields]
 
     def launch(self):
         js, self.jobs = self.jobs, []
         post, self.post = self.post, []
         if js:
-            col = lambda i: [j[i] for j in js]
-            _call("gptst_pool_jobs", len(js), _ints(col(0)), _ptrs0(col(1)), _ptrs0(col(2)), _ptrs0(col(3)), _ptrs0(col(4)), _ints(col(5)),
-                  _ints(col(6)), _ints(col(7)), _ints(col(8)), _ints(col(9)), nbytes=_nb(*[t for j in js for t in j[1:5]]))
+            _call("gptst_pool_jobs", *self.columns(js), nbytes=_nb(*[t for j in js for t in (j.emb, j.dW, j.pool, j.out)]))
         for A, G, rows, Hm in post:                      # temporal graphs whose shape is beyond the job kernel (ADVICE r03)
             _call("gptst_gram_fwd", _p(A), _p(G), rows, Hm)
 
 
 def _ptrs0(ts):
-    import ctypes
     return (ctypes.c_void_p * len(ts))(*[(t.data_ptr() if t is not None else None) for t in ts])
 
 
@@ -746,12 +764,10 @@ def cap_cross_route_lin_bwd(X, Wp, bp, c, dc1, dv, s, Rt, Ht, dyn, tmpl, dPre, o
     ddyn = torch.empty_like(dyn)
     try:
         dS_ws = torch.empty(B * T, HS, C, device=dev, dtype=torch.float32) if flags is not None else None
-        js = jobs.jobs if jobs is not None and not jobs.post and all(j[0] in (PoolJobs.BWD_POOL, PoolJobs.BWD_EMB) for j in jobs.jobs) else []
-        col = lambda i: [j[i] for j in js]      # noqa: E731
+        js = jobs.jobs if jobs is not None and not jobs.post and all(j.kind in (PoolJobs.BWD_POOL, PoolJobs.BWD_EMB) for j in jobs.jobs) else []
         _call("gptst_cap_cross_route_lin_bwd_split", _p(X), _p(Wp), _p(bp), _p(c), _p(dc1), _p(dv), _p(s), _p(Rt), _p(Ht), _p(dyn), _p(tmpl),
               _p(dPre), _p(out), int(bool(premul)), _p(dX), _p(dWp), _p(dbp), _p(dlogit), _p(ddyn), _p(dS_ws), _p(flags), B, T, N, C, HS, HT, nsplit,
-              len(js), _ints(col(0)), _ptrs0(col(1)), _ptrs0(col(2)), _ptrs0(col(3)), _ptrs0(col(4)), _ints(col(5)), _ints(col(6)), _ints(col(7)),
-              _ints(col(8)), _ints(col(9)), nbytes=_nb(X, Wp, bp, c, dc1, dv, s, Rt, dPre, out, dX, dWp, dlogit))
+              *PoolJobs.columns(js), nbytes=_nb(X, Wp, bp, c, dc1, dv, s, Rt, dPre, out, dX, dWp, dlogit))
         if js:
             jobs.jobs = []
     except _C.GptstError as e:
@@ -783,20 +799,19 @@ def _fused_jobs(jobs, u24):
     it on its own"""
     if jobs is None or not (jobs.jobs or jobs.post):
         return None
-    if not u24 or jobs.post or any(j[0] not in (PoolJobs.FWD, PoolJobs.GRAM) for j in jobs.jobs):
+    if not u24 or jobs.post or any(j.kind not in (PoolJobs.FWD, PoolJobs.GRAM) for j in jobs.jobs):
         jobs.launch()
         return None
-    odd = [j for j in jobs.jobs if j[0] == PoolJobs.FWD and j[7] % 4]          # scalar-column forward jobs (HS * N = 2070 at METR_LA): a small launch of
+    odd = [j for j in jobs.jobs if j.kind == PoolJobs.FWD and j.cols % 4]        # scalar-column forward jobs (HS * N = 2070 at METR_LA): a small launch of
     if odd:                                                                      # their own, so that the rest still rides in the mask launch
-        rest = [j for j in jobs.jobs if not (j[0] == PoolJobs.FWD and j[7] % 4)]
+        rest = [j for j in jobs.jobs if not (j.kind == PoolJobs.FWD and j.cols % 4)]
         jobs.jobs = odd
         jobs.launch()
         jobs.jobs = rest
         if not rest:
             return None
     js, jobs.jobs = jobs.jobs, []
-    col = lambda i: [j[i] for j in js]      # noqa: E731
-    return js, (len(js), _ints(col(0)), _ptrs0(col(1)), _ptrs0(col(3)), _ptrs0(col(4)), _ints(col(5)), _ints(col(6)), _ints(col(7)))
+    return js, PoolJobs.columns(js, ("kind", "emb", "pool", "out", "R", "K", "cols"))
 
 
 def mask_random(noise, k, ws=None, u24=False, jobs=None):
@@ -892,20 +907,33 @@ def timefeat_bwd(params, grads, tidx, dout, rows, K):
     _call("gptst_timefeat_bwd", *[_p(t) for t in params], *[_p(t) for t in grads], _p(tidx), _p(dout), rows, K, E)
 
 
+class TimefeatJob(NamedTuple):
+    """one time-feature MLP of a job table: params (its 10 nn.Linear tensors) on rows x K time indices; the backward also has grads and dout"""
+    params: Any
+    rows: int
+    K: int
+    grads: Any = None
+    dout: Any = None
+
+    @property
+    def E(self):
+        return self.params[1].numel()
+
+
 def timefeat_jobs_fwd(jobs, tidx):
-    """jobs: [(params (10 tensors), rows, K)] -> list of outputs (rows, E); ONE launch."""
-    outs = [torch.empty(rows, params[1].numel(), device=tidx.device, dtype=torch.float32) for params, rows, K in jobs]
-    _call("gptst_timefeat_jobs", len(jobs), 0, _ptrs([t for params, _, _ in jobs for t in params]), None, _p(tidx), _ptrs(outs),
-          _ints([r for _, r, _ in jobs]), _ints([k for _, _, k in jobs]), _ints([params[1].numel() for params, _, _ in jobs]))
+    """jobs: [TimefeatJob] -> list of outputs (rows, E); ONE launch."""
+    outs = [torch.empty(j.rows, j.E, device=tidx.device, dtype=torch.float32) for j in jobs]
+    _call("gptst_timefeat_jobs", len(jobs), 0, _ptrs([t for j in jobs for t in j.params]), None, _p(tidx), _ptrs(outs),
+          _ints([j.rows for j in jobs]), _ints([j.K for j in jobs]), _ints([j.E for j in jobs]))
     return outs
 
 
 def timefeat_jobs_bwd(jobs, tidx):
-    """jobs: [(params, grads, dout, rows, K)]; gradients are accumulated; ONE launch."""
+    """jobs: [TimefeatJob with grads and dout]; gradients are accumulated; ONE launch."""
     if not jobs:
         return
-    _call("gptst_timefeat_jobs", len(jobs), 1, _ptrs([t for j in jobs for t in j[0]]), _ptrs([t for j in jobs for t in j[1]]), _p(tidx),
-          _ptrs([j[2] for j in jobs]), _ints([j[3] for j in jobs]), _ints([j[4] for j in jobs]), _ints([j[0][1].numel() for j in jobs]))
+    _call("gptst_timefeat_jobs", len(jobs), 1, _ptrs([t for j in jobs for t in j.params]), _ptrs([t for j in jobs for t in j.grads]), _p(tidx),
+          _ptrs([j.dout for j in jobs]), _ints([j.rows for j in jobs]), _ints([j.K for j in jobs]), _ints([j.E for j in jobs]))
 
 
 # ---- loss / optimiser -------------------------------------------------------------------------------------------

@@ -447,7 +447,7 @@ class ShardedPretrainStep(PretrainStep):
             with torch.no_grad():
                 tidx = mdl._tidx(src)
                 gen = engine.gen_all(p, tidx, dims)
-                prob, _ = engine.guide_fwd(p, src, tidx, dims, base, gen=gen["guide"])
+                prob, _ = engine.guide_fwd(p, src, tidx, dims, base, gen=gen.guide)
                 if epoch <= a.change_epoch:
                     noise = rand(Mg * base) if noise is None else noise.to(self.dev).reshape(-1).contiguous()
                     mask_g = ops.mask_random(noise, int(Mg * base * a.mask_ratio))

@@ -9,6 +9,7 @@ import contextlib
 import math
 import os
 import random
+from typing import Any, NamedTuple
 
 import torch
 
@@ -19,6 +20,15 @@ from . import engine, ops
 # generation as ONE single-workgroup launch was measured too: ~120 us against ~45 us at 65 280 cells — one CU's bandwidth; it serves <= 8192 cells.)
 DEFER_GEN = os.environ.get("GPTST_DEFER_GEN", "1") == "1"      # the STHCNs' parameter generation inside the cooperative mask launch (r05)
 U24 = os.environ.get("GPTST_MASK_U24", "1") == "1"
+
+
+class Part1(NamedTuple):
+    """what part 1 of a step hands to part 2"""
+    tidx: Any
+    gen: Any        # engine.GenAll
+    red: Any        # engine.Reductions
+    prob: Any       # the guide's probabilities and engine.GuideSaved (None: no guide in this phase)
+    sv_g: Any
 
 
 class PretrainStep:
@@ -175,10 +185,10 @@ class PretrainStep:
             red.on_bucket = self._bucket_ready
             red.bucket_inline, red.fork_side = True, self.fork_side
         lowrank = self.fused_tails and engine.chain_ok(dims)      # the guide's backward (KL path) is the dPre chain: its first layers may run low-rank
-        prob, sv_g = engine.guide_fwd(p, src, tidx, dims, base, gen=gen["guide"], lowrank_in=lowrank) if need_guide else (None, None)
+        prob, sv_g = engine.guide_fwd(p, src, tidx, dims, base, gen=gen.guide, lowrank_in=lowrank) if need_guide else (None, None)
         if self._needs_exchange(phase):
-            self.label_l.copy_(sv_g[4])                           # this rank's cluster labels -> all-gather (_exchange_labels)
-        return dict(tidx=tidx, gen=gen, red=red, prob=prob, sv_g=sv_g)
+            self.label_l.copy_(sv_g.label)                           # this rank's cluster labels -> all-gather (_exchange_labels)
+        return Part1(tidx, gen, red, prob, sv_g)
 
     def _part2(self, phase, ctx):
         if not self.safe_mode:
@@ -189,10 +199,10 @@ class PretrainStep:
     def _part2_impl(self, phase, ctx):
         mdl, p, g, dims, base = self.model, self.model.param_views(), self.g, self.dims, self.base
         a = self.args
-        src, tidx, gen, red, prob, sv_g = self.src, ctx["tidx"], ctx["gen"], ctx["red"], ctx["prob"], ctx["sv_g"]
+        src, tidx, gen, red, prob, sv_g = self.src, ctx.tidx, ctx.gen, ctx.red, ctx.prob, ctx.sv_g
         engine.CTX.ARENA, engine.CTX.NODE_REDUCE = self.arena, self.node_reduce
-        pend = gen.pop("pending", None)        # the STHCNs' generated-parameter jobs: inside the mask's launch where that is the cooperative one
-        mask = self._make_mask(phase, prob, sv_g[4] if sv_g is not None else None, pend)
+        pend = gen.pending       # the STHCNs' generated-parameter jobs: inside the mask's launch where that is the cooperative one
+        mask = self._make_mask(phase, prob, sv_g.label if sv_g is not None else None, pend)
         if pend is not None:
             pend.launch()                      # (forced mask: nothing carried them; a no-op after a mask call)
         self.last_mask = mask

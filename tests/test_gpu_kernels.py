@@ -718,10 +718,11 @@ def test_timefeat_jobs_equal_single_launches():
     def params(E, K):
         return [t.to(dev) for t in (rnd(E, K, g=g), rnd(E, g=g), rnd(E, K, g=g), rnd(E, g=g), rnd(E, E, g=g), rnd(E, g=g), rnd(E, E, g=g),
                                     rnd(E, g=g), rnd(E, E, g=g), rnd(E, g=g))]
-    jobs = [(params(16, 1), B * T, 1), (params(4, 1), B * T, 1), (params(4, 12), B, 12), (params(8, 1), B * T, 1), (params(2, 12), B, 12)]
+    jobs = [ops.TimefeatJob(*j) for j in ((params(16, 1), B * T, 1), (params(4, 1), B * T, 1), (params(4, 12), B, 12), (params(8, 1), B * T, 1),
+                                          (params(2, 12), B, 12))]
     outs = ops.timefeat_jobs_fwd(jobs, tidx)
     bj = []
-    for (pp, rows, K), o in zip(jobs, outs):
+    for (pp, rows, K, _, _), o in zip(jobs, outs):
         ref = ops.timefeat_fwd(pp, tidx, rows, K)
         assert torch.equal(o, ref)
         go = rnd(rows, pp[1].numel(), g=g).to(dev)
@@ -729,7 +730,7 @@ def test_timefeat_jobs_equal_single_launches():
         ops.timefeat_bwd(pp, g1, tidx, go, rows, K)
         g2 = [torch.zeros_like(t) for t in pp]
         bj.append((pp, g2, go, rows, K, g1))
-    ops.timefeat_jobs_bwd([j[:5] for j in bj], tidx)
+    ops.timefeat_jobs_bwd([ops.TimefeatJob(pp, rows, K, g2, go) for pp, g2, go, rows, K, g1 in bj], tidx)
     for pp, g2, go, rows, K, g1 in bj:
         for a, b in zip(g1, g2):
             close(b, a.cpu(), tol=1e-5, what="timefeat_jobs bwd")
@@ -739,7 +740,7 @@ def test_timefeat_jobs_equal_single_launches():
         g3 = [[torch.zeros_like(t) for t in j[0]] for j in bj]
         ops.set_deterministic(1)
         try:
-            ops.timefeat_jobs_bwd([(j[0], g3[q], j[2], j[3], j[4]) for q, j in enumerate(bj)], tidx)
+            ops.timefeat_jobs_bwd([ops.TimefeatJob(j[0], j[3], j[4], g3[q], j[2]) for q, j in enumerate(bj)], tidx)
         finally:
             ops.set_deterministic(0)
         runs.append(g3)

@@ -2,7 +2,7 @@
 
     python tools/launch_trace.py [config ...] > trace.txt
 
-For every configuration below: the ordered (name, tag) of every call through ops._call (ops.TIMER) in one eager random-mask step and one eager
+For every configuration below (the no_* ones switch one of the engine's module attributes off after import): the ordered (name, tag) of every call through ops._call (ops.TIMER) in one eager random-mask step and one eager
 adaptive-mask + KL step, then a SHA-256 of the weights after three steps (epochs 1, 20, 25) from a fixed seed with injected mask noise and the
 library's fixed-order reductions (deterministic=True; the paths that have no such switch run under ops.set_deterministic(True)).  The graphed module
 path has no optimiser: its hash is the flat gradient of one forward / backward; the eager autograd node is traced only (see autograd_node).  Two builds of the Python side agree on what a step does exactly when
@@ -16,7 +16,7 @@ import threading
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402
-from gptst_amd import module_graph, ops, synth  # noqa: E402
+from gptst_amd import engine, module_graph, ops, synth  # noqa: E402
 from gptst_amd.config import make_args  # noqa: E402
 from gptst_amd.model import GPTST_Model, init_seed, xavier_init_  # noqa: E402
 from gptst_amd.shard import DistNodeGroup, ShardedPretrainStep  # noqa: E402
@@ -96,7 +96,8 @@ def run_steps(make, args, B, N=None):
     print("-- sha256 of the weights after 3 steps: %s" % sha(model.flat))
 
 
-def plain(shape, env=None, deterministic=False, safe=False):
+def plain(shape, env=None, deterministic=False, safe=False, attrs=None):
+    """attrs: engine module attributes switched after import, for this configuration only"""
     def make(det):
         for k, v in (env or {}).items():
             os.environ[k] = v
@@ -109,7 +110,14 @@ def plain(shape, env=None, deterministic=False, safe=False):
                 del os.environ[k]
         st.safe_mode = safe
         return st, model
-    run_steps(make, build(shape)[0], shape["B"])
+    keep = {k: getattr(engine, k) for k in attrs or {}}
+    for k, v in (attrs or {}).items():
+        setattr(engine, k, v)
+    try:
+        run_steps(make, build(shape)[0], shape["B"])
+    finally:
+        for k, v in keep.items():
+            setattr(engine, k, v)
 
 
 def shard_one_rank():
@@ -198,6 +206,9 @@ CONFIGS = {
     "graphed_module_kl": lambda: graphed(True),
     "autograd_node": autograd_node,
 }
+for _k in ("FUSE_HT_BWD", "FUSE_CROSS", "CAP_LIN", "CHAIN_FWD", "PAIR_BWD", "GUIDEIN", "CARRY_RED", "CARRY_KL"):      # branches behind the engine's switches
+    CONFIGS["no_" + _k.lower()] = lambda k=_k: plain(BENCH, attrs={k: False})
+CONFIGS["c128_no_chain128"] = lambda: plain(C128, attrs={"CHAIN128": False})
 
 if __name__ == "__main__":
     for name in sys.argv[1:] or list(CONFIGS):

@@ -61,22 +61,21 @@ def run(jobs, reps=REPS):
 
 
 def nbytes(j):
-    kind, emb, x, pool, out, R, K, cols, ns, ldx = j
-    if kind == 0:
-        return 4 * R * cols
-    if kind == 3:
-        return 4 * R * 144
-    return 4 * R * ns * cols
+    if j.kind == ops.PoolJobs.FWD:
+        return 4 * j.R * j.cols
+    if j.kind == ops.PoolJobs.GRAM:
+        return 4 * j.R * 144
+    return 4 * j.R * j.nsplit * j.cols
 
 
 for ti, tb in enumerate(TABLES):
-    kinds = sorted(set(j[0] for j in tb))
+    kinds = sorted(set(j.kind for j in tb))
     tot = sum(nbytes(j) for j in tb)
     t_all = run(tb)
     print("table %d: %3d jobs  kinds %s  %.1f MB streamed (each dW counted per job)  all: %.1f us  (%.2f TB/s)" % (
         ti, len(tb), [KIND[k] for k in kinds], tot / 1e6, t_all, tot / t_all / 1e6))
     for k in kinds:
-        sub = [j for j in tb if j[0] == k]
+        sub = [j for j in tb if j.kind == k]
         t = run(sub)
         nb = sum(nbytes(j) for j in sub)
         print("    only %-8s %3d jobs %.1f MB: %.1f us (%.2f TB/s)" % (KIND[k], len(sub), nb / 1e6, t, nb / t / 1e6))
@@ -86,8 +85,7 @@ big = max(TABLES, key=lambda tb: sum(nbytes(j) for j in tb))
 print("largest table, job by job (stand-alone launch each):")
 rows = []
 for j in big:
-    kind, emb, x, pool, out, R, K, cols, ns, ldx = j
-    rows.append((run([j], reps=10), KIND[kind], R, K, cols, ns, ldx, nbytes(j) / 1e6))
+    rows.append((run([j], reps=10), KIND[j.kind], j.R, j.K, j.cols, j.nsplit, j.ldx, nbytes(j) / 1e6))
 for t, k, R, K, cols, ns, ldx, mb in sorted(rows, reverse=True)[:40]:
     print("    %-8s R=%4d K=%2d cols=%5d ns=%d ldx=%5d  %.2f MB  %.1f us" % (k, R, K, cols, ns, ldx, mb, t))
 print("    ... %d jobs, sum of stand-alone times %.1f us" % (len(rows), sum(r[0] for r in rows)))
