@@ -520,17 +520,39 @@ def condlin_fwd(x, Wg, bg, mode, dims):
 def condlin_bwd(saved, dout, emb, wpool, bpool, g_wpool, g_bpool, d_emb, mode, dims, red, chain=False, premul=False, carried=None):
     """chain: dout already is dPre;  premul (chain only): dx is returned multiplied by lrelu'(x).
     carried: (dx, WgradParts) of the fused C = 64 pass already run by an earlier launch (KlCarry): only the reductions are queued."""
-    C = dims[3]
-    R, K = emb.shape
     assert not chain or chain_ok(dims)
     dx, w = carried if carried is not None else _genlin_bwd(dout, saved.out, saved.x, saved.W, mode, dims, chain, premul)
-    ns, db = w.ns, w.db
-    dW = w.dW if w.dW.dim() == 2 else w.dW.view(ns * R, C * C)
-    red.jobs.bwd_pool(emb, dW, g_wpool.view(K, C * C), nsplit=ns)
-    red.jobs.bwd_pool(emb, db, g_bpool, nsplit=ns)
-    red.jobs.bwd_emb(dW, wpool.view(K, C * C), d_emb, nsplit=ns)
-    red.jobs.bwd_emb(db, bpool, d_emb, nsplit=ns)
+    queue_generated(red.jobs, emb, w, wpool, bpool, g_wpool, g_bpool, d_emb)
     return dx
+
+
+# ---- reductions of a generated layer's gradients into its pools and embeddings -----------------------------------------
+def queue_generated(J, emb, parts, wpool, bpool, g_wpool, g_bpool, d_emb):
+    """Queue on J (a PoolJobs) the four reductions of a generated layer's WgradParts: pool dW, pool db, then the embedding's gradient from dW
+    and from db.  emb (R, K) generated the layer's weights from wpool (K, C, C) and bpool (K, C)."""
+    K = emb.shape[1]
+    cols = wpool.numel() // K
+    dW = parts.dW if parts.dW.dim() == 2 else parts.dW.view(-1, cols)      # (ns*R, C*C), possibly a column window of [dW | db] rows
+    J.bwd_pool(emb, dW, g_wpool.view(K, cols), nsplit=parts.ns)
+    J.bwd_pool(emb, parts.db, g_bpool, nsplit=parts.ns)
+    J.bwd_emb(dW, wpool.view(K, cols), d_emb, nsplit=parts.ns)
+    J.bwd_emb(parts.db, bpool, d_emb, nsplit=parts.ns)
+
+
+def queue_ht(J, p, g, h, hp, time_eb, d_te):
+    """the reductions of hyperTem layer h (parameter-name prefix) from its WgradParts hp; d_te: gradient of the time embedding"""
+    queue_generated(J, time_eb, hp, p[h + "weights_pool"], p[h + "bias_pool"], g[h + "weights_pool"], g[h + "bias_pool"], d_te)
+
+
+def queue_cap(J, p, g, c, cp, node, spg, time):
+    """the reductions of cap c (parameter-name prefix) from its CapParts cp.  node, spg, time: (embedding, its gradient) of the node layer
+    (node_embeddings_spg), of dyn (time_feature2, one row per sample) and of the routing logits (time_feature1_, one row per (b,t))"""
+    queue_generated(J, node[0], cp.wn, p[c + "weights_spa"], p[c + "bias_spa"], g[c + "weights_spa"], g[c + "bias_spa"], node[1])
+    for (emb, d_emb), name, dy in ((spg, "t_adj", cp.ddyn), (time, "adj", cp.dlogit)):
+        R, K = emb.shape
+        dy = dy.view(R, -1)
+        J.bwd_pool(emb, dy, g[c + name].view(K, -1))
+        J.bwd_emb(dy, p[c + name].view(K, -1), d_emb)
 
 
 # ---- STHCN (GPTST.py:253-273) --------------------------------------------------------------------------------------
@@ -700,27 +722,7 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
     # ---- gradient reductions of the generated parameters: queued as soon as a layer's partials have been launched (r05: the routing backward launches
     # further down the chain carry them as role workgroups, red.take_carry), executed by red.flush() at the latest ----
     J = red.jobs
-    CC, BT = C * C, B * T
-
-    def queue_ht(h, hp):                                         # hp.dW (ns*BT, CC), possibly a column window of [dW | db] rows
-        J.bwd_pool(time_eb, hp.dW, g[h + "weights_pool"].view(d, CC), nsplit=hp.ns)
-        J.bwd_pool(time_eb, hp.db, g[h + "bias_pool"], nsplit=hp.ns)
-        J.bwd_emb(hp.dW, p[h + "weights_pool"].view(d, CC), d_te, nsplit=hp.ns)
-        J.bwd_emb(hp.db, p[h + "bias_pool"], d_te, nsplit=hp.ns)
-
-    def queue_cap(c, cp):
-        w, ns = cp.wn, cp.wn.ns
-        dW2 = w.dW if w.dW.dim() == 2 else w.dW.view(ns * N, CC)   # (ns*N, CC), possibly a column window of [dW | db] rows
-        J.bwd_pool(nes, dW2, g[c + "weights_spa"].view(d, CC), nsplit=ns)
-        J.bwd_pool(nes, w.db, g[c + "bias_spa"], nsplit=ns)
-        J.bwd_emb(dW2, p[c + "weights_spa"].view(d, CC), dnes, nsplit=ns)
-        J.bwd_emb(w.db, p[c + "bias_spa"], dnes, nsplit=ns)
-        dd2 = cp.ddyn.view(B, HT * T * HS)
-        J.bwd_pool(tes, dd2, g[c + "t_adj"].view(ds, HT * T * HS))
-        J.bwd_emb(dd2, p[c + "t_adj"].view(ds, HT * T * HS), d_tes)
-        dl2 = cp.dlogit.view(BT, HS * N)
-        J.bwd_pool(teb, dl2, g[c + "adj"].view(ds, HS * N))
-        J.bwd_emb(dl2, p[c + "adj"].view(ds, HS * N), d_teb)
+    e_te, e_node, e_spg, e_teb = (time_eb, d_te), (nes, dnes), (tes, d_tes), (teb, d_teb)
 
     if isinstance(dout, PendingH1):                 # the STHCN above left its first layer to the pair launch with this one's last layer
         up = dout
@@ -730,19 +732,19 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
             after_pending()
     else:
         dd, hp4 = hypertem_core_bwd(sv.h4, dout, dG_all[3], dims, chain, True)
-    queue_ht(hts[3], hp4)
+    queue_ht(J, p, g, hts[3], hp4, *e_te)
     dd, cp2 = cap_core_bwd(p, g, cps[1], sv.c2, dd, dims, HS, HT, red, chain)
-    queue_cap(cps[1], cp2)
+    queue_cap(J, p, g, cps[1], cp2, e_node, e_spg, e_teb)
     pair = ht_pair_bwd(sv.h3, sv.h2, dd, dG_all[2], dG_all[1], dims) if chain and pair_bwd_on() else None
     if pair is not None:                            # hyperTem3 + hyperTem2: nothing in between (GPTST.py:267-268) -> one launch on the slab
         dd, hp3, hp2 = pair
     else:
         dd, hp3 = hypertem_core_bwd(sv.h3, dd, dG_all[2], dims, chain, True)
         dd, hp2 = hypertem_core_bwd(sv.h2, dd, dG_all[1], dims, chain, True)
-    queue_ht(hts[2], hp3)
-    queue_ht(hts[1], hp2)
+    queue_ht(J, p, g, hts[2], hp3, *e_te)
+    queue_ht(J, p, g, hts[1], hp2, *e_te)
     dd, cp1 = cap_core_bwd(p, g, cps[0], sv.c1, dd, dims, HS, HT, red, chain)
-    queue_cap(cps[0], cp1)
+    queue_cap(J, p, g, cps[0], cp1, e_node, e_spg, e_teb)
     if isinstance(sv.h1, EncIn):                 # the encoder's first layer on the low-rank input form: no input gradient tensor
         assert chain
         e = sv.h1
@@ -769,7 +771,7 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
         dd = PendingH1(sv.h1, dd, dG_all[0], dWb)
     else:
         dd, hp1 = hypertem_core_bwd(sv.h1, dd, dG_all[0], dims, chain, premul_in)
-    queue_ht(hts[0], hp1)                           # (a deferred hyperTem1: its partials are written by the pair launch that opens the STHCN below)
+    queue_ht(J, p, g, hts[0], hp1, *e_te)                      # (a deferred hyperTem1: its partials are written by the pair launch that opens the STHCN below)
     red.gram(A_all.view(4 * N, Hm, T), dG_all, dA_all.view(4 * N, Hm, T), N, nsG)
     for i, h in enumerate(hts):                                  # (dA_all is written by gram_bwd at flush time: the late table)
         red.late.bwd_pool(ne, dA_all[i], g[h + "adj"].view(d, Hm * T))
@@ -906,13 +908,8 @@ def guide_bwd(p, g, source, tidx, saved, dlogit, dims, base, red, dh2=None, chai
     if isinstance(s1, LowRankIn):   # node layer + input projection on the low-rank form: p_n, q_n per node instead of dh0 / h0
         assert chain
         neb, wpool, bpool = p["encoder.neb4mask"], p[m + "weights_pool_spa"], p[m + "bias_pool_spa"]
-        K = neb.shape[1]
         dWb, dinp = carried.inp if carried.inp is not None else ops.guide_in_bwd(dh1, source, p[m + "ln1.weight"], p[m + "ln1.bias"], s1.Wspa)
-        w = _wb_parts(dWb, C)
-        red.jobs.bwd_pool(neb, w.dW, g[m + "weights_pool_spa"].view(K, C * C))
-        red.jobs.bwd_pool(neb, w.db, g[m + "bias_pool_spa"])
-        red.jobs.bwd_emb(w.dW, wpool.view(K, C * C), g["encoder.neb4mask"])
-        red.jobs.bwd_emb(w.db, bpool, g["encoder.neb4mask"])
+        queue_generated(red.jobs, neb, _wb_parts(dWb, C), wpool, bpool, g[m + "weights_pool_spa"], g[m + "bias_pool_spa"], g["encoder.neb4mask"])
         wb = _wb_view(g[m + "ln1.weight"], g[m + "ln1.bias"])
         if wb is not None:
             red.jobs.bwd_pool(_ones(dh1.device, N), dinp, wb)

@@ -1,6 +1,7 @@
 """GPU parity tests (run on the MI355X box: pytest -m gpu): HIP kernels through the C ABI vs the pinned CPU oracle.
 Tolerance: fp32 1e-4 (north-star) on BOTH the max error relative to the tensor scale and the element-wise relative error (2 % floor),
 for every kernel output and gradient; measured worst values are recorded (profiles/parity_r02.json); index/mask work bit-exact."""
+import contextlib
 import os
 
 import pytest
@@ -49,6 +50,20 @@ def close(a, b, tol=1e-4, what=""):
 
 def rnd(*s, g, scale=1.0):
     return torch.randn(*s, generator=g) * scale
+
+
+@contextlib.contextmanager
+def launches():
+    """-> list that holds, once the block has ended, the names of the C-ABI launches enqueued inside it (ops.TIMER, as
+    tests/step_grad_util.py::one_step records a step's)"""
+    from gptst_amd import ops
+    names = []
+    ops.TIMER = []
+    try:
+        yield names
+        names += [r[0] for r in ops.TIMER]
+    finally:
+        ops.TIMER = None
 
 
 def test_poolgen_fwd_bwd():
@@ -127,6 +142,11 @@ def test_apply_and_wgrad(mode, BT, N, C):
     else:
         dW_ref = torch.einsum("bni,bno->io", A, dpre).view(1, C, C)
     close(dW, dW_ref, what="wgrad")
+    if mode == 2:       # the cap's entry Linear on its two-launch backward: dX = dY Wp + dout * lrelu'(out), and the column sums of dY (A stands for dY)
+        cs = torch.zeros(1, C, device=dev)
+        dX = ops.apply(A.to(dev), Wd.to(dev).contiguous(), mode, BT, N, resid=dout.to(dev), resid2=ref.to(dev), epi=ops.EPI_ADD_DPRE, colsum=cs)
+        close(dX, A @ W[0] + dpre, what="apply add_dpre")
+        close(cs, A.sum((0, 1)).view(1, C), what="colsum add_dpre")
 
 
 @pytest.mark.parametrize("B,N,C", [(3, 21, 64), (5, 9, 128), (1, 3, 128)])
@@ -168,6 +188,8 @@ def _hypertem_case(B, N, C, d, Hm, seed):
 
 @pytest.mark.parametrize("B,N,d,Hm", [(2, 20, 8, 8), (3, 170, 16, 8), (1, 33, 4, 5)])
 def test_hypertem_layer(B, N, d, Hm):
+    """The engine's hyperTem layer (engine.hypertem_core_fwd / hypertem_core_bwd, queue_ht and the temporal-graph reductions, through
+    gptst_amd.layers) against the ORACLE."""
     from gptst_amd import layers
     dev = _dev()
     ts, go = _hypertem_case(B, N, 64, d, Hm, 11)
@@ -177,8 +199,10 @@ def test_hypertem_layer(B, N, d, Hm):
     go = go * (ref.detach().abs() > 1e-5)       # a pre-activation within fp32 noise of 0 may pick the other LReLU slope: not a parity question
     (ref * go).sum().backward()
     gpu = [t.to(dev).requires_grad_() for t in ts]
-    out = layers.hypertem(*gpu)
-    (out * go.to(dev)).sum().backward()
+    with launches() as ran:
+        out = layers.hypertem(*gpu)
+        (out * go.to(dev)).sum().backward()
+    assert {"gptst_hypertem_fwd", "gptst_hypertem_bwd_wgrad", "gptst_gram_bwd"} <= set(ran), sorted(set(ran))      # the engine's C = 64 layer
     close(out, ref, what="hypertem out")
     for nm, a, b in zip(["x", "node_emb", "time_eb", "adj", "wpool", "bpool"], gpu, cpu):
         close(a.grad, b.grad, what="hypertem d" + nm)
@@ -195,14 +219,25 @@ def _cap_case(B, N, C, d, ds, HS, HT, seed):
     return [x, ne, tes, teb, t_adj, adj, wspa, bspa, lw, lb], go
 
 
+# test_cap_layer's cases whose engine defaults run the one-launch forms (the others' cluster tokens are beyond the launchers' LDS scratch, and the
+# engine falls back to the launches of the "kernels" id): backward gptst_cap_cross_route_lin_bwd_split, forward gptst_cap_cross_rec_fwd
+CAP_BWD_ONE_LAUNCH = {(2, 20, 8, 4, 5, 6, 3), (2, 170, 16, 4, 10, 16, 2)}
+CAP_FWD_ONE_LAUNCH = CAP_BWD_ONE_LAUNCH | {(1, 33, 4, 3, 16, 5, 0)}
+CAP_BWD_LAUNCHES = {"gptst_cap_cross_bwd", "gptst_cap_route_bwd", "gptst_linear_bwd"}
+CAP_FWD_LAUNCHES = {"gptst_cap_cross_fwd", "gptst_cap_rec_fwd"}
+
+
 @pytest.mark.parametrize("B,N,d,ds,HS,HT,R", [(2, 20, 8, 4, 5, 6, 3), (2, 170, 16, 4, 10, 16, 2), (1, 33, 4, 3, 16, 5, 0),
                                               (1, 41, 4, 4, 20, 8, 2)])
 @pytest.mark.parametrize("one_launch", [False, True], ids=["kernels", "route_lin_bwd"])
 def test_cap_layer(B, N, d, ds, HS, HT, R, one_launch, monkeypatch):
-    """one_launch (r05): the backward through gptst_cap_cross_route_lin_bwd — cross-time role + routing backward + the entry Linear's backward in one
-    launch, the fused step's default — against the ORACLE (dx, ln_p weight / bias, cluster-logit and cross-time-graph gradients)."""
-    from gptst_amd import layers
-    monkeypatch.setattr(layers, "CAP_BWD_ONE_LAUNCH", one_launch)
+    """The engine's cap (engine.cap_core_fwd / cap_core_bwd and its reduction queueing, through gptst_amd.layers) against the ORACLE.
+    one_launch: the engine's defaults — cross-time block + node scatter in one forward launch, and the backward through
+    gptst_cap_cross_route_lin_bwd (cross-time role + routing backward + the entry Linear's backward in one launch) where the shape is served;
+    else engine.FUSE_CROSS off: the per-kernel launches, as the safe-mode and node-sharded steps run them.  Each case asserts which it ran."""
+    from gptst_amd import engine, layers
+    if not one_launch:
+        monkeypatch.setattr(engine, "FUSE_CROSS", False)
     dev = _dev()
     C, T = 64, 12
     ts, go = _cap_case(B, N, C, d, ds, HS, HT, 21)
@@ -214,8 +249,19 @@ def test_cap_layer(B, N, d, ds, HS, HT, R, one_launch, monkeypatch):
     go = go * (ref.detach().abs() > 1e-5)       # a pre-activation within fp32 noise of 0 may pick the other LReLU slope: not a parity question
     (ref * go).sum().backward()
     gpu = [t.to(dev).requires_grad_() for t in ts]
-    out, c, dyn = layers.cap(*gpu, tmpl.to(dev), R)
-    (out * go.to(dev)).sum().backward()
+    with launches() as ran:
+        out, c, dyn = layers.cap(*gpu, tmpl.to(dev), R)
+        (out * go.to(dev)).sum().backward()
+    case, ran = (B, N, d, ds, HS, HT, R), set(ran)
+    bwd_fused, fwd_fused = one_launch and case in CAP_BWD_ONE_LAUNCH, one_launch and case in CAP_FWD_ONE_LAUNCH
+    if bwd_fused:
+        assert "gptst_cap_cross_route_lin_bwd_split" in ran and not ran & CAP_BWD_LAUNCHES, sorted(ran)
+    else:
+        assert CAP_BWD_LAUNCHES <= ran and not [n for n in ran if n.startswith("gptst_cap_cross_route")], sorted(ran)
+    if fwd_fused:
+        assert "gptst_cap_cross_rec_fwd" in ran and not ran & CAP_FWD_LAUNCHES, sorted(ran)
+    else:
+        assert CAP_FWD_LAUNCHES <= ran and "gptst_cap_cross_rec_fwd" not in ran, sorted(ran)
     close(c, cref.squeeze(-1), what="cap c")
     close(dyn, dynref, what="cap dyn")
     close(out, ref, what="cap out")
@@ -232,10 +278,10 @@ def test_cap_layer(B, N, d, ds, HS, HT, R, one_launch, monkeypatch):
                                                        (1, 266, 64, 4, 3, 40, 5, 2, True), (2, 70, 64, 4, 3, 20, 5, 2, True), (1, 45, 64, 4, 3, 64, 5, 1, True),
                                                        (1, 33, 64, 4, 3, 17, 5, 3, True)])
 def test_cap_layer_streaming_path(B, N, C, d, ds, HS, HT, R, force, flow):
-    """cap through the streaming kernels — the fused MFMA passes of capflow.hip (HS <= 16) or the first-generation cap_big.hip kernels:
+    """The engine's cap (as test_cap_layer) through the streaming kernels — the fused MFMA passes of capflow.hip (HS <= 16) or the first-generation cap_big.hip kernels:
     taken when the (b,t) capsule matrix does not fit LDS (N = 600 at C = 64, N = 300 at C = 128 — BASELINE config 5 territory) or
     forced, vs the oracle; the LDS path is covered by test_cap_layer.  Ragged node counts (N % 4 != 0, N % 16 != 0, several 256-node
-    chunks) and R = 0 .. 4 routing iterations included."""
+    chunks) and R = 0 .. 4 routing iterations included.  Each case asserts which of the two kernel families it ran."""
     from gptst_amd import layers, ops
     dev = _dev()
     T = 12
@@ -251,10 +297,15 @@ def test_cap_layer_streaming_path(B, N, C, d, ds, HS, HT, R, force, flow):
     gpu = [t.to(dev).requires_grad_() for t in ts]
     ops.FORCE_CAP_BIG, ops.CAP_FLOW = force, flow
     try:
-        out, c, dyn = layers.cap(*gpu, tmpl.to(dev), R)
-        (out * go.to(dev)).sum().backward()
+        capflow = ops.capflow_ok(HS, C)             # (False under the capbig id, and beyond capflow.hip's shapes: C = 128 with HS = 40)
+        with launches() as ran:
+            out, c, dyn = layers.cap(*gpu, tmpl.to(dev), R)
+            (out * go.to(dev)).sum().backward()
     finally:
         ops.FORCE_CAP_BIG, ops.CAP_FLOW = False, True
+    assert capflow == (flow and ops.capflow_ok(HS, C))
+    assert any(n.startswith("gptst_capflow_") for n in ran) == capflow, sorted(set(ran))
+    assert capflow or any(n.startswith("gptst_capbig_") for n in ran), sorted(set(ran))
     close(c, cref.squeeze(-1), what="cap c")
     close(out, ref, what="cap out")
     names = ["x", "node_emb", "time_eb_spg", "teb", "t_adj", "adj", "wspa", "bspa", "lnp_w", "lnp_b"]
@@ -915,6 +966,8 @@ def test_hypertem_bwd_wgrad_one_launch_equals_two(B, N):
     db_ref = (dO * torch.where(out > 0, 1.0, 0.01)).view(B * T, N, C).double().sum(1).cpu()
     close(dWb2[:, C * C:], db_ref, what="fused db")
     assert float((dWb1[:, C * C:] - dWb2[:, C * C:]).abs().max()) <= 4e-7 * float(db_ref.abs().max())
+    _, db1, _ = ops.hypertem_bwd(dO, out, X, G, Wbt)            # want_dbias: (node tiles, B*T, C) partials of the same sums
+    close(db1.view(-1, B * T, C).sum(0), db_ref, what="hypertem_bwd db")
 
 
 def _lg(t):
