@@ -67,7 +67,7 @@ def main():
         dp.broadcast_(model.flat)
 
     batches, nb = gdata.epoch_batches(train, args.batch_size, dp)      # under data parallelism the epoch's tail is kept as padded rounds
-    Trainer(model, args, batches, mean, std, args.batch_size, dp=dp, batches_per_epoch=nb).train()
+    Trainer(model, args, batches, mean, std, args.batch_size, dp=dp, batches_per_epoch=nb, loader=train).train()      # (-resume: Trainer.train)
     if dp is not None:
         import torch.distributed as dist
         dp.barrier()
@@ -106,7 +106,7 @@ def main_shard(args, dev):
         if ld is not None:
             ld.series = ld.series[:, n0:n1].contiguous()
     batches, nb = gdata.epoch_batches(train, args.batch_size)          # same permutation on every rank: the same global batches
-    Trainer(model, largs, batches, mean, std, args.batch_size, batches_per_epoch=nb, shard=(group, ranges)).train()
+    Trainer(model, largs, batches, mean, std, args.batch_size, batches_per_epoch=nb, shard=(group, ranges), loader=train).train()
     if dp is not None:
         import torch.distributed as dist
         dp.barrier()

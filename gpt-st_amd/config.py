@@ -65,6 +65,10 @@ def parse_args(device, argv=None):
     ap.add_argument("-steps_per_replay", default=STEPS_PER_REPLAY, type=int)      # not a reference option: see STEPS_PER_REPLAY
     # not a reference option: what the ranks of a torch.distributed.run job split — the batch (data parallel) or the nodes (shard.py)
     ap.add_argument("-shard", default="batch", choices=["batch", "nodes"], type=str)
+    # not reference options: the run's state in one portable file (checkpoint.py), written every N epochs and read back by -resume
+    ap.add_argument("-ckpt_every", default=CKPT_DEFAULTS["ckpt_every"], type=int)      # epochs between checkpoints; 0 writes none
+    ap.add_argument("-ckpt_path", default=CKPT_DEFAULTS["ckpt_path"], type=str)        # '' = <log_dir>/pretrain_state.pth; may contain {epoch}
+    ap.add_argument("-resume", default=CKPT_DEFAULTS["resume"], type=str)              # '' = start fresh, 'auto' = ckpt_path if that file exists
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -73,6 +77,9 @@ def parse_args(device, argv=None):
 # Optimisation steps enqueued per hipGraph replay by the trainer and bench.py (PretrainStep.step_group): the device idles ~19 us between
 # two graph replays, one replay per 4 steps removes three quarters of that.  1 = one replay per step.  Results do not depend on it.
 STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
+
+
+CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -84,6 +91,8 @@ def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
     ns.interval, ns.week_day = DATASET_TIME.get(dataset, (5, 7))
     ns.scaler_zeros = 0.0
     ns.steps_per_replay = STEPS_PER_REPLAY
+    for k, v in CKPT_DEFAULTS.items():
+        setattr(ns, k, v)
     for k, v in overrides.items():
         setattr(ns, k, v)
     return ns

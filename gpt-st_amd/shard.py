@@ -466,3 +466,26 @@ class ShardedPretrainStep(PretrainStep):
         finally:
             ctx.NODE_REDUCE = None
         return out.view(B, T, self.Nl, base), mask.view(B, T, self.Nl, base)
+
+    # ---- the run's state: GLOBAL tensors in the file, this rank's node range in its buffers (both collective) -------------------------
+    def _to_global(self, named):
+        full = gather_state_dict(self.group, {k: v.detach() for k, v in named.items()}, self.ranges)
+        return {k: v.cpu().clone() for k, v in full.items()}
+
+    def _to_local(self, named):
+        return shard_state_dict(named, self.n0, self.n1)
+
+    def _padding(self):
+        """mask of the flat buffer's elements no parameter owns (node_capacity padding, alignment)"""
+        mdl = self.model
+        pad = torch.ones(mdl.flat.numel(), dtype=torch.bool)
+        for k, t in mdl.named_parameters():
+            pad[mdl._offs[k]:mdl._offs[k] + t.numel()] = False
+        return pad.to(self.dev)
+
+    def load_state_dict(self, sd):
+        super().load_state_dict(sd)
+        pad = self._padding()
+        if bool(pad.any()):
+            worst = max(float(buf[pad].abs().max()) for buf in (self.model.flat, self.m, self.v))
+            assert worst == 0.0, "node_capacity padding is not zero after the load (largest |value| %g)" % worst

@@ -696,3 +696,65 @@ class PretrainStep:
             st = self.stats_out.cpu()
             del self._unseen[:]
         return self._stats_row(st, bool(self.tB and self.phase_kl))
+
+    # ---- the run's state (checkpoint.py) -------------------------------------------------------------------------------------------
+    # What a step sequence depends on besides its batches: weights, Adam moments, the two step counts (bias corrections AND, with noise_seed, the
+    # Philox key of the mask noise), the learning rate and the class-order stream.  Moments are stored by parameter name with their true shape,
+    # never as the flat buffer: the file does not know about segment order, alignment, node_capacity or ranks.
+    def _settle(self):
+        """Read the statistics of every step still in flight, as losses() / losses_group() do: an update skipped after a lost hand-off is re-run
+        and tA / tB agree with the device before they are written down."""
+        if not self._unseen:                             # every enqueued step has been looked at
+            return
+        if self._g_last is not None or self._g_fallback:
+            self.losses_group()
+        else:
+            self.losses()
+
+    def _to_global(self, named):
+        """Hook: {key: this rank's device tensor} -> {key: GLOBAL tensor on the CPU} (node shards gather over their group)"""
+        return {k: v.detach().cpu().clone() for k, v in named.items()}
+
+    def _to_local(self, named):
+        """Hook: {key: global tensor} -> this rank's part"""
+        return named
+
+    def state_dict(self):
+        """The `model`, `optimizer` and `rng` sections of a checkpoint (checkpoint.py) — synchronises.  Collective where the stepper is."""
+        self._settle()
+        mdl = self.model
+        order = {k: i for i, k in enumerate(mdl.param_keys)}
+        m, v = ({k: t for k, t in sorted(mdl.views_of(buf).items(), key=lambda kv: order[kv[0]])} for buf in (self.m, self.v))
+        return dict(model=self._to_global(mdl.state_dict()),
+                    optimizer=dict(exp_avg=self._to_global(m), exp_avg_sq=self._to_global(v), step=self.tA, step_kl=self.tB, lr=float(self.lr)),
+                    rng=dict(noise_seed=int(self.noise_seed), class_order=self.rng.getstate()))
+
+    def _stage_flat(self, named, what):
+        """{key: this rank's tensor} -> a CPU image of a flat buffer in this model's layout; what no parameter owns (alignment, capacity padding) is zero"""
+        mdl = self.model
+        img = torch.zeros(mdl.flat.numel(), dtype=torch.float32)
+        for k, view in mdl.views_of(img).items():
+            if k not in named:
+                raise KeyError("the checkpoint's %s lack %r" % (what, k))
+            if tuple(named[k].shape) != tuple(view.shape):
+                raise ValueError("%s of %s: the checkpoint holds shape %s, this model %s" % (what, k, tuple(named[k].shape), tuple(view.shape)))
+            view.copy_(named[k])
+        return img
+
+    def load_state_dict(self, sd):
+        """Continue from the `model`, `optimizer` and `rng` sections of a checkpoint.  Weights and moments are copied INTO the existing buffers: graphs
+        captured before stay valid, steppers that alias m / v (the trainer's ragged-batch steppers) keep sharing them."""
+        from .checkpoint import rng_state
+        mdl, opt = self.model, sd["optimizer"]
+        images = [self._stage_flat(self._to_local(named), what)
+                  for named, what in ((sd["model"], "weights"), (opt["exp_avg"], "exp_avg"), (opt["exp_avg_sq"], "exp_avg_sq"))]
+        self._settle()                                   # nothing of this stepper's is in flight when its buffers change
+        for dst, img in zip((mdl.flat, self.m, self.v), images):
+            dst.copy_(img)
+        for k, b in mdl.named_buffers():
+            b.copy_(sd["model"][k])
+        self.tA, self.tB, self.lr = int(opt["step"]), int(opt["step_kl"]), float(opt["lr"])
+        self.noise_seed = int(sd["rng"]["noise_seed"])
+        self.rng.setstate(rng_state(sd["rng"]["class_order"]))
+        self._unseen, self._last_call, self._g_last, self._g_fallback, self._g_list_cs = [], None, None, None, None
+        self.lost_steps = self.lost_batches = 0

@@ -29,11 +29,13 @@ def get_logger(log_dir, name="GPTST", debug=True):
 
 
 class Trainer:
-    def __init__(self, model, args, batches, scaler_mean, scaler_std, batch_size, dp=None, use_graph=True, batches_per_epoch=None, shard=None):
+    def __init__(self, model, args, batches, scaler_mean, scaler_std, batch_size, dp=None, use_graph=True, batches_per_epoch=None, shard=None,
+                 loader=None):
         """batches: a callable epoch -> iterable of (B,T,N,base+2) device tensors (ragged last batch allowed), consumed lazily — the
         windowed dataset is 12x the series and is never materialised; batches_per_epoch: the 'i/n' of the log line when known.
         shard: (group, ranges) — node-sharded run (shard.py): `model` / `args` are this rank's shard (num_nodes = its width), `batches` yields
-        its node columns [n0, n1) of the same global batches on every rank; the checkpoint and the closing report are global."""
+        its node columns [n0, n1) of the same global batches on every rank; the checkpoint and the closing report are global.
+        loader: the data.WindowLoader behind `batches` — its generator (the epoch shuffle) is part of the run's state (save_state / load_state)."""
         self.model, self.args, self.batches = model, args, batches
         self.dp, self.nb_epoch, self.shard = dp, batches_per_epoch, shard
         if shard is not None:
@@ -53,6 +55,12 @@ class Trainer:
         self.best_path = os.path.join(args.log_dir, args.save_pretrain_path)
         self.lr_steps = [int(i) for i in str(args.lr_decay_step).split(",")] if args.lr_decay else []
         self.up_epoch = [int(i) for i in str(args.up_epoch).split(",")]
+        # the run's state beside the stepper's (checkpoint.py `trainer` section): last completed epoch and the best-so-far bookkeeping
+        self.loader = loader
+        self.epoch, self.best_loss, self.best_state, self.not_improved = 0, float("inf"), None, 0
+        self.ckpt_every = int(getattr(args, "ckpt_every", 0) or 0)
+        self.ckpt_path = getattr(args, "ckpt_path", "") or os.path.join(args.log_dir, "pretrain_state.pth")
+        self.resume = getattr(args, "resume", "") or ""
 
     def _rank(self):
         if self.shard is not None:
@@ -142,9 +150,15 @@ class Trainer:
 
     def train(self):
         a = self.args
-        best_loss, best_state, not_improved = float("inf"), None, 0
+        resume = self._resume_path()
+        if resume:
+            self.load_state(resume)
+            self.logger.info("Resumed from {} after epoch {}".format(resume, self.epoch))
+        else:
+            self.epoch, self.best_loss, self.best_state, self.not_improved = 0, float("inf"), None, 0
+        best_loss, best_state, not_improved = self.best_loss, self.best_state, self.not_improved
         t0 = time.time()
-        for epoch in range(1, a.epochs + 1):
+        for epoch in range(self.epoch + 1 if resume else 1, a.epochs + 1):
             loss = self.train_epoch(epoch)
             if epoch in self.up_epoch:                   # BasicTrainer.py:138-139
                 best_loss = float("inf")
@@ -160,6 +174,10 @@ class Trainer:
             if a.early_stop and not_improved == a.early_stop_patience:    # :171-175
                 self.logger.info("Validation performance didn't improve for {} epochs. Training stops.".format(a.early_stop_patience))
                 break
+            self.epoch, self.best_loss, self.best_state, self.not_improved = epoch, best_loss, best_state, not_improved
+            if self.ckpt_every > 0 and epoch % self.ckpt_every == 0:
+                self.save_state(self.ckpt_path)
+        self.best_loss, self.best_state, self.not_improved = best_loss, best_state, not_improved
         self.logger.info("Total training time: {:.4f}min, best loss: {:.6f}".format((time.time() - t0) / 60, best_loss))
         if a.debug and best_state is not None and self.shard is not None:
             from .shard import gather_state_dict
@@ -178,6 +196,75 @@ class Trainer:
             self.test(self.batches(a.epochs))
             self.model.load_state_dict(last)
         return best_state
+
+    # ---- the run's state: one portable file (checkpoint.py) ------------------------------------------------------------------------------
+    def _agree(self, flag):
+        """rank 0's yes / no on every rank; doubles as the barrier between rank 0 writing a file and the others reading it"""
+        if self.shard is not None and self.shard[0].world > 1:
+            t = torch.tensor([float(flag) if self._rank() == 0 else 0.0], device=self.step.dev)
+            return bool(self.shard[0].all_reduce_(t).item())
+        if self.dp is not None and self.dp.world > 1:
+            t = torch.tensor([float(flag)], device=self.step.dev)
+            return bool(self.dp.broadcast_(t).item())
+        return bool(flag)
+
+    def _resume_path(self):
+        """-resume: '' = fresh, 'auto' = the checkpoint path if rank 0 finds a file there (a preempted job started again), else that file"""
+        if not self.resume:
+            return None
+        if self.resume != "auto":
+            return self.resume
+        path = self.ckpt_path.replace("{epoch}", str(self.args.epochs))
+        if "{epoch}" in self.ckpt_path:                  # one file per checkpoint: the latest epoch that has one
+            found = [e for e in range(1, self.args.epochs + 1) if os.path.exists(self.ckpt_path.replace("{epoch}", str(e)))]
+            path = self.ckpt_path.replace("{epoch}", str(found[-1])) if found else path
+        return path if self._agree(os.path.exists(path)) else None
+
+    def _global_dims(self):
+        from . import checkpoint
+        return checkpoint.dims_of(self.args, num_nodes=self.shard[1][-1][1] if self.shard is not None else None)
+
+    def save_state(self, path):
+        """Write the run's state after the last completed epoch (collective on node-sharded and data-parallel runs; rank 0 alone touches the file).
+        `path` may contain {epoch}."""
+        from . import checkpoint
+        sd = self.step.state_dict()
+        sd["rng"]["ragged_class_order"] = {int(B): s.rng.getstate() for B, s in sorted(self.ragged.items())}
+        gen = getattr(self.loader, "gen", None)
+        sd["rng"]["loader"] = gen.get_state().clone() if gen is not None else None
+        best = self.step._to_global(self.best_state) if self.best_state is not None else None
+        ckpt = checkpoint.pack(sd["model"], sd["optimizer"], sd["rng"],
+                               dict(epoch=int(self.epoch), best_loss=float(self.best_loss), not_improved=int(self.not_improved), best_state=best,
+                                    lr=float(self.step.lr)), self._global_dims())
+        path = path.replace("{epoch}", str(self.epoch))
+        if self._rank() == 0:
+            checkpoint.save(ckpt, path)
+        self._agree(True)
+        return path
+
+    def load_state(self, path):
+        """Continue from a checkpoint written by any run mode and rank layout with the same `dims` (collective: every rank reads the file)."""
+        from . import checkpoint
+        ckpt = checkpoint.load(path, self._global_dims())
+        self.step.load_state_dict(ckpt)
+        for B, state in (ckpt["rng"].get("ragged_class_order") or {}).items():
+            self._stepper_for(int(B), tail=int(B) == self.step.B).rng.setstate(checkpoint.rng_state(state))
+        gen = getattr(self.loader, "gen", None)
+        if ckpt["rng"].get("loader") is not None:
+            if gen is None:
+                raise ValueError("the checkpoint carries the state of the epoch shuffle, but this Trainer was given no loader with a generator")
+            gen.set_state(ckpt["rng"]["loader"])
+        t = ckpt["trainer"]
+        self.epoch, self.best_loss, self.not_improved = int(t["epoch"]), float(t["best_loss"]), int(t["not_improved"])
+        self.step.lr = float(t["lr"])
+        best = t["best_state"]
+        self.best_state = None if best is None else {k: v.to(self.step.dev) for k, v in self.step._to_local(best).items()}
+        if self.dp is not None and self.dp.world > 1:    # every rank read the same file: the replicas must hold the same bits
+            ref = self.model.flat.clone()
+            self.dp.broadcast_(ref)
+            if not torch.equal(ref, self.model.flat):
+                raise RuntimeError("rank %d's weights differ from rank 0's after loading %s" % (self.dp.rank, path))
+        return ckpt
 
     def test(self, batches):
         """Trainer.test of the reference in pretrain mode (model/BasicTrainer.py:209-248): forward at epoch = args.epochs (adaptive
