@@ -135,7 +135,7 @@ def main_eval(args, dev):
          else graph.synthetic_adjacency(args.num_nodes, seed=args.seed))
     ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                          drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)
-    model = EnhanceFrontEnd(args, predictor=STGCN(ap, dev, args.hidden_dim, args.output_dim)).to(dev)
+    model = EnhanceFrontEnd(args, predictor=STGCN(ap, dev, args.hidden_dim, args.output_dim), finetune_encoder=bool(args.finetune_encoder)).to(dev)
     ckpt = args.log_dir + str(args.load_pretrain_path)                           # model/Model.py:92 (plain concatenation: '/GPTST_ada.pth')
     if os.path.exists(ckpt):
         model.load_pretrained_model(ckpt)                                        # model/Model.py:91-94
@@ -145,7 +145,7 @@ def main_eval(args, dev):
                                 "randomly initialised frozen encoder)" % ckpt)
     else:
         print("gpt-st_amd: no pretrained encoder at %s -> Xavier-initialised encoder (demo run)" % ckpt)
-        for p_ in model.pretrain_model.parameters():                             # frozen (requires_grad False): xavier_init_ would skip them
+        for p_ in model.pretrain_model.parameters():                             # (all of them, the frozen ones too: xavier_init_ would skip those)
             torch.nn.init.xavier_uniform_(p_) if p_.dim() > 1 else torch.nn.init.uniform_(p_)
     EvalTrainer(model, args, train, val, test, float(scaler.mean), float(scaler.std)).train()
 

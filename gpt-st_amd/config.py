@@ -69,6 +69,9 @@ def parse_args(device, argv=None):
     ap.add_argument("-ckpt_every", default=CKPT_DEFAULTS["ckpt_every"], type=int)      # epochs between checkpoints; 0 writes none
     ap.add_argument("-ckpt_path", default=CKPT_DEFAULTS["ckpt_path"], type=str)        # '' = <log_dir>/pretrain_state.pth; may contain {epoch}
     ap.add_argument("-resume", default=CKPT_DEFAULTS["resume"], type=str)              # '' = start fresh, 'auto' = ckpt_path if that file exists
+    # not reference options: -mode eval trains the pretrained encoder too (enhance.EnhanceFrontEnd), at lr_init * encoder_lr_scale
+    ap.add_argument("-finetune_encoder", default=FINETUNE_DEFAULTS["finetune_encoder"], type=_EVAL)
+    ap.add_argument("-encoder_lr_scale", default=FINETUNE_DEFAULTS["encoder_lr_scale"], type=float)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -80,6 +83,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
+FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0)
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -91,7 +95,7 @@ def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
     ns.interval, ns.week_day = DATASET_TIME.get(dataset, (5, 7))
     ns.scaler_zeros = 0.0
     ns.steps_per_replay = STEPS_PER_REPLAY
-    for k, v in CKPT_DEFAULTS.items():
+    for k, v in list(CKPT_DEFAULTS.items()) + list(FINETUNE_DEFAULTS.items()):
         setattr(ns, k, v)
     for k, v in overrides.items():
         setattr(ns, k, v)

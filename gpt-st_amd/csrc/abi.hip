@@ -7,6 +7,7 @@ extern "C" int gptst_abi_version(void) { return GPTST_ABI_VERSION; }
 thread_local int g_deterministic = 0;
 // 1: bit-reproducible steps (single-owner reductions in a fixed order where the default path uses float atomics); thread-local.
 extern "C" int gptst_set_deterministic(int on) { g_deterministic = on ? 1 : 0; return GPTST_OK; }
+extern "C" int gptst_deterministic_state(void) { return g_deterministic; }
 
 // number of bounded in-launch hand-off waits that expired since the library was loaded (cap_route_bwd2_kernel's roles, hypertem_bwd_pair_kernel's
 // lower weight-gradient role, the grid barriers of the cooperative mask launch): 0 in a healthy run.  An expiry poisons that launch's output with NaN; this tells such a NaN from numerical trouble.

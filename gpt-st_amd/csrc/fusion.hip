@@ -223,6 +223,87 @@ __global__ __launch_bounds__(256, 2) void fusion_gate_bwd_kernel(const float* __
     }
 }
 
+// the same data path when the embedding is trained too (fine-tuning): besides the four tensors above, the gradient of F itself,
+//     dF = dHm z + dpre W_s        (Hm = z F + (1 - z) x_t;  pre = F W_s^T + ...)
+// dpre goes from the accumulator layout through the wave's tile into the A layout (as Hm does in the forward) for a second GEMM against W_s^T
+// staged beside W_o^T.  dpre, dxd, Hm, xt: the arithmetic of fusion_gate_bwd_kernel in its order (bit-identical).
+__global__ __launch_bounds__(256, 2) void fusion_gate_bwd_df_kernel(const float* __restrict__ dOut, const float* __restrict__ F, const float* __restrict__ z,
+                                                                    const float* __restrict__ src, int lda, int base, FuW w, float* __restrict__ dpre,
+                                                                    float* __restrict__ dxd, float* __restrict__ Hm, float* __restrict__ xt,
+                                                                    float* __restrict__ dF, int rows, int tiles_per_wave) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* WoT = smem;                      // [64 (c)][FU_P] : W_o transposed (dHm = dOut W_o)
+    float* WsT = WoT + 64 * FU_P;           // [64 (c)][FU_P] : W_s transposed (dpre W_s: the same GEMM form)
+    float* Wtl = WsT + 64 * FU_P;
+    float* btl = Wtl + 64 * FU_MAXB;
+    float* tiles = btl + 64;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
+    fu_stage_w<true>(WoT, w.Wo, tid, 256); fu_stage_w<true>(WsT, w.Ws, tid, 256);
+    if (tid < 64) {
+        for (int b = 0; b < FU_MAXB; ++b) Wtl[tid * FU_MAXB + b] = b < base ? w.Wt[tid * base + b] : 0.f;
+        btl[tid] = w.bt[tid];
+    }
+    __syncthreads();
+    float* tile = tiles + wave * 16 * FU_P;
+    const int ntiles = (rows + 15) / 16;
+    const int t0 = (blockIdx.x * 4 + wave) * tiles_per_wave, t1 = min(ntiles, t0 + tiles_per_wave);
+    for (int t = t0; t < t1; ++t) {
+        const int row0 = t * 16;
+        const int ra = min(row0 + j, rows - 1);
+        float4 ad[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ad[q] = ld4(dOut + (size_t)ra * 64 + 16 * q + 4 * kk);
+        float fd[4][4], xd[4][4], zd[4][4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int rr = min(row0 + kk * 4 + r, rows - 1);
+            float sd[FU_MAXB];
+#pragma unroll
+            for (int b = 0; b < FU_MAXB; ++b) sd[b] = b < base ? src[(size_t)rr * lda + b] : 0.f;
+#pragma unroll
+            for (int ct = 0; ct < 4; ++ct) {
+                fd[ct][r] = F[(size_t)rr * 64 + 16 * ct + j];
+                zd[ct][r] = z[(size_t)rr * 64 + 16 * ct + j];
+                float a = btl[16 * ct + j];
+                for (int b = 0; b < base; ++b) a = fmaf(sd[b], Wtl[(16 * ct + j) * FU_MAXB + b], a);
+                xd[ct][r] = a;
+            }
+        }
+        SB();
+        f32x4 acc[4];
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        fu_gemm(acc, ad, WoT, j, kk);
+        float v0[4][4], v1[4][4], v2[4][4], v3[4][4];
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float dh = acc[ct][r], zz = zd[ct][r];
+                v0[ct][r] = dh * (fd[ct][r] - xd[ct][r]) * (zz * (1.f - zz));     // dpre
+                v1[ct][r] = dh * (1.f - zz);                                     // dxd
+                v2[ct][r] = fmaf(zz, fd[ct][r] - xd[ct][r], xd[ct][r]);          // Hm
+                v3[ct][r] = dh * zz;                                             // the blend's direct path into F
+            }
+        fu_store_tile(tile, v1, dxd, row0, rows, lane, j, kk);
+        fu_store_tile(tile, v2, Hm, row0, rows, lane, j, kk);
+        fu_store_tile(tile, xd, xt, row0, rows, lane, j, kk);
+        fu_store_tile(tile, v0, dpre, row0, rows, lane, j, kk);
+        // ---- the tile now holds dpre: -> A layout, dF = dpre W_s + dHm z ----
+        float4 ap[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) ap[q] = ld4(tile + j * FU_P + 16 * q + 4 * kk);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        fu_gemm(acc, ap, WsT, j, kk);
+#pragma unroll
+        for (int ct = 0; ct < 4; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v3[ct][r] += acc[ct][r];
+        fu_store_tile(tile, v3, dF, row0, rows, lane, j, kk);
+    }
+}
+
 static int fu_tiles_per_wave(int rows) {
     const int ntiles = (rows + 15) / 16;
     int tpw = (ntiles + 4 * 512 - 1) / (4 * 512);                    // ~512 workgroups of 4 waves (two per CU: 70 KB of LDS each)
@@ -254,6 +335,21 @@ extern "C" int gptst_fusion_gate_bwd(const float* dOut, const float* F, const fl
     const int tpw = fu_tiles_per_wave(rows), ntiles = (rows + 15) / 16;
     hipLaunchKernelGGL(fusion_gate_bwd_kernel, dim3((ntiles + 4 * tpw - 1) / (4 * tpw)), dim3(256), smem, (hipStream_t)stream, dOut, F, z, src, lda, base,
                        FuW{nullptr, nullptr, nullptr, nullptr, Wo, nullptr, Wt, bt}, dpre, dxd, Hm, xt, rows, tpw);
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}
+
+// gptst_fusion_gate_bwd plus dF (rows, 64) = dHm z + dpre W_s, the gradient of the embedding F (fine-tuning the encoder), in the same launch
+extern "C" int gptst_fusion_gate_bwd_df(const float* dOut, const float* F, const float* z, const float* src, int lda, int base, const float* Wo,
+                                        const float* Wt, const float* bt, const float* Ws, float* dpre, float* dxd, float* Hm, float* xt, float* dF,
+                                        int rows, int C, void* stream) {
+    if (!dOut || !F || !z || !src || !Wo || !Wt || !bt || !Ws || !dpre || !dxd || !Hm || !xt || !dF || rows <= 0 || base <= 0 || lda < base)
+        return GPTST_EARG;
+    if (C != 64 || base > FU_MAXB) return GPTST_ESHAPE;
+    const size_t smem = (2 * 64 * FU_P + 64 * FU_MAXB + 64 + 4 * 16 * FU_P) * sizeof(float);      // 53,504 B: two workgroups per CU
+    const int tpw = fu_tiles_per_wave(rows), ntiles = (rows + 15) / 16;
+    hipLaunchKernelGGL(fusion_gate_bwd_df_kernel, dim3((ntiles + 4 * tpw - 1) / (4 * tpw)), dim3(256), smem, (hipStream_t)stream, dOut, F, z, src, lda,
+                       base, FuW{Ws, nullptr, nullptr, nullptr, Wo, nullptr, Wt, bt}, dpre, dxd, Hm, xt, dF, rows, tpw);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
 }

@@ -1068,6 +1068,14 @@ def model_bwd(p, g, source, mask, tidx, sv_e, sv_d, dec, d_out, d_dec, dims, bas
         _in_proj_grads(source, base, d_x0, g["encoder.dim_in_flow.weight"], g["encoder.dim_in_flow.bias"], mask, scaler_zeros, red)
 
 
+def encoder_bwd(p, g, source, tidx, sv_e, d_emb, dims, base, red):
+    """Backward of autoencoder_fwd(decoder=False, lowrank_in=False, mask=None) given d_emb (BTN, C), the gradient of the encoder's embedding
+    (fine-tuning the encoder downstream: model._EncoderFn): the encoder STHCN in the non-chain forms the module path runs, then the input
+    projection on the unmasked flow.  The caller runs red.flush(tidx)."""
+    d_x0 = sthcn_bwd(p, g, ENC, tidx, sv_e, d_emb, dims, red, chain=False, premul_in=False)
+    _in_proj_grads(source, base, d_x0, g["encoder.dim_in_flow.weight"], g["encoder.dim_in_flow.bias"], None, 0.0, red)
+
+
 def step_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, scaler_zeros, red, loss, stats, sws=None, with_kl=False, kl=None):
     """The pretraining loss (masked MAE [+ 0.1 KL], Run.py:92-100) and the whole backward behind autoencoder_fwd / guide_fwd, for the steppers.
     loss: (sigma, mu, mape threshold).  sws (the step's per-workgroup loss statistics, zeroed): the FUSED heads — loss_tail and kl_head go

@@ -7,7 +7,7 @@ import torch
 import torch.nn as nn
 
 from .fusion import fusion_gate
-from .model import GPTST_Model
+from .model import GPTST_Model, _on_encoder_path
 
 
 class Fusion(nn.Module):                                                   # model/Model.py:5-18
@@ -24,15 +24,19 @@ class Fusion(nn.Module):                                                   # mod
 
 class EnhanceFrontEnd(nn.Module):
     """``Enhance_model`` in ``mode='eval'`` (model/Model.py:40-46,91-107): frozen pretrained encoder -> fusion with a linear lift
-    of the raw flow -> predictor.  ``predictor=None`` returns the fused embedding."""
+    of the raw flow -> predictor.  ``predictor=None`` returns the fused embedding.  ``finetune_encoder=True`` unfreezes the encoder path
+    (``encoder.dim_in_flow`` and ``encoder.STHCN_encode``; the guide network and the decoder stay frozen): gradients reach it through the gate
+    (fusion.py) and the encoder's own HIP backward (model._EncoderFn)."""
 
-    def __init__(self, args, predictor=None):
+    def __init__(self, args, predictor=None, finetune_encoder=False):
         super().__init__()
         assert args.mode == "eval", "the enhanced front end wraps the encoder in eval mode (reference Run.py -mode eval)"
         self.input_base_dim = args.input_base_dim
+        self.finetune_encoder = bool(finetune_encoder)
         self.pretrain_model = GPTST_Model(args)
-        for p in self.pretrain_model.parameters():                         # :93-94
-            p.requires_grad = False
+        self.pretrain_model.finetune = self.finetune_encoder
+        for k, p in self.pretrain_model.named_parameters():                # :93-94; fine-tuning: what the embedding depends on is trained too
+            p.requires_grad = self.finetune_encoder and _on_encoder_path(k)
         self.fusion = Fusion(args.hidden_dim)
         self.lin_test = nn.Linear(args.input_base_dim, args.hidden_dim)
         self.predictor = predictor
@@ -44,7 +48,9 @@ class EnhanceFrontEnd(nn.Module):
     def forward(self, source, label=None, batch_seen=None):                # :96-107
         x_pretrain_flow = self.pretrain_model(source, label)[0]
         # :105-107 lin_test + Fusion: one HIP launch forward (csrc/fusion.hip) where the shape allows, the torch modules otherwise
-        eb = fusion_gate(x_pretrain_flow.detach(), source, self.fusion, self.lin_test, self.input_base_dim)
+        if not self.finetune_encoder:
+            x_pretrain_flow = x_pretrain_flow.detach()
+        eb = fusion_gate(x_pretrain_flow, source, self.fusion, self.lin_test, self.input_base_dim)
         if self.predictor is None:
             return eb
         x = self.predictor(eb)

@@ -1,5 +1,5 @@
 """``-mode eval`` training loop (reference model/BasicTrainer.py:38-123 non-pretrain branches, :125-197, :209-248): a downstream predictor
-is trained on the enhanced embedding — frozen HIP encoder -> Fusion -> predictor (enhance.EnhanceFrontEnd) — with the masked-MAE loss on
+is trained on the enhanced embedding — frozen (or, -finetune_encoder True, fine-tuned) HIP encoder -> Fusion -> predictor (enhance.EnhanceFrontEnd) — with the masked-MAE loss on
 de-normalised values (Run.py:91-101, lib/metrics.py:11-18), gradient clipping and Adam + MultiStepLR (Run.py:134-141); the best model
 on the validation loss is kept (early stopping as in the reference) and tested per horizon on the test loader, the metric sums
 accumulated on the device by gptst_metrics_accum.  The trainable part is ordinary torch autograd (downstream plumbing, not the hot path)."""
@@ -23,12 +23,22 @@ class EvalTrainer:
         self.model, self.args = model, args
         self.train_loader, self.val_loader, self.test_loader = train, val, test
         self.mean, self.std = float(scaler_mean), float(scaler_std)
-        params = [p for p in model.parameters() if p.requires_grad]
-        self.opt = torch.optim.Adam(params, lr=args.lr_init, eps=1.0e-8, weight_decay=0, amsgrad=False)      # Run.py:134-135
+        self.opt = torch.optim.Adam(self.param_groups(model, args), lr=args.lr_init, eps=1.0e-8, weight_decay=0, amsgrad=False)   # Run.py:134-135
         steps = [int(i) for i in str(args.lr_decay_step).split(",")] if args.lr_decay else []
         self.sched = torch.optim.lr_scheduler.MultiStepLR(self.opt, milestones=steps, gamma=args.lr_decay_rate) if steps else None
         self.logger = get_logger(args.log_dir, name=str(args.model), debug=args.debug)
         self.nin = args.input_base_dim + args.input_extra_dim
+
+    @staticmethod
+    def param_groups(model, args):
+        """the trainable parameters; a fine-tuned encoder's (EnhanceFrontEnd(finetune_encoder=True)) as a group of their own at
+        lr_init * encoder_lr_scale.  The scheduler scales every group."""
+        params = [p for p in model.parameters() if p.requires_grad]
+        ids = {id(p) for p in model.pretrain_model.parameters()} if hasattr(model, "pretrain_model") else set()
+        enc, rest = [p for p in params if id(p) in ids], [p for p in params if id(p) not in ids]
+        if not enc:
+            return params
+        return [dict(params=rest), dict(params=enc, lr=args.lr_init * float(getattr(args, "encoder_lr_scale", 1.0)))]
 
     def _loss(self, out, target):
         return masked_mae(out, target[..., :self.args.output_dim], self.mean, self.std, self.args.mape_thresh)

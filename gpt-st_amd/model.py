@@ -145,6 +145,40 @@ class _PretrainFn(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads)
 
 
+def _on_encoder_path(key):
+    """the parameters the eval-mode embedding depends on (forward_fune): the input projection and the encoder STHCN"""
+    return key.startswith("encoder.dim_in_flow.") or key.startswith(engine.ENC)
+
+
+class _EncoderFn(torch.autograd.Function):
+    """Autograd node of the eval-mode embedding when the encoder is fine-tuned downstream (GPTST_Model.finetune): forward_fune's forward with
+    its saved state kept, and the encoder's backward in the non-chain forms _PretrainFn runs."""
+
+    @staticmethod
+    def forward(ctx, model, source, *params):
+        dims, base = model._dims(source), model.input_base_dim
+        fw = engine.autoencoder_fwd(model.param_views(), source, None, dims, base, model.num_route, model.scaler_zeros, decoder=False)
+        ctx.model, ctx.saved = model, (source, fw.sv_e, dims)
+        B, T, N, C = dims
+        return fw.emb.view(B, T, N, C)
+
+    @staticmethod
+    def backward(ctx, d_emb):
+        model = ctx.model
+        source, sv_e, dims = ctx.saved
+        g = model.views_of(model._grad_buffer())      # (fresh per node: see _grad_buffer)
+        red = engine.Reductions()
+        red.no_carry = True
+        tidx = model._tidx(source)
+        # fixed-order reductions: by default the time-feature and embedding gradients end in float atomics, and two backwards of one batch then differ
+        # by ~2e-6 of scale in time_feature1.  The mode is thread-local and autograd runs this node on its own thread: switched here, put back after.
+        # Measured cost: 0.3 ms of the 8.4 ms fine-tuning step at (64, 12, 170, 64) (DESIGN.md section 14)
+        with ops.deterministic():
+            engine.encoder_bwd(model.param_views(), g, source, tidx, sv_e, d_emb.contiguous().view(-1, dims[3]), dims, model.input_base_dim, red)
+            red.flush(tidx)
+        return (None, None) + tuple(g[k] if _on_encoder_path(k) else None for k in model.param_keys)
+
+
 class GPTST_Model(nn.Module):
     _named = None                                # [(key, Parameter)] in module order, walked once per _flatten()
 
@@ -166,6 +200,7 @@ class GPTST_Model(nn.Module):
         self.HS, self.HT, self.HT_Tem = args.HS, args.HT, args.HT_Tem
         self.num_route = args.num_route
         self.mode = args.mode
+        self.finetune = False                    # eval mode: gradients reach the encoder (forward_fune; enhance.EnhanceFrontEnd(finetune_encoder=True))
         self.model = getattr(args, "model", None)
         self.scaler_zeros = float(getattr(args, "scaler_zeros", 0.0))
         self.mask_ratio, self.ada_mask_ratio, self.ada_type = args.mask_ratio, args.ada_mask_ratio, args.ada_type
@@ -350,6 +385,9 @@ class GPTST_Model(nn.Module):
 
     def forward_fune(self, source, label):
         source = source.contiguous().float()
+        if self.finetune and torch.is_grad_enabled():
+            e = _EncoderFn.apply(self, source, *[t for _, t in self._named])
+            return e, e, e, e, e
         with torch.no_grad():
             emb = engine.autoencoder_fwd(self.param_views(), source, None, self._dims(source), self.input_base_dim,
                                          self.num_route, self.scaler_zeros, decoder=False).emb

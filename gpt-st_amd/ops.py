@@ -3,6 +3,7 @@
 All tensors are contiguous fp32 CUDA tensors; calls enqueue on torch's current stream and never synchronise,
 so they are hipGraph-capturable.  No CPU path exists here by design.
 """
+import contextlib
 import ctypes
 from typing import Any, NamedTuple
 
@@ -963,6 +964,17 @@ def set_deterministic(on):
     weight gradients) run as single-owner kernels with a fixed summation order.  Thread-local in the library."""
     _C.lib().call("gptst_set_deterministic", int(bool(on)))
 
+
+@contextlib.contextmanager
+def deterministic():
+    """the launches enqueued inside run in the fixed-order mode on THIS thread (autograd runs a backward node on a thread of its own, which
+    does not see the caller's set_deterministic); the thread's setting is put back afterwards"""
+    keep = _C.lib().value("gptst_deterministic_state")
+    set_deterministic(True)
+    try:
+        yield
+    finally:
+        set_deterministic(keep)
 
 
 def tail_parts(rows):

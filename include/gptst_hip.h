@@ -26,12 +26,13 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 16  /* 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 17  /* 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
  * order-fixed by construction.  Thread-local. */
 int gptst_set_deterministic(int on);
+int gptst_deterministic_state(void);   /* the calling thread's setting (a caller that switches the mode for a few launches puts it back) */
 /* Number of bounded in-launch hand-off waits that expired since the library was loaded (the roles of gptst_cap_cross_route_bwd /
  * gptst_cap_cross_route_lin_bwd, the lower weight-gradient role of gptst_hypertem_bwd_pair, the grid barriers of the cooperative mask launch
  * (gptst_mask_*_u24): a consumer workgroup waits at most 2 s of wall clock for its producer and poisons its output with NaN on expiry).  0 in a healthy run; lets a NaN loss be told from numerical trouble.  Synchronises. */
@@ -425,6 +426,11 @@ int gptst_fusion_gate_fwd(const float* F, const float* src, int lda, int base, c
                           int rows, int C, void* stream);
 int gptst_fusion_gate_bwd(const float* dOut, const float* F, const float* z, const float* src, int lda, int base, const float* Wo,
                           const float* Wt, const float* bt, float* dpre, float* dxd, float* Hm, float* xt, int rows, int C, void* stream);
+/* gptst_fusion_gate_bwd when the embedding F is trained too (fine-tuning the encoder): the same four tensors, bit-identical, and in the same
+ * launch dF (rows, C) = dHm z + dpre Ws, the gradient of F through the blend and through HS_fc.  C = 64 and base <= 4, else GPTST_ESHAPE. */
+int gptst_fusion_gate_bwd_df(const float* dOut, const float* F, const float* z, const float* src, int lda, int base, const float* Wo,
+                             const float* Wt, const float* bt, const float* Ws, float* dpre, float* dxd, float* Hm, float* xt, float* dF,
+                             int rows, int C, void* stream);
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column
  * sums of X | sums of a'] for the caller to fold (one kind-1 pool job next to the other reductions of a step). */
