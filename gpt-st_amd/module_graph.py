@@ -91,8 +91,7 @@ class GraphedPretrain:
         self.M = B * T * N
         self.src = torch.zeros(*shape, device=self.dev)
         self.ctrl = torch.zeros(self.HS + 2, dtype=torch.int32, device=self.dev)             # [class order | adaptive budget, random budget]
-        self._ring = [dict(h=torch.zeros(self.HS + 2, dtype=torch.int32).pin_memory(), ev=None) for _ in range(4)]
-        self._ring_i = 0
+        self._ring = ops.PinnedRing(self.HS + 2, slots=4)
         self.arena_f, self.arena_b = engine.ZeroArena(self.dev), engine.ZeroArena(self.dev)
         self.gflat = torch.zeros_like(model.flat)
         self.g = model.views_of(self.gflat)
@@ -177,18 +176,11 @@ class GraphedPretrain:
         m = self.model
         self.src.copy_(source, non_blocking=True)
         if self.phase == 1:
-            sl = self._ring[self._ring_i]
-            self._ring_i = (self._ring_i + 1) % len(self._ring)
-            if sl["ev"] is not None:
-                sl["ev"].synchronize()
             list_c = list(range(self.HS))
             random.shuffle(list_c)                                                             # GPTST.py:357-358
             ada, rnd = m.adaptive_counts(self.M, epoch)
-            sl["h"].numpy()[:] = list_c + [ada, rnd]
-            self.ctrl.copy_(sl["h"], non_blocking=True)
-            if sl["ev"] is None:
-                sl["ev"] = torch.cuda.Event()
-            sl["ev"].record()
+            self._ring.next()[:] = list_c + [ada, rnd]
+            self._ring.send(self.ctrl)
         self.gen_id += 1
         self.busy = True
         self.gf.replay()

@@ -5,6 +5,7 @@ so they are hipGraph-capturable.  No CPU path exists here by design.
 """
 import contextlib
 import ctypes
+import math
 from typing import Any, NamedTuple
 
 import torch
@@ -1027,6 +1028,41 @@ def step_begin(z0, z1, src, base, noise=None, rng=None):
     _call("gptst_step_begin", _p(z0), z0.numel(), _p(z1), z1.numel() if z1 is not None else 0, _p(src), _p(tidx), B * T, N, lda, base,
           _p(noise), noise.numel() if noise is not None else 0, _p(rng))
     return tidx
+
+
+class PinnedRing:
+    """Per-step host scalars on their way into a device buffer: a ring of pinned records, each guarded by an event recorded behind its H2D copy.
+    Steppers never synchronise, so with a single pinned record the host could rewrite the scalars of step k+j (Adam bias corrections, class
+    order) before the DMA of step k has read them."""
+
+    def __init__(self, words, rows=None, slots=4, dtype=torch.int32):
+        """records of `words` elements, or of (rows, words)"""
+        self._host = [torch.zeros((words,) if rows is None else (rows, words), dtype=dtype).pin_memory() for _ in range(slots)]
+        self._np = [h.numpy() for h in self._host]             # written without a torch dispatch per element
+        self._ev = [None] * slots
+        self._i = -1
+
+    def next(self):
+        """-> the next record (numpy); waits, host side, until the copy that last used it has run"""
+        self._i = (self._i + 1) % len(self._host)
+        if self._ev[self._i] is not None:
+            self._ev[self._i].synchronize()
+        return self._np[self._i]
+
+    def send(self, dev):
+        """the record next() handed out -> the device buffer (asynchronous)"""
+        dev.copy_(self._host[self._i], non_blocking=True)
+        if self._ev[self._i] is None:
+            self._ev[self._i] = torch.cuda.Event()
+        self._ev[self._i].record()
+
+
+def adam_scalars(lr, tA, tB, b1, b2, eps, clip, kl, sum_loss):
+    """hyper[0..12] of gptst_clip_adam for optimiser step tA of the reconstruction path and tB of the KL path (0: never stepped).  kl: this step
+    carries the KL path; sum_loss: the gradient is that of the SUM loss, the optimiser divides path A by the kept-cell count."""
+    return (lr / (1 - b1 ** tA), math.sqrt(1 - b2 ** tA), lr / (1 - b1 ** tB) if tB else 0.0, math.sqrt(1 - b2 ** tB) if tB else 1.0,
+            b1, b2, eps, clip, 1.0 if kl else 0.0, 1.0 if sum_loss else 0.0, 1.0,
+            1 - b1, 1 - b2)          # as the host rounds them (torch passes python's 1 - beta): 1.f - 0.999f is 1.3e-5 low
 
 
 def clip_adam(p, g, m, v, nA, nB, hyper, stats, ws=None, stats_out=None, sws=None):

@@ -12,8 +12,6 @@ are skipped and keep no state, as in torch — the KL-path parameters before ``c
 MultiStepLR and friends work: the learning rate is read from ``param_groups`` every step.  Gradients that are not the model's flat views (a foreign
 backward) are gathered into a flat buffer first.
 """
-import math
-
 import torch
 
 from . import ops
@@ -38,8 +36,7 @@ class ClipAdam(torch.optim.Optimizer):
         self.stats = torch.zeros(8, device=dev)
         self.stats_out = torch.zeros(8, device=dev)
         self.hyper = torch.zeros(16, device=dev)
-        self._ring = [dict(h=torch.zeros(16).pin_memory(), ev=None) for _ in range(4)]
-        self._ring_i = 0
+        self._ring = ops.PinnedRing(16, slots=4, dtype=torch.float32)
         self.tA = self.tB = 0
         self._first_key = min((k for k, _ in model._named), key=lambda k: model._offs[k])      # first tensor of the reconstruction-path segment (offset 0)
         self._first = dict(model._named)[self._first_key]
@@ -77,16 +74,8 @@ class ClipAdam(torch.optim.Optimizer):
         if hasB:
             self.tB += 1
         tA, tB, lr = self.tA, self.tB, float(gr["lr"])
-        sl = self._ring[self._ring_i]
-        self._ring_i = (self._ring_i + 1) % len(self._ring)
-        if sl["ev"] is not None:
-            sl["ev"].synchronize()
-        sl["h"].numpy()[:13] = (lr / (1 - b1 ** tA), math.sqrt(1 - b2 ** tA), lr / (1 - b1 ** tB) if tB else 0.0, math.sqrt(1 - b2 ** tB) if tB else 1.0,
-                                b1, b2, gr["eps"], gr["max_grad_norm"], 1.0 if hasB else 0.0, 0.0, 1.0, 1 - b1, 1 - b2)
-        self.hyper.copy_(sl["h"], non_blocking=True)
-        if sl["ev"] is None:
-            sl["ev"] = torch.cuda.Event()
-        sl["ev"].record()
+        self._ring.next()[:13] = ops.adam_scalars(lr, tA, tB, b1, b2, gr["eps"], gr["max_grad_norm"], kl=hasB, sum_loss=False)
+        self._ring.send(self.hyper)
         mdl = self.model
         ops.clip_adam(mdl.flat, self._flat_grad(), self.m, self.v, mdl.nA, mdl.nB, self.hyper, self.stats, stats_out=self.stats_out)
         return loss

@@ -27,7 +27,7 @@ import threading
 import torch
 
 from . import engine, ops
-from .step import PretrainStep, U24
+from .step import PretrainStep
 
 
 def is_node_local(key):
@@ -228,6 +228,7 @@ class ShardedPretrainStep(PretrainStep):
     """One optimisation step of a rank that owns nodes [n0, n1) of N (node_ranges: shard widths may differ by one).  Unequal shards
     need models built with node_capacity = the widest shard, so that [flat gradient | statistics] has the same layout on every rank."""
     DETERMINISTIC_MODE = False      # the sharded step has never taken the bit-reproducible launch forms: GPTST_DETERMINISTIC is not read here
+    FORCED_MASK = False             # ... nor teacher-forced masks
 
     def __init__(self, model_local, args_local, n_global, group, scaler_mean, scaler_std, batch_size, seed=0, use_graph=None):
         """use_graph: None = capture the step in a hipGraph when the group's collectives are capturable (see the module docstring)."""
@@ -336,57 +337,32 @@ class ShardedPretrainStep(PretrainStep):
         """the fused form skips the classifier in the random-mask phase; the unfused form always runs it (GPTST_ALWAYS_GUIDE is not read here)"""
         return phase == 1 or not self.fused_tails
 
-    def _make_mask(self, phase, prob, label, pend):
-        """The selection over the GLOBAL cells, cut to this rank's node columns.  label: the guide's argmax labels of the local cells;
-        pend: the STHCNs' generation table (engine.gen_all(defer=True)), launched by the mask call — inside its launch where that is the cooperative one"""
-        a, base = self.args, self.base
-        Mg = self.B * self.T * self.Ng
-        ws = self._mask_ws()
-        if phase == 0:
-            mask_g = ops.mask_random(self.noise_g, int(Mg * base * a.mask_ratio), ws=ws, u24=U24, jobs=pend)
-        else:
-            label_g = self._gather_labels(label, self.B)
-            mask_g = ops.mask_adaptive(label_g, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a_g, self.noise_r_g,
-                                       a.ada_type == "all", base, ws=ws, u24=U24, jobs=pend)[2]  # (class histogram of the gathered labels: taken inside)
-        self.last_mask_global = mask_g
-        return self._cols(mask_g, base)
+    def _mask_labels(self, label):
+        """the guide's argmax labels of the local cells -> of the GLOBAL cells (the class histogram is taken from the gathered labels)"""
+        return self._gather_labels(label, self.B)
+
+    def _mask_cut(self, mask):
+        """the selection over the GLOBAL cells, cut to this rank's node columns"""
+        self.last_mask_global = mask
+        return self._cols(mask, self.base)
 
     def _fold_stats(self, sws):
         """always into the gradient buffer's tail, which the all-reduce moves.  Unfused (sws None): a zero row — only the fold's other job, stats[5] <-
         this rank's hand-off expiries, so that every rank skips the update and re-runs the step together, as on the fused path"""
         ops.stats_fold(sws if sws is not None else self.arena.zeros(1, 4), self.stats)
 
-    def step(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None):
-        """source: this rank's (B,T,Nl,base+2) slice; injected noise (tests) covers the GLOBAL (B,T,N[,base]) cells."""
-        a = self.args
-        phase = 0 if epoch <= a.change_epoch else 1
-        if source is not self.src:
-            self.src.copy_(source, non_blocking=True)
-        inject = noise is not None or noise_a is not None
-        if inject:
-            if phase == 0:
-                self.noise_g.copy_(noise.reshape(-1))
-            else:
-                self.noise_a_g.copy_(noise_a.reshape(-1)); self.noise_r_g.copy_(noise_r.reshape(-1))
-        self._host_prepare(phase, epoch, list_c)
-        # (ADVICE r05) what losses() needs to repeat this step after a lost hand-off: the base class's re-run calls step(src, epoch, list_c=...) — this one
-        self._g_last = None
-        self._last_call = (epoch, self._filled_list_c, self.rank_weight) if not inject else None
-        self._unseen.append(phase)
-        if len(self._unseen) > 4096:
-            del self._unseen[:2048]
-        if not self.shard_graph:
-            self.inject_noise = inject
-            self._body(phase)
-            return
-        key = (phase, inject, False)            # one hipGraph per (phase, injected noise), kernels and collectives: the base class's capture
-        if key not in self.graphs:
-            self._capture(key)
-        self.graphs[key][0].replay()
+    def _graphed(self):
+        """one hipGraph per (phase, injected noise), kernels and collectives: the base class's capture"""
+        return self.shard_graph
 
-    def _fill(self, sl, phase, epoch, list_c):
-        super()._fill(sl, phase, epoch, list_c)
-        sl["hyper"][13] = 1.0 if self.group.world > 1 else 0.0     # the optimiser clips by the norm _after_backward leaves in stats[3]
+    def group_ok(self, epoch):
+        """a sharded stepper never runs a group as one graph"""
+        return False
+
+    def _fill(self, row, phase, epoch, list_c):
+        list_c = super()._fill(row, phase, epoch, list_c)
+        row[13:14].view("float32")[0] = 1.0 if self.group.world > 1 else 0.0     # the optimiser clips by the norm _after_backward leaves in stats[3]
+        return list_c
 
     def _after_backward(self, phase):
         # ---- gradients: replicated-compute parameters count once, node-local ones stay local, the rest is summed ----

@@ -6,7 +6,8 @@ statistics block whenever the caller asks.  Data-parallel: one process per GPU, 
 [flat gradient | loss statistics] between backward and the optimiser (dist.py).
 """
 import contextlib
-import math
+import dataclasses
+import itertools
 import os
 import random
 from typing import Any, NamedTuple
@@ -31,9 +32,25 @@ class Part1(NamedTuple):
     sv_g: Any
 
 
+@dataclasses.dataclass(eq=False)
+class Enqueued:
+    """One enqueued optimisation step, as the stepper's ledger keeps it until the host has read its statistics"""
+    phase: int
+    epoch: int
+    list_c: Any     # the class order the step ran with (None in the random-mask phase)
+    weight: float   # rank_weight of the step
+    src: Any        # device tensor that still holds the step's batch; None: the step cannot be repeated (injected noise, forced mask, buffer reused)
+    stats: Any      # device snapshot of the step's statistics; None: written over by a later step
+    replay: int     # shared by the steps of one graph replay
+    group: int      # shared by the steps of one step() / step_group() call
+    slot: Any       # j: sub-step j of a group (src, stats are the group's j-th buffers); None: a plain step (self.src, self.stats_out)
+    row: Any = None  # the statistics on the host, once read
+
+
 class PretrainStep:
-    RING = 8                                  # pinned host slots in flight (see __init__)
+    RING = 8                                  # pinned host slots in flight (ops.PinnedRing)
     DETERMINISTIC_MODE = True                 # the stepper sets the library's launch mode from self.deterministic (False: never touches it)
+    FORCED_MASK = True                        # step(forced_mask=) is served
 
     def __init__(self, model, args, scaler_mean, scaler_std, batch_size, use_graph=True, dp=None, seed=0, global_mask=True,
                  deterministic=None):
@@ -66,13 +83,9 @@ class PretrainStep:
         self.ctrl = self.hc[16:16 + self.HS + 2]
         self.rng_words = self.hc[16 + self.HS + 2:]                  # Philox key of the step's mask noise (step_begin)
         self.noise_seed = 1234567 + seed
-        # Per-step host scalars travel through a RING of pinned slots, each guarded by an event recorded behind its H2D copies:
-        # step() never synchronises, so with a single pinned buffer the host could rewrite the Adam bias corrections / class
-        # order of step k+j before the DMA of step k has read them (hundreds of steps are queued back to back by bench.py).
-        self._ring = [self._views(torch.zeros(16 + self.HS + 4, dtype=torch.int32).pin_memory()) for _ in range(self.RING)]
-        self._ring_i = 0
+        self._ring = ops.PinnedRing(self.hc.numel(), slots=self.RING)        # (hundreds of steps are queued back to back by bench.py)
         self.phase_kl = False                                        # phase of the last enqueued step (losses())
-        self._gK, self._g_last, self._group_failed = 0, None, False  # step_group(): group size set up, (K, phase) of the last group, capture refused
+        self._gK, self._group_failed = 0, False                      # step_group(): group size set up, capture refused
         self.stats_out = torch.zeros(8, device=self.dev)            # snapshot of stats after the step (graph output)
         self.mask_buf = torch.ones(M * self.base, device=self.dev)   # teacher-forced mask (parity runs)
         self.last_mask = None
@@ -82,7 +95,6 @@ class PretrainStep:
         self.rng = random.Random(seed)
         self.graphs = {}
         self._g_graphs = {}                  # step_group(): phase -> graph of K steps
-        self._g_fallback = None              # step_group() fell back to single steps: their statistics snapshots (losses_group())
         self._graph_comm_failed = False      # capturing the collectives failed once: they run between graph replays
         self._ctx_keep = []                  # part 1's tensors of every two-graph capture (inputs of its second graph)
         self._sws = None                     # fused loss statistics awaiting the optimiser's launch (_fold_stats)
@@ -96,9 +108,9 @@ class PretrainStep:
         self.safe_mode = False
         self.lost_steps = 0                  # steps re-run so far
         self.lost_batches = 0                # ... and steps that were skipped with a later one and could not be repeated (their batches were gone)
-        self._unseen = []                    # phase of every step enqueued since the host last read the statistics
-        self._last_call = None               # (epoch, list_c) of the last plain step()
-        self._g_list_cs = None               # class orders of the last group
+        self._ledger = []                    # Enqueued records: the last call's steps, then every step enqueued since the host last read the statistics
+        self._holder = {}                    # slot -> the record that last wrote that slot's buffers (_note)
+        self._ids = itertools.count()
         self.arena = engine.ZeroArena(self.dev)
         self.fused_tails = os.environ.get("GPTST_FUSED_TAILS", "1") == "1" and engine.fused_tails_ok(model.param_views(), self.C, self.base, self.HS)
         # ---- data parallel: masks over the GLOBAL batch (dist.py) ----
@@ -236,17 +248,30 @@ class PretrainStep:
         return phase == 1 or self.always_guide
 
     def _make_mask(self, phase, prob, label, pend):
-        """Hook: the visibility mask of this rank's cells.  label: the guide's argmax labels (rowdot's by-product, None without the guide);
-        pend: the deferred generation jobs, which the mask's launch carries"""
-        a, base, M = self.args, self.base, self.B * self.T * self.N
-        if self.gmask:
-            return self._global_mask(phase, jobs=pend)
+        """The visibility mask of this rank's cells.  label: the guide's argmax labels (rowdot's by-product, None without the guide);
+        pend: the deferred generation jobs, which the mask's launch carries.  The selection covers the cells of _noise_buffer(phase)."""
+        a = self.args
         if self.force_mask:
             return self.mask_buf
+        noise = self._noise_buffer(phase)                   # Philox / torch.rand noise: k * 2^-24
         if phase == 0:
-            return ops.mask_random(self.noise, int(M * base * a.mask_ratio), ws=self._mask_ws(), u24=U24, jobs=pend)       # Philox / torch.rand noise: k * 2^-24
-        return ops.mask_adaptive(label, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a, self.noise_r,       # (class histogram: taken inside)
-                                 a.ada_type == "all", base, ws=self._mask_ws(), u24=U24, jobs=pend)[2]
+            mask = ops.mask_random(noise, int(noise.numel() * a.mask_ratio), ws=self._mask_ws(), u24=U24, jobs=pend)
+        else:                                               # (class histogram: taken inside)
+            noise_a, noise_r = noise.chunk(2)
+            mask = ops.mask_adaptive(self._mask_labels(label), None, self.ctrl[:self.HS], self.ctrl[self.HS:], noise_a, noise_r,
+                                     a.ada_type == "all", self.base, ws=self._mask_ws(), u24=U24, jobs=pend)[2]
+        return self._mask_cut(mask)
+
+    def _mask_labels(self, label):
+        """Hook: the labels of the selection's cells (global masks: label_g was gathered by _exchange_labels())"""
+        return self.label_g if self.gmask else label
+
+    def _mask_cut(self, mask):
+        """Hook: the selection -> this rank's cells (global masks: its rows of the selection over the global batch, identical on every rank)"""
+        if not self.gmask:
+            return mask
+        self.last_mask_global = mask
+        return self.dp.rows_of(mask, self.B * self.T * self.N * self.base)
 
     def _fold_stats(self, sws):
         """Hook: the fused heads' per-workgroup loss statistics -> stats[0..2] (sws None: the unfused loss kernels summed into stats themselves)"""
@@ -283,20 +308,6 @@ class PretrainStep:
         """The selections' histogram scratch comes zeroed out of the step's arena (cleared by the step's first launch): no zeroing launch."""
         return self.arena.zeros(ops.mask_ws_floats())
 
-    def _global_mask(self, phase, jobs=None):
-        """Mask of this rank's rows cut out of the selection over the global batch (identical on every rank)."""
-        a, base, M = self.args, self.base, self.B * self.T * self.N
-        Mg = M * self.W
-        if self.force_mask:
-            return self.mask_buf
-        if phase == 0:
-            mask_g = ops.mask_random(self.noise_g, int(Mg * base * a.mask_ratio), ws=self._mask_ws(), u24=U24, jobs=jobs)
-        else:                                              # label_g was gathered by _exchange_labels(); class histogram taken inside
-            mask_g = ops.mask_adaptive(self.label_g, None, self.ctrl[:self.HS], self.ctrl[self.HS:], self.noise_a_g,
-                                       self.noise_r_g, a.ada_type == "all", base, ws=self._mask_ws(), u24=U24, jobs=jobs)[2]
-        self.last_mask_global = mask_g
-        return self.dp.rows_of(mask_g, M * base)
-
     def _exchange_labels(self):
         """Adaptive phase under DP: ONE all-gather of the int32 cluster labels (261 KB per 32-sample rank), between the two parts."""
         self.dp.gather_labels(self.label_l, out=self.label_g)
@@ -330,84 +341,69 @@ class PretrainStep:
             self._enqueue(phase)
 
     # ---- host side of one step -------------------------------------------------------------------------------------
-    def _views(self, hc):
-        """numpy views of one pinned host-scalar record (written without a torch dispatch per element)"""
-        HS = self.HS
-        n = hc.numpy()
-        return dict(hc=hc, hyper=n[:16].view("float32"), ctrl=n[16:16 + HS + 2], rng=n[16 + HS + 2:], ev=None)
+    def _phase(self, epoch):
+        return 0 if epoch <= self.args.change_epoch else 1
 
-    def _slot(self):
-        """Next pinned slot of the ring; waits (host side) until the copies that last used it have run."""
-        sl = self._ring[self._ring_i]
-        self._ring_i = (self._ring_i + 1) % self.RING
-        if sl["ev"] is not None:
-            sl["ev"].synchronize()
-        return sl
-
-    def _host_prepare(self, phase, epoch, list_c):
-        sl = self._slot()
-        self._fill(sl, phase, epoch, list_c)
-        self.hc.copy_(sl["hc"], non_blocking=True)
-        if sl["ev"] is None:
-            sl["ev"] = torch.cuda.Event()
-        sl["ev"].record()
-
-    def _fill(self, sl, phase, epoch, list_c):
-        """Advance the optimiser counters by one step and write that step's host scalars into the pinned views of `sl`."""
-        a = self.args
+    def _fill(self, row, phase, epoch, list_c):
+        """Advance the optimiser counters by one step and write that step's host scalars into `row` (numpy, one pinned record of ops.PinnedRing).
+        -> the class order the step runs with (None in the random-mask phase)"""
+        a, HS = self.args, self.HS
         self.tA += 1
         if phase == 1:
             self.tB += 1
         self.phase_kl = phase == 1
-        b1, b2 = 0.9, 0.999
-        tA, tB = self.tA, self.tB
-        sl["hyper"][11:13] = (1 - b1, 1 - b2)           # as the host rounds them (torch passes python's 1 - beta): 1.f - 0.999f is 1.3e-5 low
-        sl["hyper"][:11] = (self.lr / (1 - b1 ** tA), math.sqrt(1 - b2 ** tA),
-                            self.lr / (1 - b1 ** tB) if tB else 0.0, math.sqrt(1 - b2 ** tB) if tB else 1.0,
-                            b1, b2, 1e-8, float(a.max_grad_norm) if a.grad_norm else 0.0, 1.0 if phase == 1 else 0.0,
-                            1.0,          # the backward carries the gradient of the SUM loss: the optimiser divides path A by the (global) kept count
-                            1.0)
-        sl["rng"][:2] = (self.noise_seed & 0x7FFFFFFF, tA & 0x7FFFFFFF)                      # same key on every rank: same global noise
-        if phase == 1:
-            if list_c is None:
-                list_c = list(range(self.HS))
-                self.rng.shuffle(list_c)                                   # GPTST.py:357-358
-            ada, rnd = self.model.adaptive_counts(self.B * self.T * self.N * (self.W if self.gmask else 1), epoch)
-            ada, rnd = self._budgets(ada, rnd, epoch)
-            sl["ctrl"][:] = [int(v) for v in list_c] + [int(ada), int(rnd)]
-        self._filled_list_c = [int(v) for v in list_c] if phase == 1 else None
+        tA = self.tA
+        # (sum loss: the backward carries the gradient of the SUM loss, the optimiser divides path A by the (global) kept count)
+        row[:13].view("float32")[:] = ops.adam_scalars(self.lr, tA, self.tB, 0.9, 0.999, 1e-8, float(a.max_grad_norm) if a.grad_norm else 0.0,
+                                                       kl=phase == 1, sum_loss=True)
+        row[16 + HS + 2:16 + HS + 4] = (self.noise_seed & 0x7FFFFFFF, tA & 0x7FFFFFFF)          # same key on every rank: same global noise
+        if phase == 0:
+            return None
+        if list_c is None:
+            list_c = list(range(HS))
+            self.rng.shuffle(list_c)                                   # GPTST.py:357-358
+        list_c = [int(v) for v in list_c]
+        ada, rnd = self.model.adaptive_counts(self.B * self.T * self.N * (self.W if self.gmask else 1), epoch)
+        ada, rnd = self._budgets(ada, rnd, epoch)
+        row[16:16 + HS + 2] = list_c + [int(ada), int(rnd)]
+        return list_c
 
     def _budgets(self, ada, rnd, epoch):
         """Hook: subclasses whose masks cover more cells than this rank's batch (node sharding) replace the budgets."""
         return ada, rnd
 
-    def step(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None, forced_mask=None):
-        """Enqueue one optimisation step on ``source`` (B,T,N,base+2).  Never synchronises.
+    def _graphed(self):
+        """Hook: does step() replay a captured graph?"""
+        return self.use_graph
+
+    def step(self, source, epoch, noise=None, noise_a=None, noise_r=None, list_c=None, forced_mask=None, _sub=None):
+        """Enqueue one optimisation step on ``source`` (B,T,N,base+2).  Never synchronises.  Injected noise (tests) covers the cells of the
+        selection: the GLOBAL batch with global masks, the GLOBAL nodes of a node shard.
         ``forced_mask`` (fp32, 1 = visible) teacher-forces the mask: used by loss-curve parity runs in the adaptive phase,
-        where an fp32-level argmax flip of the cluster classifier would otherwise change which cells are masked."""
-        phase = 0 if epoch <= self.args.change_epoch else 1
-        self._g_last = None
-        self._g_fallback = None
+        where an fp32-level argmax flip of the cluster classifier would otherwise change which cells are masked.
+        ``_sub`` = (group id, j): step_group() running its sub-step j as a single step — ``source`` is the group's j-th buffer."""
+        phase = self._phase(epoch)
+        forced = forced_mask is not None
+        if forced and not self.FORCED_MASK:
+            raise ValueError("%s does not teacher-force masks" % type(self).__name__)
         if source is not self.src:
             self.src.copy_(source, non_blocking=True)
         inject = noise is not None or noise_a is not None
-        if inject:                                      # with global masks the injected noise covers the GLOBAL batch
-            n0, na, nr = (self.noise_g, self.noise_a_g, self.noise_r_g) if self.gmask else (self.noise, self.noise_a, self.noise_r)
+        if inject:
+            buf = self._noise_buffer(phase)
             if phase == 0:
-                n0.copy_(noise.reshape(-1), non_blocking=True)
+                buf.copy_(noise.reshape(-1), non_blocking=True)
             else:
+                na, nr = buf.chunk(2)
                 na.copy_(noise_a.reshape(-1), non_blocking=True)
                 nr.copy_(noise_r.reshape(-1), non_blocking=True)
-        if forced_mask is not None:
+        if forced:
             self.mask_buf.copy_(forced_mask.reshape(-1), non_blocking=True)
-        self._host_prepare(phase, epoch, list_c)
-        self._last_call = (epoch, self._filled_list_c, self.rank_weight) if not inject and forced_mask is None else None
-        self._unseen.append(phase)                      # steps enqueued since the host last looked at the statistics (losses())
-        if len(self._unseen) > 4096:
-            del self._unseen[:2048]
-        key = (phase, inject, forced_mask is not None)
-        if not self.use_graph:
-            self.inject_noise, self.force_mask = inject, forced_mask is not None
+        list_c = self._fill(self._ring.next(), phase, epoch, list_c)
+        self._ring.send(self.hc)
+        key = (phase, inject, forced)
+        if not self._graphed():
+            self.inject_noise, self.force_mask = inject, forced
             self._body(phase)
         else:
             if key not in self.graphs:
@@ -420,6 +416,31 @@ class PretrainStep:
         if self.dp is not None and not self._dp_in_graph():
             self._allreduce(self.gbuf)
             self._optim()
+        group, j = _sub if _sub is not None else (next(self._ids), None)
+        rec = Enqueued(phase, epoch, list_c, self.rank_weight, self.src, self.stats_out, next(self._ids), group, j)
+        if inject or forced:
+            rec.src = None
+        elif j is not None:                             # the group's own buffers: later plain steps do not write over them
+            rec.src, rec.stats = source, self._g_rows[j]
+            rec.stats.copy_(self.stats_out)
+        self._note(rec, *{None, j})
+
+    def _note(self, rec, *slots):
+        """Append to the ledger.  slots: whose buffers this enqueue wrote over (None: self.src / self.stats_out, j: the group's j-th) — the
+        records that pointed at them can no longer be read or repeated."""
+        for s in slots:
+            old = self._holder.get(s)
+            if old is not None and old.slot == s:
+                old.src = old.stats = None
+            self._holder[s] = rec
+        self._ledger.append(rec)
+        if len(self._ledger) > 4096:                    # (nobody looks: a lost hand-off is then undone for the steps still on record)
+            del self._ledger[:2048]
+
+    @property
+    def last_replay_steps(self):
+        """number of steps the most recent graph replay (eager: enqueue) ran"""
+        return sum(1 for r in self._ledger if r.replay == self._ledger[-1].replay)
 
     def _capture(self, key):
         """Capture the step of `key` = (phase, injected noise, forced mask).  If capturing the collectives of a data-parallel step fails
@@ -471,7 +492,7 @@ class PretrainStep:
     # (BasicTrainer.py:72-103) unrolled K times.  Results are those of K step() calls (tests/test_gpu_step.py).
     def group_ok(self, epoch):
         """A group runs as one graph when the whole step is one graph (no host-side collective inside the step)."""
-        phase = 0 if epoch <= self.args.change_epoch else 1
+        phase = self._phase(epoch)
         if self._group_failed:
             return False
         return self.use_graph and (self.dp is None or self._dp_in_graph()) and not (self._needs_exchange(phase) and not self._dp_in_graph())
@@ -484,11 +505,8 @@ class PretrainStep:
         self._g_hc = torch.zeros(K, W, dtype=torch.int32, device=self.dev)
         self._g_src = [torch.zeros_like(self.src) for _ in range(K)]
         self._g_stats = torch.zeros(K, 8, device=self.dev)
-        self._g_ring = []
-        for _ in range(self.RING):
-            hc = torch.zeros(K, W, dtype=torch.int32).pin_memory()
-            self._g_ring.append(dict(hc=hc, rows=[self._views(hc[j]) for j in range(K)], ev=None))
-        self._g_ring_i = 0
+        self._g_rows = list(self._g_stats.unbind(0))
+        self._g_ring = ops.PinnedRing(W, rows=K, slots=self.RING)
         self._g_graphs = {}
 
     def group_sources(self, K):
@@ -500,26 +518,25 @@ class PretrainStep:
         """Point the per-step buffers of the body at sub-step j of the group (host scalars, source, statistics snapshot)."""
         HS = self.HS
         r = self._g_hc[j]
-        self.src, self.stats_out = self._g_src[j], self._g_stats[j]
+        self.src, self.stats_out = self._g_src[j], self._g_rows[j]
         self.hyper, self.ctrl, self.rng_words = r[:16].view(torch.float32), r[16:16 + HS + 2], r[16 + HS + 2:]
 
     def step_group(self, sources, epoch, list_cs=None):
         """Enqueue len(sources) consecutive optimisation steps of the same epoch.  Never synchronises.  Falls back to a loop over step()
-        where a step is not one graph (eager mode, host-side collectives).  losses_group() returns the K loss triples."""
-        K = len(sources)
-        if K == 1 or not self.group_ok(epoch):
-            snaps = []                                  # every step's statistics (device copies, no sync): losses_group() returns K triples here too
-            for j, src in enumerate(sources):
-                self.step(src, epoch, list_c=None if list_cs is None else list_cs[j])
-                snaps.append((self.stats_out.clone(), bool(self.tB and self.phase_kl), src, self._filled_list_c, epoch))
-            self._g_last = None
-            self._g_fallback = snaps
-            return
-        phase = 0 if epoch <= self.args.change_epoch else 1
-        self._group_init(K)
+        where a step is not one graph (eager mode, host-side collectives).  losses_group() returns the K loss triples.  Either way the
+        batches are kept in the group's own buffers (group_sources) until a later group reuses them: the caller's tensors are free at once."""
+        K, phase, group = len(sources), self._phase(epoch), next(self._ids)
+        list_cs = [None] * K if list_cs is None else list_cs
+        grouped = K > 1 and self.group_ok(epoch)
+        if grouped or K > self._gK:
+            self._group_init(K)
         for j, src in enumerate(sources):
             if src is not self._g_src[j]:
                 self._g_src[j].copy_(src, non_blocking=True)
+        if not grouped:
+            for j in range(K):                          # one replay per step, the same kind of record
+                self.step(self._g_src[j], epoch, list_c=list_cs[j], _sub=(group, j))
+            return
         if phase not in self._g_graphs:
             # capture BEFORE any per-step state is advanced: if the runtime cannot record this group (e.g. collectives of K steps in one
             # graph), every rank fails alike, the group falls back to K single steps and later groups do not try again
@@ -542,30 +559,22 @@ class PretrainStep:
                     self._g_graphs.pop(phase, None)
             if self._group_failed:
                 return self.step_group(sources, epoch, list_cs)
-        sl = self._g_ring[self._g_ring_i]
-        self._g_ring_i = (self._g_ring_i + 1) % self.RING
-        if sl["ev"] is not None:
-            sl["ev"].synchronize()
-        self._g_list_cs = []
+        rows, replay = self._g_ring.next(), next(self._ids)
         for j in range(K):
-            self._fill(sl["rows"][j], phase, epoch, None if list_cs is None else list_cs[j])
-            self._g_list_cs.append(self._filled_list_c)
-        self._g_epoch = epoch
-        self._g_hc.copy_(sl["hc"], non_blocking=True)
-        if sl["ev"] is None:
-            sl["ev"] = torch.cuda.Event()
-        sl["ev"].record()
+            self._note(Enqueued(phase, epoch, self._fill(rows[j], phase, epoch, list_cs[j]), self.rank_weight, self._g_src[j], self._g_rows[j],
+                                replay, group, j), j)
+        self._g_ring.send(self._g_hc)
         self._g_graphs[phase].replay()
-        self._g_last = (K, phase)
 
     def _capture_group(self, phase, K, epoch):
         self.inject_noise, self.force_mask = False, False
         keep = (self.model.flat.clone(), self.m.clone(), self.v.clone())
         # the warm-up runs need plausible host scalars in the device table: fill it as the first group would, then put the counters back
         st = (self.tA, self.tB, self.phase_kl, self.rng.getstate())
+        rows = self._g_ring.next()
         for j in range(K):
-            self._fill(self._g_ring[0]["rows"][j], phase, epoch, None)
-        self._g_hc.copy_(self._g_ring[0]["hc"])
+            self._fill(rows[j], phase, epoch, None)
+        self._g_ring.send(self._g_hc)
         torch.cuda.synchronize()
         self.tA, self.tB, self.phase_kl = st[:3]
         self.rng.setstate(st[3])
@@ -601,49 +610,57 @@ class PretrainStep:
         self._g_graphs[phase] = g
 
     def losses_group(self):
-        """[(loss, loss_flow, loss_s)] of the steps of the last step_group() — synchronises."""
-        if self._g_last is None:
-            if self._g_fallback:                        # step_group() fell back to single steps: one triple per step, as the grouped path
-                snaps, self._g_fallback = self._g_fallback, None
-                rows = [(st.cpu(), kl) for st, kl, _, _, _ in snaps]
-                out = [self._stats_row(st, kl) for st, kl in rows]
-                lost = [j for j, (st, _) in enumerate(rows) if float(st[5]) > 0]
-                del self._unseen[:]
-                if lost:                                # a hand-off expired in step j0: its update and every later one were skipped (ADVICE r05) —
-                    j0 = lost[0]                        # take them back and re-run them, as the grouped path does
-                    self._enter_safe_mode(len(snaps) - j0, sum(1 for _, kl, _, _, _ in snaps[j0:] if kl))
-                    for j in range(j0, len(snaps)):
-                        _, kl, src, lc, ep = snaps[j]
-                        self.step(src, ep, list_c=lc)
-                        out[j] = self._stats_row(self.stats_out.cpu(), kl)
-                    del self._unseen[:]
-                return out
-            return [self.losses()]
-        K, phase = self._g_last
-        st = self._g_stats.cpu()
-        del self._unseen[:]
-        rerun = {}
-        if float(st[:, 5].max()) > 0:           # a hand-off expired in sub-step j0: its update and every later one were skipped
-            j0 = int((st[:, 5] > 0).float().argmax())
-            # (groups enqueued BEFORE this one without a look in between — bench loops — were skipped too if the expiry is older: the device's count of
-            #  skipped updates says how many; their batches are gone, their optimiser steps are taken back with this group's)
-            extra = max(0, int(st[K - 1, 6]) - (K - j0))
-            if extra:
+        """[(loss, loss_flow, loss_s)] of the steps of the last step_group() (of the last step(): one triple) — synchronises."""
+        self._look()
+        if not self._ledger:                            # nothing enqueued since the stepper was built / loaded
+            return [self._stats_row(self.stats_out.cpu(), bool(self.tB and self.phase_kl))]
+        return [self._stats_row(r.row, r.phase == 1) for r in self._ledger]
+
+    def _read(self, recs):
+        """statistics of these records -> host: one copy per buffer (a group's table travels whole)"""
+        host = {}
+        for r in recs:
+            if r.stats is not None:
+                buf = r.stats if r.slot is None else r.stats._base
+                if id(buf) not in host:
+                    host[id(buf)] = buf.cpu()
+                r.row = host[id(buf)] if r.slot is None else host[id(buf)][r.slot]
+
+    def _look(self):
+        """Read the statistics of every step enqueued since the last look, undo a lost hand-off (the one rule of DESIGN.md §15:
+        however the steps were enqueued) and keep the last call's records for losses() / losses_group()."""
+        led = self._ledger
+        new = [r for r in led if r.row is None]         # (they trail the records read before)
+        if not new:
+            return
+        self._read(new)
+        first = next((i for i, r in enumerate(new) if r.row is not None and float(r.row[5]) > 0), None)
+        if first is not None:
+            # A hand-off expired in that step: the guard skipped its update and EVERY later one while the record was up.  The device counts them
+            # (row[6]) — steps whose statistics were written over since (bench loops) included, as far as the ledger still knows them.
+            n = min(max(len(new) - first, int(new[-1].row[6])), len(new))
+            if new[-1].src is None:
+                raise RuntimeError("an in-launch hand-off expired in a step with injected mask inputs: call _enter_safe_mode() and repeat the step")
+            skipped = new[-n:]
+            del led[-n:]
+            self._enter_safe_mode(n, sum(r.phase for r in skipped))
+            again = [r for r in skipped if r.src is not None]
+            if len(again) < n:
                 import sys
-                self.lost_batches += extra
-                print("gpt-st_amd: %d step(s) of earlier groups were skipped too and cannot be repeated (their batches are gone): the optimiser counters "
-                      "were taken back, the batches were not trained on" % extra, file=sys.stderr)
-            self._enter_safe_mode(K - j0 + extra, (K - j0 + extra) if phase == 1 else 0)
-            srcs, lcs, epoch = [t.clone() for t in self._g_src[j0:]], self._g_list_cs[j0:], self._g_epoch
-            for j, (src, lc) in enumerate(zip(srcs, lcs)):
-                self.step(src, epoch, list_c=lc)
-                rerun[j0 + j] = self._stats_row(self.stats_out.cpu(), phase == 1)
-            del self._unseen[:]
-            self._g_last = (K, phase)            # (step() cleared it: the group's triples stay readable)
-        out = []
-        for j in range(K):
-            out.append(rerun[j] if j in rerun else self._stats_row(st[j], phase == 1))
-        return out
+                self.lost_batches += n - len(again)
+                print("gpt-st_amd: %d step(s) enqueued before the last one were skipped with it and cannot be repeated (their batches are gone): "
+                      "the optimiser counters were taken back, the batches were not trained on" % (n - len(again)), file=sys.stderr)
+            # (a plain step's batch lies in self.src, which every re-run writes: kept aside when it is not the only one)
+            srcs = [r.src.clone() if r.src is self.src and len(again) > 1 else r.src for r in again]
+            keep_w = self.rank_weight
+            try:
+                for r, src in zip(again, srcs):         # each the same weighted step (a padding rank of a tail round re-runs as padding)
+                    self.rank_weight = r.weight
+                    self.step(src, r.epoch, list_c=r.list_c, _sub=None if r.slot is None else (r.group, r.slot))
+            finally:
+                self.rank_weight = keep_w
+            self._read(led[-len(again):])
+        led[:] = [r for r in led if r.group == led[-1].group]
 
     @staticmethod
     def _stats_row(st, kl):
@@ -671,46 +688,12 @@ class PretrainStep:
     # ---- results ---------------------------------------------------------------------------------------------------
     def losses(self):
         """(loss, loss_flow, loss_s) of the last step — synchronises (reference BasicTrainer.py:98-103 does so every step)."""
-        if self._g_last is not None:
-            return self.losses_group()[-1]
-        st = self.stats_out.cpu()
-        unseen, self._unseen = self._unseen, []
-        if float(st[5]) > 0:                     # the update of this step was skipped (a hand-off expired): re-run it from the untouched weights
-            if self._last_call is None:
-                raise RuntimeError("an in-launch hand-off expired in a step with injected mask inputs: call _enter_safe_mode() and repeat the step")
-            # The guard skips EVERY update while the record is up, and the host may have enqueued several steps since it last looked (bench loops): the
-            # device counts them (stats_out[6]).  All of them are taken back; only the last one can be repeated — the earlier batches are gone.
-            nskip = max(1, min(int(st[6]), len(unseen))) if unseen else 1
-            epoch, lc, weight = self._last_call
-            self._enter_safe_mode(nskip, sum(unseen[-nskip:]) if unseen else (1 if self.phase_kl else 0))
-            if nskip > 1:
-                import sys
-                self.lost_batches += nskip - 1
-                print("gpt-st_amd: %d step(s) enqueued before the last one were skipped with it and cannot be repeated (their batches are gone): "
-                      "the optimiser counters were taken back, the batches were not trained on" % (nskip - 1), file=sys.stderr)
-            keep_w, self.rank_weight = self.rank_weight, weight          # the same weighted step (a padding rank of a tail round re-runs as padding)
-            try:
-                self.step(self.src, epoch, list_c=lc)
-            finally:
-                self.rank_weight = keep_w
-            st = self.stats_out.cpu()
-            del self._unseen[:]
-        return self._stats_row(st, bool(self.tB and self.phase_kl))
+        return self.losses_group()[-1]
 
     # ---- the run's state (checkpoint.py) -------------------------------------------------------------------------------------------
     # What a step sequence depends on besides its batches: weights, Adam moments, the two step counts (bias corrections AND, with noise_seed, the
     # Philox key of the mask noise), the learning rate and the class-order stream.  Moments are stored by parameter name with their true shape,
     # never as the flat buffer: the file does not know about segment order, alignment, node_capacity or ranks.
-    def _settle(self):
-        """Read the statistics of every step still in flight, as losses() / losses_group() do: an update skipped after a lost hand-off is re-run
-        and tA / tB agree with the device before they are written down."""
-        if not self._unseen:                             # every enqueued step has been looked at
-            return
-        if self._g_last is not None or self._g_fallback:
-            self.losses_group()
-        else:
-            self.losses()
-
     def _to_global(self, named):
         """Hook: {key: this rank's device tensor} -> {key: GLOBAL tensor on the CPU} (node shards gather over their group)"""
         return {k: v.detach().cpu().clone() for k, v in named.items()}
@@ -721,7 +704,7 @@ class PretrainStep:
 
     def state_dict(self):
         """The `model`, `optimizer` and `rng` sections of a checkpoint (checkpoint.py) — synchronises.  Collective where the stepper is."""
-        self._settle()
+        self._look()
         mdl = self.model
         order = {k: i for i, k in enumerate(mdl.param_keys)}
         m, v = ({k: t for k, t in sorted(mdl.views_of(buf).items(), key=lambda kv: order[kv[0]])} for buf in (self.m, self.v))
@@ -748,7 +731,7 @@ class PretrainStep:
         mdl, opt = self.model, sd["optimizer"]
         images = [self._stage_flat(self._to_local(named), what)
                   for named, what in ((sd["model"], "weights"), (opt["exp_avg"], "exp_avg"), (opt["exp_avg_sq"], "exp_avg_sq"))]
-        self._settle()                                   # nothing of this stepper's is in flight when its buffers change
+        self._look()                                   # nothing of this stepper's is in flight when its buffers change
         for dst, img in zip((mdl.flat, self.m, self.v), images):
             dst.copy_(img)
         for k, b in mdl.named_buffers():
@@ -756,5 +739,5 @@ class PretrainStep:
         self.tA, self.tB, self.lr = int(opt["step"]), int(opt["step_kl"]), float(opt["lr"])
         self.noise_seed = int(sd["rng"]["noise_seed"])
         self.rng.setstate(rng_state(sd["rng"]["class_order"]))
-        self._unseen, self._last_call, self._g_last, self._g_fallback, self._g_list_cs = [], None, None, None, None
+        del self._ledger[:]
         self.lost_steps = self.lost_batches = 0

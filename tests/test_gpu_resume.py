@@ -72,7 +72,7 @@ def test_group_replay_after_a_resume_lines_up_with_single_steps():
     st.load_state_dict(sd)
     assert st.group_ok(3)
     st.step_group(U.batches(N1, 9)[5:], 3)
-    assert st._g_last == (4, 1), "the four steps did not run as one replay"
+    assert st.last_replay_steps == 4, "the four steps did not run as one replay"
     triples = st.losses_group()
     assert triples == [s["loss"] for s in run_a[5:]], (triples, [s["loss"] for s in run_a[5:]])
     U.assert_same_run(U.snapshot(st), run_a[8], "after the group")

@@ -460,6 +460,80 @@ def test_lost_handoff_with_several_steps_enqueued_before_the_host_looks():
         lib.call("gptst_handoff_reset")
 
 
+def _handoff_case(seed):
+    """shape and setup of the lost-hand-off tests: B=4, T=12, N=20, base 1, deterministic -> (fresh, batches, class orders)"""
+    from gptst_amd.model import GPTST_Model
+    from gptst_amd.step import PretrainStep
+    args = _args()
+    sd = O.init_state_dict(args, 2)
+
+    def fresh(group_fails=False):
+        model = GPTST_Model(args); model.load_state_dict(sd); model = model.to(DEV)
+        st = PretrainStep(model, args, synth.SCALER_MEAN, synth.SCALER_STD, batch_size=4, use_graph=True, deterministic=True)
+        st._group_failed = group_fails
+        return model, st
+    return fresh, [synth.make_batch(4, 12, 20, 1, seed=seed + i).to(DEV) for i in range(10)], [synth.class_order(5, 60 + i) for i in range(10)]
+
+
+def _assert_same_state(got, want):
+    (m1, s1, l1), (m0, s0, l0) = got, want
+    assert l1 == l0, (l1, l0)
+    assert torch.equal(m1.flat, m0.flat) and torch.equal(s1.m, s0.m) and torch.equal(s1.v, s0.v)
+    assert (s1.tA, s1.tB) == (s0.tA, s0.tB)
+
+
+def test_lost_handoff_in_fallen_back_groups_enqueued_before_one_look():
+    """Groups that run as single steps, SEVERAL of them before one look: group A (2 steps) is seen, the expiry goes on record, groups B and C
+    (4 steps each) are enqueued, then ONE losses_group().  All eight updates were skipped: eight optimiser steps are taken back (Adam's bias
+    corrections and the Philox step key follow the device again), C is repeated from the stepper's own buffers, B's batches are gone — the
+    state of a run that stepped on A and then on C.
+    (Before the ledger the fallback branch took back C's four steps only: tA = tB = 10, and every later step ran with the wrong bias corrections
+    and mask noise.)"""
+    from gptst_amd import _C
+    fresh, srcs, orders = _handoff_case(960)
+    A, B_, C = slice(0, 2), slice(2, 6), slice(6, 10)
+    lib = _C.lib()
+    try:
+        m0, s0 = fresh(group_fails=True)
+        s0.step_group(srcs[A], 5, list_cs=orders[A]); s0.losses_group()
+        s0.step_group(srcs[C], 5, list_cs=orders[C]); l0 = s0.losses_group()
+        m1, s1 = fresh(group_fails=True)
+        s1.step_group(srcs[A], 5, list_cs=orders[A]); s1.losses_group()
+        torch.cuda.synchronize()
+        lib.call("gptst_handoff_inject", 1)
+        s1.step_group(srcs[B_], 5, list_cs=orders[B_])
+        s1.step_group(srcs[C], 5, list_cs=orders[C])
+        l1 = s1.losses_group()
+        assert s1.safe_mode and s1.lost_steps == 8 and s1.lost_batches == 4 and (s1.tA, s1.tB) == (6, 6)
+        assert len(l1) == 4
+        _assert_same_state((m1, s1, l1), (m0, s0, l0))
+    finally:
+        lib.call("gptst_handoff_reset")
+
+
+def test_lost_handoff_in_a_fallen_back_group_whose_caller_reuses_its_tensors():
+    """step_group() promises that the caller's tensors are free once it returns — also when the group runs as single steps: the batches are
+    repeated from the stepper's own buffers, not from tensors the caller has overwritten (stream-ordered behind the steps) in the meantime."""
+    from gptst_amd import _C
+    fresh, srcs, orders = _handoff_case(980)
+    lib = _C.lib()
+    try:
+        m0, s0 = fresh(group_fails=True)
+        s0.step_group(srcs[:4], 5, list_cs=orders[:4]); l0 = s0.losses_group()
+        m1, s1 = fresh(group_fails=True)
+        mine = [t.clone() for t in srcs[:4]]
+        torch.cuda.synchronize()
+        lib.call("gptst_handoff_inject", 1)
+        s1.step_group(mine, 5, list_cs=orders[:4])
+        for t in mine:
+            t.zero_()
+        l1 = s1.losses_group()
+        assert s1.safe_mode and s1.lost_steps == 4 and s1.lost_batches == 0
+        _assert_same_state((m1, s1, l1), (m0, s0, l0))
+    finally:
+        lib.call("gptst_handoff_reset")
+
+
 def test_step_group_falls_back_to_single_steps_when_the_capture_fails(monkeypatch):
     """A runtime that cannot record K steps in one graph (e.g. collectives) raises at capture time: the group then runs as K single steps —
     counters not advanced twice, later groups do not retry — and gives the results of K step() calls."""
