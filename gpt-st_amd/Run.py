@@ -135,7 +135,8 @@ def main_eval(args, dev):
          else graph.synthetic_adjacency(args.num_nodes, seed=args.seed))
     ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                          drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)
-    model = EnhanceFrontEnd(args, predictor=STGCN(ap, dev, args.hidden_dim, args.output_dim), finetune_encoder=bool(args.finetune_encoder)).to(dev)
+    model = EnhanceFrontEnd(args, predictor=STGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stgcn_backend)),
+                            finetune_encoder=bool(args.finetune_encoder)).to(dev)
     ckpt = args.log_dir + str(args.load_pretrain_path)                           # model/Model.py:92 (plain concatenation: '/GPTST_ada.pth')
     if os.path.exists(ckpt):
         model.load_pretrained_model(ckpt)                                        # model/Model.py:91-94

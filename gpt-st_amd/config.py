@@ -72,6 +72,8 @@ def parse_args(device, argv=None):
     # not reference options: -mode eval trains the pretrained encoder too (enhance.EnhanceFrontEnd), at lr_init * encoder_lr_scale
     ap.add_argument("-finetune_encoder", default=FINETUNE_DEFAULTS["finetune_encoder"], type=_EVAL)
     ap.add_argument("-encoder_lr_scale", default=FINETUNE_DEFAULTS["encoder_lr_scale"], type=float)
+    # not a reference option: what runs the STGCN predictor of -mode eval: the torch modules or the HIP kernels (predictors/stgcn_hip.py)
+    ap.add_argument("-stgcn_backend", default=FINETUNE_DEFAULTS["stgcn_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -83,7 +85,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
-FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0)
+FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):

@@ -1109,3 +1109,90 @@ def metrics_report(sums_t, sums_tn):
     per_t = rows_of(st, sn)
     avg = rows_of(st.sum(0), sn.sum(0))
     return torch.cat([per_t, avg[None]], 0)
+
+
+# ---- the downstream STGCN predictor (csrc/stgcn.hip) -------------------------------------------------------------------
+ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_GLU = 0, 1, 2, 3
+
+
+def _dts(taps):
+    assert 1 <= len(taps) <= 4
+    return tuple(int(t) for t in taps) + (0,) * (4 - len(taps))
+
+
+def stgcn_tapgemm(X, W, bias, taps, act, T, N, res=None, res_w=0, keep=False):
+    """Y (rows, co) = act(sum_j X[row + taps[j] N] W_j + bias + res[:, :res_w]); W (co | 2 co (GLU), len(taps) * ci), tap-major columns.
+    keep (GLU): -> (Y, S = sigmoid(Q), A = P + bias + res), what the backward needs."""
+    _chk(X, W, bias, res)
+    rows, ci = X.shape
+    co = W.shape[0] // 2 if act == ACT_GLU else W.shape[0]
+    assert W.shape[1] == len(taps) * ci
+    Y = torch.empty(rows, co, device=X.device, dtype=torch.float32)
+    S, A = (torch.empty_like(Y), torch.empty_like(Y)) if keep else (None, None)
+    _call("gptst_stgcn_tapgemm", _p(X), ci, ci, len(taps), *_dts(taps), _p(W), _p(bias), _p(res), res.shape[1] if res is not None else 0, res_w,
+          _p(Y), co, _p(S), _p(A), act, rows, T, N, tag="ci%d co%d k%d act%d" % (ci, co, len(taps), act), nbytes=_nb(X, W, Y, S, A))
+    return (Y, S, A) if keep else Y
+
+
+def stgcn_gate_bwd(dOut, act, out=None, S=None, A=None):
+    """dPre (rows, co | 2 co (GLU)) of a tap GEMM's epilogue from dOut and the kept tensors"""
+    _chk(dOut, out, S, A)
+    rows, co = dOut.shape
+    dPre = torch.empty(rows, 2 * co if act == ACT_GLU else co, device=dOut.device, dtype=torch.float32)
+    _call("gptst_stgcn_gate_bwd", _p(dOut), _p(out), _p(S), _p(A), _p(dPre), act, rows, co, tag="act%d co%d" % (act, co), nbytes=_nb(dOut, out, S, A, dPre))
+    return dPre
+
+
+def stgcn_wgrad(D, X, taps, T, N, want_bias=True):
+    """-> (dW (cw, len(taps) * ci) = D^T X_shift, db (cw) = column sums of D): row-split partials summed in a fixed order"""
+    _chk(D, X)
+    rows, cw = D.shape
+    ci = X.shape[1]
+    K = len(taps) * ci
+    ns = _C.lib().value("gptst_stgcn_wgrad_nsplit", rows, cw, K)
+    part = torch.empty(ns, cw, K, device=D.device, dtype=torch.float32)
+    bpart = torch.empty(ns, cw, device=D.device, dtype=torch.float32) if want_bias else None
+    _call("gptst_stgcn_wgrad", _p(D), cw, _p(X), ci, ci, len(taps), *_dts(taps), _p(part), _p(bpart), ns, rows, T, N,
+          tag="cw%d ci%d k%d" % (cw, ci, len(taps)), nbytes=_nb(D, X, part))
+    return part.sum(0), (bpart.sum(0) if want_bias else None)
+
+
+def stgcn_nodemix(Lp, In, N, c, reduce, res=None):
+    """Lp (ks, Np, Np) zero-padded; reduce False: In (rows, c) -> (rows, ks c) = [L_k In]_k;  True: In (rows, ks c) -> (rows, c) = sum_k L_k In_k + res"""
+    _chk(Lp, In, res)
+    ks, Np = Lp.shape[0], Lp.shape[1]
+    rows = In.shape[0]
+    assert In.shape[1] == (ks * c if reduce else c) and rows % N == 0
+    Out = torch.empty(rows, c if reduce else ks * c, device=In.device, dtype=torch.float32)
+    _call("gptst_stgcn_nodemix", _p(Lp), Np, ks, _p(In), _p(Out), _p(res), c, int(reduce), rows // N, N, tag="c%d r%d" % (c, int(reduce)),
+          nbytes=_nb(In, Out, res))
+    return Out
+
+
+def stgcn_ln_fwd(X, gamma, beta, units, eps, keep=True):
+    """LayerNorm over each unit's M = X.numel() / units values -> (Y, mean, rstd) (mean, rstd None when not kept)"""
+    _chk(X, gamma, beta)
+    M = X.numel() // units
+    Y = torch.empty_like(X)
+    mean, rstd = (torch.empty(units, device=X.device, dtype=torch.float32) for _ in range(2)) if keep else (None, None)
+    _call("gptst_stgcn_ln_fwd", _p(X), _p(gamma), _p(beta), _p(Y), _p(mean), _p(rstd), units, M, float(eps), tag="M%d" % M, nbytes=_nb(X, Y))
+    return Y, mean, rstd
+
+
+def stgcn_ln_bwd(dY, X, gamma, mean, rstd, units):
+    """-> dX of the LayerNorm over each unit"""
+    _chk(dY, X, gamma, mean, rstd)
+    M = X.numel() // units
+    dX = torch.empty_like(X)
+    _call("gptst_stgcn_ln_bwd", _p(dY), _p(X), _p(gamma), _p(mean), _p(rstd), _p(dX), units, M, tag="M%d" % M, nbytes=_nb(dY, X, dX))
+    return dX
+
+
+def stgcn_ln_bwd_param(dY, X, mean, rstd, units):
+    """-> (dgamma, dbeta) (M values each), summed over the units in a fixed order"""
+    _chk(dY, X, mean, rstd)
+    M = X.numel() // units
+    ns = _C.lib().value("gptst_stgcn_ln_nsplit", units)
+    pg, pb = (torch.empty(ns, M, device=X.device, dtype=torch.float32) for _ in range(2))
+    _call("gptst_stgcn_ln_bwd_param", _p(dY), _p(X), _p(mean), _p(rstd), _p(pg), _p(pb), ns, units, M, tag="M%d" % M, nbytes=_nb(dY, X))
+    return pg.sum(0), pb.sum(0)

@@ -7,7 +7,10 @@ so the output is (B, T, N, dim_out).
     ST block:  GLU temporal conv (kt)  ->  Chebyshev graph conv (ks) + ReLU  ->  ReLU temporal conv (kt)  ->  LayerNorm([N, C])
     output:    GLU temporal conv (outputl_ks)  ->  LayerNorm([N, C])  ->  sigmoid 1x1 conv  ->  1x1 conv to dim_out
 
-This is downstream plumbing (torch ops on the GPU), not the hand-written hot path.
+The torch modules below are downstream plumbing (torch ops on the GPU), not the hand-written hot path, and the default.
+``STGCN(..., backend="hip")`` runs the same parameter tree on the project's own kernels instead (predictors/stgcn_hip.py, csrc/stgcn.hip),
+channels-last and without a permute, wherever those serve the call; elsewhere (a CPU input, active dropout, an unsupported width) the
+forward takes the torch modules.  ``backend_used`` records which of the two the last forward took.
 """
 import math
 
@@ -109,10 +112,17 @@ class _Head(nn.Module):
 
 class STGCN(nn.Module):
     """``args_predictor``: Ks, Kt, num_nodes, G (Ks, N, N) Chebyshev polynomials of the scaled Laplacian (gptst_amd.graph), blocks1
-    = [c0, c1, c2], drop_prob, outputl_ks — the fields of reference STGCN/args.py:52-88."""
+    = [c0, c1, c2], drop_prob, outputl_ks — the fields of reference STGCN/args.py:52-88.
 
-    def __init__(self, args_predictor, device, dim_in, dim_out):
+    The two backends differ in one observable way: in eval mode the HIP path runs under ``no_grad`` and keeps nothing for a backward, so its output
+    has ``requires_grad == False`` even when gradients are enabled, where the torch modules would return a differentiable one.  Gradients
+    (of the parameters or of the input) through ``backend="hip"`` need ``train()`` mode."""
+
+    def __init__(self, args_predictor, device, dim_in, dim_out, backend="torch"):
         super().__init__()
+        if backend not in ("torch", "hip"):
+            raise ValueError("STGCN backend must be 'torch' or 'hip', got %r" % (backend,))
+        self.backend, self.backend_used = backend, None
         a = args_predictor
         lk = a.G.to(device)
         blocks0 = [dim_in, a.blocks1[1], a.blocks1[0]]                    # stgcn.py:134
@@ -121,5 +131,14 @@ class STGCN(nn.Module):
         self.output = _Head(a.blocks1[2], a.outputl_ks, a.num_nodes, dim_out)
 
     def forward(self, x):                                                  # x (B, T, N, dim_in)
+        if self.backend == "hip":
+            from . import stgcn_hip
+            if stgcn_hip.supported(self, x):
+                self.backend_used = "hip"
+                if self.training and torch.is_grad_enabled():
+                    return stgcn_hip.forward(self, x, keep=True)
+                with torch.no_grad():                                      # eval mode: nothing is kept for a backward
+                    return stgcn_hip.forward(self, x, keep=False)
+        self.backend_used = "torch"
         y = self.output(self.st_conv2(self.st_conv1(x.permute(0, 3, 1, 2))))
         return y.permute(0, 2, 3, 1)                                      # (B, T, N, dim_out)

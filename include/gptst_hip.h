@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 17  /* 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 18  /* 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -431,6 +431,37 @@ int gptst_fusion_gate_bwd(const float* dOut, const float* F, const float* z, con
 int gptst_fusion_gate_bwd_df(const float* dOut, const float* F, const float* z, const float* src, int lda, int base, const float* Wo,
                              const float* Wt, const float* bt, const float* Ws, float* dpre, float* dxd, float* Hm, float* xt, float* dF,
                              int rows, int C, void* stream);
+/* ---- the downstream STGCN predictor (stgcn.hip; reference model/STGCN/stgcn.py, gpt-st_amd/predictors/stgcn_hip.py) ----------------------
+ * Channels-last throughout: an activation is (rows = B*T*N, C), a temporal tap is a row offset of dt*N rows, nothing is permuted.
+ * act: 0 none, 1 relu, 2 sigmoid, 3 GLU.  Widths are multiples of 16, else GPTST_ESHAPE.
+ * tapgemm: Y (rows, co) = act(sum_j X[row + dt_j N][0..ci) W_j + bias + res): W (co or, GLU, 2 co rows; ntap*ci columns, tap-major),
+ *   ntap <= 4 taps of time offsets dt_j (a tap outside [0, T) is zero padding and is not read), res = R[row][ch] for ch < res_w (row stride
+ *   ldr; res_w = 0: none).  GLU: Y = (P + bias + res) sigmoid(Q + bias), P = W rows [0, co), Q = rows [co, 2 co); S, A (rows, co; both or
+ *   neither) keep sigmoid(Q) and P + bias + res for the backward.  ntap*ci <= 1024.
+ * gate_bwd: dPre from dOut: relu / sigmoid from the layer's output `out`; GLU from S, A -> dPre (rows, 2 co) = [dOut S | dOut A S (1 - S)].
+ * wgrad: part (nsplit, cw, ntap*ci) = row-split partials of D^T X_shift (D (rows, cw) = dPre; X, ci, taps as in tapgemm), bpart
+ *   (nsplit, cw; may be NULL) = those of the column sums of D; the caller sums the splits (fixed order, no atomics).
+ * nodemix: per (b,t) unit of N rows, with L (ks, Np, Np) zero-padded to Np = 16 ceil(N/16):  reduce = 0: Out (rows, ks*c), Out[:, k c + ch] =
+ *   (L_k In)[:, ch], In (rows, c);  reduce = 1: Out (rows, c) = sum_k L_k In[:, k c ..] + R, In (rows, ks*c), R (rows, c) or NULL.
+ * ln_fwd / ln_bwd / ln_bwd_param: LayerNorm over the M = N*C values of a unit (gamma, beta: M values): Y, and mean, rstd (units; may both
+ *   be NULL);  dX;  pg, pb (nsplit, M) = unit-split partials of dgamma, dbeta. */
+int gptst_stgcn_tapgemm(const float* X, int ldx, int ci, int ntap, int dt0, int dt1, int dt2, int dt3, const float* W, const float* bias,
+                        const float* R, int ldr, int res_w, float* Y, int co, float* S, float* A, int act, int rows, int T, int N,
+                        void* stream);
+int gptst_stgcn_gate_bwd(const float* dOut, const float* out, const float* S, const float* A, float* dPre, int act, int rows, int co,
+                         void* stream);
+int gptst_stgcn_wgrad_nsplit(int rows, int cw, int Ktot);
+int gptst_stgcn_wgrad(const float* D, int cw, const float* X, int ldx, int ci, int ntap, int dt0, int dt1, int dt2, int dt3, float* part,
+                      float* bpart, int nsplit, int rows, int T, int N, void* stream);
+int gptst_stgcn_nodemix(const float* L, int Np, int ks, const float* In, float* Out, const float* R, int c, int reduce, int units, int N,
+                        void* stream);
+int gptst_stgcn_ln_fwd(const float* X, const float* gamma, const float* beta, float* Y, float* mean, float* rstd, int units, int M,
+                       float eps, void* stream);
+int gptst_stgcn_ln_bwd(const float* dY, const float* X, const float* gamma, const float* mean, const float* rstd, float* dX, int units,
+                       int M, void* stream);
+int gptst_stgcn_ln_nsplit(int units);
+int gptst_stgcn_ln_bwd_param(const float* dY, const float* X, const float* mean, const float* rstd, float* pg, float* pb, int nsplit,
+                             int units, int M, void* stream);
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column
  * sums of X | sums of a'] for the caller to fold (one kind-1 pool job next to the other reductions of a step). */
