@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN``: the downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -46,7 +46,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -114,15 +114,15 @@ def main_shard(args, dev):
 
 
 def main_eval(args, dev):
-    """``-mode eval -model STGCN``: train the STGCN predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88 with the values of conf/STGCN/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88 and model/TGCN/args.py:7-41 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import STGCN
-    if str(args.model) != "STGCN":
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN (SURVEY.md §8f rank 4: one baseline predictor)")
+    from gptst_amd.predictors import STGCN, TGCN
+    if str(args.model) not in ("STGCN", "TGCN"):
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN and -model TGCN (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     init_seed(args.seed)
@@ -133,10 +133,15 @@ def main_eval(args, dev):
     csv_path = os.path.join(data_root, args.dataset, args.dataset + ".csv")
     A = (graph.adjacency_from_distance_csv(csv_path, args.num_nodes) if os.path.exists(csv_path)
          else graph.synthetic_adjacency(args.num_nodes, seed=args.seed))
-    ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
-                         drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)
-    model = EnhanceFrontEnd(args, predictor=STGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stgcn_backend)),
-                            finetune_encoder=bool(args.finetune_encoder)).to(dev)
+    if str(args.model) == "TGCN":                                                # model/Model.py:67-69: built from the raw adjacency
+        ap = SimpleNamespace(num_nodes=args.num_nodes, input_window=pargs.input_window, output_window=pargs.output_window,
+                             rnn_units=pargs.rnn_units, output_dim=pargs.output_dim, G=graph.tgcn_graph(A))
+        predictor = TGCN(ap, dev, args.hidden_dim, backend=str(args.tgcn_backend))
+    else:
+        ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
+                             drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)
+        predictor = STGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stgcn_backend))
+    model = EnhanceFrontEnd(args, predictor=predictor, finetune_encoder=bool(args.finetune_encoder)).to(dev)
     ckpt = args.log_dir + str(args.load_pretrain_path)                           # model/Model.py:92 (plain concatenation: '/GPTST_ada.pth')
     if os.path.exists(ckpt):
         model.load_pretrained_model(ckpt)                                        # model/Model.py:91-94

@@ -74,6 +74,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-encoder_lr_scale", default=FINETUNE_DEFAULTS["encoder_lr_scale"], type=float)
     # not a reference option: what runs the STGCN predictor of -mode eval: the torch modules or the HIP kernels (predictors/stgcn_hip.py)
     ap.add_argument("-stgcn_backend", default=FINETUNE_DEFAULTS["stgcn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the TGCN predictor (predictors/tgcn_hip.py)
+    ap.add_argument("-tgcn_backend", default=FINETUNE_DEFAULTS["tgcn_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -85,7 +87,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
-FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch")
+FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -112,13 +114,18 @@ _PRED_TRAIN = [("batch_size", int), ("epochs", int), ("lr_init", float), ("lr_de
 _STGCN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data", "output_window", int), ("model", "Ks", int),
                ("model", "Kt", int), ("model", "blocks1", _EVAL), ("model", "drop_prob", int), ("model", "outputl_ks", int),
                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+# reference model/TGCN/args.py:14-25.  `lam` is parsed and, as in the reference (TGCN.py:140 stores it, nothing reads it), used nowhere.
+_TGCN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data", "output_window", int), ("model", "rnn_units", int),
+              ("model", "lam", float), ("model", "output_dim", int),
+              ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  Only STGCN is built."""
-    if model != "STGCN":
-        raise ValueError("gpt-st_amd builds the STGCN predictor only, got %r" % (model,))
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN and TGCN are built."""
+    if model not in _PRED_KEYS:
+        raise ValueError("gpt-st_amd builds the STGCN and TGCN predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)
@@ -131,7 +138,7 @@ def predictor_args(dataset, model="STGCN", argv=None):
     cm = configparser.ConfigParser()
     cm.optionxform = str
     cm.read(path)
-    for sec, key, typ in _STGCN_KEYS:
+    for sec, key, typ in _PRED_KEYS[model]:
         ap.add_argument("--" + key, default=typ(cm[sec][key]), type=typ)
     pargs, _ = ap.parse_known_args([] if argv is None else argv)
     return pargs

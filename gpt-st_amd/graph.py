@@ -1,6 +1,6 @@
-"""Predefined-graph helpers the STGCN predictor needs (reference model/STGCN/args.py:7-49, lib/predifineGraph.py:6-60): scaled graph
-Laplacian and its Chebyshev polynomials, the adjacency of the PEMS distance csv, and a synthetic sensor graph for runs without the
-(non-redistributable) data files."""
+"""Predefined-graph helpers the downstream predictors need (reference model/STGCN/args.py:7-49, lib/predifineGraph.py:6-60,
+model/TGCN/TGCN.py:8-25): scaled graph Laplacian and its Chebyshev polynomials (STGCN), the normalised adjacency (TGCN), the adjacency of the
+PEMS distance csv, and a synthetic sensor graph for runs without the (non-redistributable) data files."""
 import csv
 
 import numpy as np
@@ -61,3 +61,19 @@ def synthetic_adjacency(num_nodes, seed=0, degree=3):
 def stgcn_graph(A, Ks=3):
     """The ``args_predictor.G`` tensor of the reference (args.py:86-88; the reference hard-codes 3 polynomials there)."""
     return torch.tensor(cheb_polynomials(scaled_laplacian(A), Ks), dtype=torch.float32)
+
+
+def normalized_adjacency(A):
+    """TGCN's graph (reference TGCN.py:8-25, ``calculate_normalized_laplacian``): with A~ = A + I and D = diag(row sums of A~), the reference's
+    operand order (A~ D^-1/2)^T D^-1/2 = D^-1/2 A~^T D^-1/2 — for a non-symmetric A the TRANSPOSE of the textbook D^-1/2 A~ D^-1/2."""
+    At = np.asarray(A, dtype=np.float64) + np.identity(len(A))
+    d = At.sum(axis=1)
+    with np.errstate(divide="ignore"):
+        dis = np.power(d, -0.5)
+    dis[np.isinf(dis)] = 0.0
+    return (At * dis[None, :]).T * dis[None, :]
+
+
+def tgcn_graph(A):
+    """The dense fp32 (N, N) graph of ``predictors.TGCN`` (the reference builds it inside the cell and casts it with ``.float()``, TGCN.py:37,116)."""
+    return torch.tensor(normalized_adjacency(A), dtype=torch.float32)

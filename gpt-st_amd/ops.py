@@ -1196,3 +1196,48 @@ def stgcn_ln_bwd_param(dY, X, mean, rstd, units):
     pg, pb = (torch.empty(ns, M, device=X.device, dtype=torch.float32) for _ in range(2))
     _call("gptst_stgcn_ln_bwd_param", _p(dY), _p(X), _p(mean), _p(rstd), _p(pg), _p(pb), ns, units, M, tag="M%d" % M, nbytes=_nb(dY, X))
     return pg.sum(0), pb.sum(0)
+
+
+# ---- the downstream TGCN predictor's recurrence (csrc/tgcn.hip) ---------------------------------------------------------------------
+# step tensors are (B*N, Hp), seq tensors (B*T*N, width) with row (b T + t) N + n; outputs are the caller's buffers (the loop reuses them)
+def _tg_nb(Lp, W, step, k):
+    """algorithmic bytes of a step launch: the graph, the weights, and k step-sized (B*N, Hp) blocks read or written"""
+    return _nb(Lp, W) + k * step.numel() * 4
+
+
+def tgcn_fwd_gates(Lp, W0h, h, Gx0, t, u, q, B, T, N, r=None, z=None, zoff=0, tiles=0):
+    """[r, u] = sigmoid((L h) W0h^T + Gx0[:, t]) -> u, q = r h, and when given r and z[(b, t) rows, zoff:zoff + Hp] = L h"""
+    _chk(Lp, W0h, h, Gx0, u, q, r, z)
+    Hp = h.shape[1]
+    assert W0h.shape == (2 * Hp, Hp) and h.shape[0] == B * N and Gx0.shape == (B * T * N, 2 * Hp) and u.shape == q.shape == h.shape
+    _call("gptst_tgcn_fwd_gates", _p(Lp), Lp.shape[0], _p(W0h), _p(h), _p(Gx0), _p(u), _p(r), _p(q), _p(z), z.shape[1] if z is not None else 0, zoff,
+          B, T, N, Hp, t, tiles, tag="Hp%d" % Hp, nbytes=_tg_nb(Lp, W0h, h, 5 + (r is not None) + (z is not None)))      # h, Gx0 (2), u, q
+
+
+def tgcn_fwd_state(Lp, W1h, q, Gx1, t, u, h, h_out, B, T, N, c=None, z=None, zoff=0, tiles=0):
+    """c = tanh((L q) W1h^T + Gx1[:, t]) -> h_out = u h + (1 - u) c, and when given c and z[(b, t) rows, zoff:zoff + Hp] = L q"""
+    _chk(Lp, W1h, q, Gx1, u, h, h_out, c, z)
+    Hp = h.shape[1]
+    assert W1h.shape == (Hp, Hp) and h.shape[0] == B * N and Gx1.shape == (B * T * N, Hp) and u.shape == q.shape == h_out.shape == h.shape
+    _call("gptst_tgcn_fwd_state", _p(Lp), Lp.shape[0], _p(W1h), _p(q), _p(Gx1), _p(u), _p(h), _p(h_out), _p(c), _p(z),
+          z.shape[1] if z is not None else 0, zoff, B, T, N, Hp, t, tiles, tag="Hp%d" % Hp,
+          nbytes=_tg_nb(Lp, W1h, h, 5 + (c is not None) + (z is not None)))      # q, Gx1, u, h, h_out
+
+
+def tgcn_bwd_cand(LpT, W1hT, dh, u, c, r, h, t, dpre1, dpre0, dh_part, B, T, N, tiles=0):
+    """dpre1[:, t] = dh (1 - u)(1 - c^2);  dq = (L^T dpre1) W1h;  dpre0[:, t] = [dq h r (1 - r) | dh (h - c) u (1 - u)];  dh_part = dh u + dq r"""
+    _chk(LpT, W1hT, dh, u, c, r, h, dpre1, dpre0, dh_part)
+    Hp = h.shape[1]
+    assert W1hT.shape == (Hp, Hp) and h.shape[0] == B * N and dpre1.shape == (B * T * N, Hp) and dpre0.shape == (B * T * N, 2 * Hp)
+    assert dh.shape == u.shape == c.shape == r.shape == dh_part.shape == h.shape
+    _call("gptst_tgcn_bwd_cand", _p(LpT), LpT.shape[0], _p(W1hT), _p(dh), _p(u), _p(c), _p(r), _p(h), _p(dpre1), _p(dpre0), _p(dh_part),
+          B, T, N, Hp, t, tiles, tag="Hp%d" % Hp, nbytes=_tg_nb(LpT, W1hT, h, 9))      # dh, u, c, r, h; dpre1, dpre0 (2), dh_part
+
+
+def tgcn_bwd_state(LpT, W0hT, dpre0, dh_part, t, dh_out, B, T, N, tiles=0):
+    """dh_out = dh_part + (L^T dpre0[:, t]) W0h"""
+    _chk(LpT, W0hT, dpre0, dh_part, dh_out)
+    Hp = dh_part.shape[1]
+    assert W0hT.shape == (Hp, 2 * Hp) and dh_part.shape[0] == B * N and dpre0.shape == (B * T * N, 2 * Hp) and dh_out.shape == dh_part.shape
+    _call("gptst_tgcn_bwd_state", _p(LpT), LpT.shape[0], _p(W0hT), _p(dpre0), _p(dh_part), _p(dh_out), B, T, N, Hp, t, tiles, tag="Hp%d" % Hp,
+          nbytes=_tg_nb(LpT, W0hT, dh_part, 4))      # dpre0 (2), dh_part, dh_out

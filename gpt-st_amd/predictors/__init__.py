@@ -1,3 +1,4 @@
 """Downstream predictors trained on the enhanced embedding.  Not part of the pretraining hot path: they are
 ordinary ``torch.nn`` modules on the GPU (rocBLAS / MIOpen through PyTorch-ROCm) behind the frozen HIP encoder of ``enhance.py``."""
 from .stgcn import STGCN   # noqa: F401
+from .tgcn import TGCN     # noqa: F401

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 18  /* 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 19  /* 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -462,6 +462,29 @@ int gptst_stgcn_ln_bwd(const float* dY, const float* X, const float* gamma, cons
 int gptst_stgcn_ln_nsplit(int units);
 int gptst_stgcn_ln_bwd_param(const float* dY, const float* X, const float* mean, const float* rstd, float* pg, float* pb, int nsplit,
                              int units, int M, void* stream);
+/* ---- the downstream TGCN predictor's recurrence (tgcn.hip; reference model/TGCN/TGCN.py:70-91, gpt-st_amd/predictors/tgcn_hip.py) -------------
+ * Per step t: [r, u] = sigmoid(L [x_t, h] W0 + b0), c = tanh(L [x_t, r h] W1 + b1), h' = u h + (1 - u) c.  The x_t halves (Gx0 = L X W0[:C] + b0,
+ * Gx1 likewise) and every weight / input gradient are hoisted onto gptst_stgcn_nodemix / tapgemm / wgrad; these four launches are the h chain.
+ * A "step" tensor is (B*N, Hp), row b N + n; a "seq" tensor is (B*T*N, width), row (b T + t) N + n.  Hp = rnn_units zero-padded to a multiple of
+ * 16 (16..128, else GPTST_ESHAPE); L / LT (Np, Np) zero-padded to Np = 16 ceil(N/16).  Each launch computes M = L[rows, :] In_b per batch element,
+ * P = M Wt^T with Wt (outputs, K) row-major, and an epilogue.  tiles: 16-node tiles per workgroup, 1 or 2; 0 = chosen from B and N.
+ * fwd_gates: In = h;  W0h (2 Hp, Hp);  Gx0 (seq, 2 Hp) -> u, q = r h (step), and when not NULL r (step) and z[seq row][zoff + col] = M (ld ldz).
+ * fwd_state: In = q;  W1h (Hp, Hp);  Gx1 (seq, Hp) -> h_out = u h + (1 - u) c (step; may be h), and when not NULL c (step) and z as above.
+ * bwd_cand:  In = dpre1 = dh (1 - u)(1 - c^2) formed on load, -> dpre1 (seq, Hp);  W1hT (Hp, Hp) = W1h^T;  -> dpre0 (seq, 2 Hp) =
+ *            [dq h r (1 - r) | dh (h - c) u (1 - u)], dh_part = dh u + dq r (step; not dh);  h = the step's INPUT state.
+ * bwd_state: In = dpre0 (seq, 2 Hp);  W0hT (Hp, 2 Hp) = W0h^T  -> dh_out = dh_part + P (step).
+ * lds_bytes: the dynamic LDS of the widest of the four at this shape (above 160 KB they return GPTST_ESHAPE). */
+int gptst_tgcn_lds_bytes(int N, int Hp, int B);
+int gptst_tgcn_fwd_gates(const float* L, int Np, const float* W0h, const float* h, const float* Gx0, float* u, float* r, float* q,
+                         float* z, int ldz, int zoff, int B, int T, int N, int Hp, int t, int tiles, void* stream);
+int gptst_tgcn_fwd_state(const float* L, int Np, const float* W1h, const float* q, const float* Gx1, const float* u, const float* h,
+                         float* h_out, float* c, float* z, int ldz, int zoff, int B, int T, int N, int Hp, int t, int tiles,
+                         void* stream);
+int gptst_tgcn_bwd_cand(const float* LT, int Np, const float* W1hT, const float* dh, const float* u, const float* c, const float* r,
+                        const float* h, float* dpre1, float* dpre0, float* dh_part, int B, int T, int N, int Hp, int t, int tiles,
+                        void* stream);
+int gptst_tgcn_bwd_state(const float* LT, int Np, const float* W0hT, const float* dpre0, const float* dh_part, float* dh_out, int B,
+                         int T, int N, int Hp, int t, int tiles, void* stream);
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column
  * sums of X | sums of a'] for the caller to fold (one kind-1 pool job next to the other reductions of a step). */
