@@ -76,6 +76,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-stgcn_backend", default=FINETUNE_DEFAULTS["stgcn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the TGCN predictor (predictors/tgcn_hip.py)
     ap.add_argument("-tgcn_backend", default=FINETUNE_DEFAULTS["tgcn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the MTGNN predictor (predictors/mtgnn_hip.py)
+    ap.add_argument("-mtgnn_backend", default=FINETUNE_DEFAULTS["mtgnn_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -87,7 +89,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
-FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch")
+FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -118,14 +120,22 @@ _STGCN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data
 _TGCN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data", "output_window", int), ("model", "rnn_units", int),
               ("model", "lam", float), ("model", "output_dim", int),
               ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
-_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS}
+# reference model/MTGNN/args.py:13-39.  `use_curriculum_learning` and `task_level` are parsed and, as in the reference, read by nothing.
+_MTGNN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data", "output_window", int), ("data", "output_dim", int),
+               ("model", "gcn_true", _EVAL), ("model", "buildA_true", _EVAL), ("model", "gcn_depth", int), ("model", "dropout", float),
+               ("model", "subgraph_size", int), ("model", "node_dim", int), ("model", "dilation_exponential", int),
+               ("model", "conv_channels", int), ("model", "residual_channels", int), ("model", "skip_channels", int),
+               ("model", "end_channels", int), ("model", "layers", int), ("model", "propalpha", float), ("model", "tanhalpha", int),
+               ("model", "layer_norm_affline", _EVAL), ("model", "use_curriculum_learning", _EVAL), ("model", "task_level", int),
+               ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN and TGCN are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN and MTGNN are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN and TGCN predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN and MTGNN predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)

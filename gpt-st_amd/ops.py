@@ -1241,3 +1241,61 @@ def tgcn_bwd_state(LpT, W0hT, dpre0, dh_part, t, dh_out, B, T, N, tiles=0):
     assert W0hT.shape == (Hp, 2 * Hp) and dh_part.shape[0] == B * N and dpre0.shape == (B * T * N, 2 * Hp) and dh_out.shape == dh_part.shape
     _call("gptst_tgcn_bwd_state", _p(LpT), LpT.shape[0], _p(W0hT), _p(dpre0), _p(dh_part), _p(dh_out), B, T, N, Hp, t, tiles, tag="Hp%d" % Hp,
           nbytes=_tg_nb(LpT, W0hT, dh_part, 4))      # dpre0 (2), dh_part, dh_out
+
+
+# ---- the downstream MTGNN predictor (csrc/mtgnn.hip): tensors are (B * T * N rows, width) with T the tensor's own frame ----------------------
+def mtgnn_tapgemm(X, W, bias, offs, B, Tsrc, Tdst, N, gated=False, xmask=None, omask=None, res=None, res_frame=None, res_off=0, out=None,
+                  keep=False):
+    """Y (B Tdst N, co)[b, to, n] = epi(sum_j (X xmask)[b, to + offs[j], n] W_j + bias); W (co | 2 co (gated), len(offs) * ci), tap-major columns.
+    plain: epi(v) = (v + res[b, to + res_off, n]) omask, res of frame res_frame (default Tdst); out: the caller's buffer (out = res of the same frame
+    accumulates in place).
+    gated: tanh(P) sigmoid(Q) omask; keep -> (Y, tanh, sigmoid), what the backward needs."""
+    _chk(X, W, bias, xmask, omask, res, out)
+    ci = X.shape[1]
+    co = W.shape[0] // 2 if gated else W.shape[0]
+    assert X.shape[0] == B * Tsrc * N and W.shape[1] == len(offs) * ci and (xmask is None or xmask.shape == X.shape)
+    Tr = Tdst if res_frame is None else res_frame
+    assert res is None or (res.shape == (B * Tr * N, co) and not gated)
+    Y = torch.empty(B * Tdst * N, co, device=X.device, dtype=torch.float32) if out is None else out
+    assert Y.shape == (B * Tdst * N, co) and (omask is None or omask.shape == Y.shape)
+    Tn, S = (torch.empty_like(Y), torch.empty_like(Y)) if keep else (None, None)
+    _call("gptst_mtgnn_tapgemm", _p(X), ci, ci, _p(xmask), len(offs), _ints(offs), _p(W), _p(bias), _p(res), co, Tr, int(res_off), _p(omask), _p(Y),
+          co, _p(Tn), _p(S), int(gated), B, Tsrc, Tdst, N, tag="ci%d co%d k%d g%d T%d>%d" % (ci, co, len(offs), int(gated), Tsrc, Tdst),
+          nbytes=_nb(X, W, Y, Tn, S, xmask, omask, res))
+    return (Y, Tn, S) if keep else Y
+
+
+def mtgnn_gate_bwd(dG, Tn, S, omask=None):
+    """dPre (rows, 2 co) = [dG omask S (1 - Tn^2) | dG omask Tn S (1 - S)]"""
+    _chk(dG, Tn, S, omask)
+    rows, co = dG.shape
+    dPre = torch.empty(rows, 2 * co, device=dG.device, dtype=torch.float32)
+    _call("gptst_mtgnn_gate_bwd", _p(dG), _p(Tn), _p(S), _p(omask), _p(dPre), rows, co, tag="co%d" % co, nbytes=_nb(dG, Tn, S, omask, dPre))
+    return dPre
+
+
+def mtgnn_wgrad(D, X, offs, B, Tsrc, Tdst, N, xmask=None, want_bias=True):
+    """-> (dW (cw, len(offs) * ci) = sum D[b, to, n]^T (X xmask)[b, to + offs[j], n], db (cw)): row-split partials summed in a fixed order"""
+    _chk(D, X, xmask)
+    cw, ci = D.shape[1], X.shape[1]
+    K = len(offs) * ci
+    assert D.shape[0] == B * Tdst * N and X.shape[0] == B * Tsrc * N
+    ns = _C.lib().value("gptst_stgcn_wgrad_nsplit", D.shape[0], cw, K)
+    part = torch.empty(ns, cw, K, device=D.device, dtype=torch.float32)
+    bpart = torch.empty(ns, cw, device=D.device, dtype=torch.float32) if want_bias else None
+    _call("gptst_mtgnn_wgrad", _p(D), cw, _p(X), ci, ci, _p(xmask), len(offs), _ints(offs), _p(part), _p(bpart), ns, B, Tsrc, Tdst, N,
+          tag="cw%d ci%d k%d T%d>%d" % (cw, ci, len(offs), Tsrc, Tdst), nbytes=_nb(D, X, part, xmask))
+    return part.sum(0), (bpart.sum(0) if want_bias else None)
+
+
+def mtgnn_graphgrad(D, X, N, c, ks, dcol0=0):
+    """-> dM (ks, N, N), dM_k[v, w] = sum_{unit, ch} D[unit N + v, dcol0 + k c + ch] X[unit N + w, ch]: unit-split partials summed in a fixed order"""
+    _chk(D, X)
+    rows = X.shape[0]
+    assert D.shape[0] == rows and rows % N == 0 and X.shape[1] == c and D.shape[1] >= dcol0 + ks * c
+    units = rows // N
+    ns = _C.lib().value("gptst_mtgnn_graphgrad_nsplit", units, N, ks)
+    part = torch.empty(ns, ks, N, N, device=D.device, dtype=torch.float32)
+    _call("gptst_mtgnn_graphgrad", _p(D), D.shape[1], dcol0, _p(X), c, c, ks, _p(part), ns, units, N, tag="c%d ks%d" % (c, ks),
+          nbytes=rows * (ks + 1) * c * 4 + part.numel() * 4)
+    return part.sum(0)

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 19  /* 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 20  /* 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -485,6 +485,28 @@ int gptst_tgcn_bwd_cand(const float* LT, int Np, const float* W1hT, const float*
                         void* stream);
 int gptst_tgcn_bwd_state(const float* LT, int Np, const float* W0hT, const float* dpre0, const float* dh_part, float* dh_out, int B,
                          int T, int N, int Hp, int t, int tiles, void* stream);
+/* ---- the downstream MTGNN predictor (mtgnn.hip; reference model/MTGNN/MTGNN.py, gpt-st_amd/predictors/mtgnn_hip.py) ------------------------
+ * Rows (b, t, n), channels last, as above; a tensor's time length is its frame.  Widths are multiples of 16, else GPTST_ESHAPE.
+ * tapgemm: Y (B*Tdst*N, co)[b, to, n] = epi(sum_j X[b, to + offs[j], n][0..ci) W_j + bias): X (B*Tsrc*N rows, row stride ldx), ntap <= 32 taps
+ *   (host array offs; a tap whose source time falls outside [0, Tsrc) is not read), W (co or, gated, 2 co rows; ntap*ci columns, tap-major), any
+ *   K (walked in chunks).  XM (X's layout, or NULL) multiplies the operand.  gated = 0: epi(v) = (v + R[b, to + roff, n][ch]) OM, R of frame Tr
+ *   and row stride ldr read where 0 <= to + roff < Tr (NULL: none; R may be Y when Tr == Tdst and roff == 0: accumulation), OM (rows, co; NULL: 1).
+ *   gated = 1: Y = tanh(P + bias) sigmoid(Q + bias) OM, P = W rows [0, co), Q = rows [co, 2 co); Tn, S (rows, co; both or neither) keep the tanh
+ *   and the sigmoid.  The data backward is the same call: X = dPre, taps -offs[j], W = [W_j^T]_j, frames swapped, R = a second gradient.
+ * gate_bwd: dPre (rows, 2 co) = [dG OM S (1 - Tn^2) | dG OM Tn S (1 - S)].
+ * wgrad: part (nsplit, cw, ntap*ci) = row-split partials of sum_rows D[b, to, n]^T (X XM)[b, to + offs[j], n], D (B*Tdst*N, cw); bpart (nsplit, cw;
+ *   may be NULL) = those of the column sums of D; nsplit = gptst_stgcn_wgrad_nsplit(B*Tdst*N, cw, ntap*ci); the caller sums the splits.
+ * graphgrad: part (nsplit, ks, N, N) = unit-split partials of dM_k[v][w] = sum_{unit, ch} D[unit N + v][dcol0 + k c + ch] X[unit N + w][ch]: the
+ *   gradient of gptst_stgcn_nodemix (reduce = 0: D = dOut, X = In) with respect to L_k, unpadded; units of exactly N rows. */
+int gptst_mtgnn_tapgemm(const float* X, int ldx, int ci, const float* XM, int ntap, const int* offs, const float* W, const float* bias,
+                        const float* R, int ldr, int Tr, int roff, const float* OM, float* Y, int co, float* Tn, float* S, int gated,
+                        int B, int Tsrc, int Tdst, int N, void* stream);
+int gptst_mtgnn_gate_bwd(const float* dG, const float* Tn, const float* S, const float* OM, float* dPre, int rows, int co, void* stream);
+int gptst_mtgnn_wgrad(const float* D, int cw, const float* X, int ldx, int ci, const float* XM, int ntap, const int* offs, float* part,
+                      float* bpart, int nsplit, int B, int Tsrc, int Tdst, int N, void* stream);
+int gptst_mtgnn_graphgrad_nsplit(int units, int N, int ks);
+int gptst_mtgnn_graphgrad(const float* D, int ldd, int dcol0, const float* X, int ldx, int c, int ks, float* part, int nsplit, int units,
+                          int N, void* stream);
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column
  * sums of X | sums of a'] for the caller to fold (one kind-1 pool job next to the other reductions of a step). */
