@@ -305,6 +305,25 @@ static bool mt_taps(MtTaps& t, int ntap, const int* offs, int Tsrc, int Tdst) {
     return true;
 }
 
+// the launch plan of the tap GEMM: the one place that derives it, for the launch and for the query of the tests
+struct MtTgPlan { int colblocks, rowblocks, tpw; };
+
+static MtTgPlan mt_tapgemm_plan(long rows, int co, int gated) {
+    MtTgPlan g;
+    const int per = gated ? 32 : 64, ntiles = (int)((rows + 15) / 16), wpb = MT_THREADS / 64;
+    g.colblocks = (co + per - 1) / per;
+    const bool two = (ntiles + 2 * wpb - 1) / (2 * wpb) * g.colblocks >= 512;    // two tiles per wave once that still fills the device twice
+    g.tpw = two ? 2 : 1;
+    g.rowblocks = (ntiles + wpb * g.tpw - 1) / (wpb * g.tpw);
+    return g;
+}
+
+// (include/gptst_hip_testing.h) tiles per wave of the launch gptst_mtgnn_tapgemm makes for this shape: 1 or 2
+extern "C" int gptst_mtgnn_tapgemm_tpw(long rows, int co, int gated) {
+    if (rows <= 0 || rows > (1L << 30) || co <= 0) return GPTST_EARG;
+    return mt_tapgemm_plan(rows, co, gated).tpw;
+}
+
 extern "C" int gptst_mtgnn_tapgemm(const float* X, int ldx, int ci, const float* XM, int ntap, const int* offs, const float* W, const float* bias,
                                    const float* R, int ldr, int Tr, int roff, const float* OM, float* Y, int co, float* Tn, float* S, int gated,
                                    int B, int Tsrc, int Tdst, int N, void* stream) {
@@ -314,9 +333,9 @@ extern "C" int gptst_mtgnn_tapgemm(const float* X, int ldx, int ci, const float*
         return GPTST_EARG;
     const long rows = (long)B * Tdst * N;
     if (ci < 16 || ci % 16 || co < 16 || co % 16 || ldx % 4 || rows > (1L << 30) || (long)B * Tsrc * N > (1L << 30)) return GPTST_ESHAPE;
-    const int per = gated ? 32 : 64, colblocks = (co + per - 1) / per, ntiles = (int)((rows + 15) / 16), wpb = MT_THREADS / 64;
-    const bool two = (ntiles + 2 * wpb - 1) / (2 * wpb) * colblocks >= 512;      // two tiles per wave once that still fills the device twice
-    const int tpw = two ? 2 : 1, rowblocks = (ntiles + wpb * tpw - 1) / (wpb * tpw);
+    const MtTgPlan g = mt_tapgemm_plan(rows, co, gated);
+    const bool two = g.tpw == 2;
+    const int colblocks = g.colblocks, rowblocks = g.rowblocks;
     MtTg p{X, ldx, ci, XM, tap, W, ntap * ci, bias, R, ldr, Tr, roff, OM, Y, co, Tn, S, gated, (int)rows, Tsrc, Tdst, N};
     if (two) hipLaunchKernelGGL(mt_tapgemm_kernel<2>, dim3(rowblocks, colblocks), dim3(MT_THREADS), 0, (hipStream_t)stream, p);
     else hipLaunchKernelGGL(mt_tapgemm_kernel<1>, dim3(rowblocks, colblocks), dim3(MT_THREADS), 0, (hipStream_t)stream, p);

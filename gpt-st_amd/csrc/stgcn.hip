@@ -375,6 +375,28 @@ static bool sg_taps_ok(int ntap, const int* dt, int T) {
     return true;
 }
 
+// the launch plan of the tap GEMM: the one place that derives it, for the launch and for the query of the tests
+struct SgTgPlan { bool wide; int ocw, colblocks, rowblocks, tpw; };
+
+static SgTgPlan sg_tapgemm_plan(int rows, int co, int Ktot, int act) {
+    SgTgPlan g;
+    g.wide = Ktot <= 384;                                            // 64 weight rows of up to 388 floats: 99 KB; beyond that 32 rows
+    g.ocw = g.wide ? 64 : 32;
+    const int per = act == SG_ACT_GLU ? g.ocw / 2 : g.ocw;
+    const int ntiles = (rows + 15) / 16, wpb = SG_TG_THREADS / 64;
+    g.colblocks = (co + per - 1) / per;
+    int rowblocks = 512 / g.colblocks; if (rowblocks < 1) rowblocks = 1;
+    g.tpw = (ntiles + wpb * rowblocks - 1) / (wpb * rowblocks); if (g.tpw < 1) g.tpw = 1;
+    g.rowblocks = (ntiles + wpb * g.tpw - 1) / (wpb * g.tpw);
+    return g;
+}
+
+// (include/gptst_hip_testing.h) tiles per wave of the launch gptst_stgcn_tapgemm makes for this shape
+extern "C" int gptst_stgcn_tapgemm_tpw(int rows, int co, int Ktot, int act) {
+    if (rows <= 0 || co <= 0 || Ktot <= 0 || act < 0 || act > 3) return GPTST_EARG;
+    return sg_tapgemm_plan(rows, co, Ktot, act).tpw;
+}
+
 extern "C" int gptst_stgcn_tapgemm(const float* X, int ldx, int ci, int ntap, int dt0, int dt1, int dt2, int dt3, const float* W, const float* bias,
                                    const float* R, int ldr, int res_w, float* Y, int co, float* S, float* A, int act, int rows, int T, int N,
                                    void* stream) {
@@ -384,13 +406,10 @@ extern "C" int gptst_stgcn_tapgemm(const float* X, int ldx, int ci, int ntap, in
         return GPTST_EARG;
     const int Ktot = ntap * ci;
     if (ci < 16 || ci % 16 || co < 16 || co % 16 || ldx % 4 || Ktot > 1024) return GPTST_ESHAPE;
-    const bool wide = Ktot <= 384;                                   // 64 weight rows of up to 388 floats: 99 KB; beyond that 32 rows
-    const int ocw = wide ? 64 : 32, per = act == SG_ACT_GLU ? ocw / 2 : ocw;
-    const size_t smem = ((size_t)ocw * (Ktot + 4) + ocw) * sizeof(float);
-    const int colblocks = (co + per - 1) / per, ntiles = (rows + 15) / 16, wpb = SG_TG_THREADS / 64;
-    int rowblocks = 512 / colblocks; if (rowblocks < 1) rowblocks = 1;
-    int tpw = (ntiles + wpb * rowblocks - 1) / (wpb * rowblocks); if (tpw < 1) tpw = 1;
-    rowblocks = (ntiles + wpb * tpw - 1) / (wpb * tpw);
+    const SgTgPlan g = sg_tapgemm_plan(rows, co, Ktot, act);
+    const bool wide = g.wide;
+    const int colblocks = g.colblocks, rowblocks = g.rowblocks, tpw = g.tpw;
+    const size_t smem = ((size_t)g.ocw * (Ktot + 4) + g.ocw) * sizeof(float);
     SgTg p{X, ldx, ci, SgTap{ntap, {dt0, dt1, dt2, dt3}}, W, Ktot, bias, res_w > 0 ? R : nullptr, ldr, res_w, Y, co, S, A, act, rows, T, N, tpw};
     // more than 64 KB of dynamic LDS needs the attribute, on every device this process launches on
     static bool attr_set[SG_MAX_DEVICES] = {};

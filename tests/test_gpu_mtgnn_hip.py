@@ -2,7 +2,9 @@
 comparison is fp64 torch on the CPU: ``F.conv2d`` and autograd for the tap GEMM family, ``einsum`` for the graph gradient, the torch MTGNN module
 (pinned to the reference implementation's vectors by tests/test_predictor_mtgnn.py) for the whole model.  The bound is the project's element-wise
 one, 1e-4 of the reference tensor's largest magnitude, for every output, dX and parameter gradient.  The shapes are the smallest at which a
-kernel can still go wrong (odd N, N of exactly one tile, several workgroups, K beyond one LDS chunk), not the workload's."""
+kernel can still go wrong (odd N, N of exactly one tile, several workgroups, K beyond one LDS chunk), not the workload's; the cases with a PLANS
+entry, ``test_graphgrad_several_steps`` and the shipped configurations are the smallest at which the launch plans take the paths of a real
+batch (two tiles per wave, several chunks or units per split, a second grid-stride pass), and each asserts that it is on its path first."""
 import functools
 import logging
 from types import SimpleNamespace
@@ -12,8 +14,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from gptst_amd import ops, synth
-from gptst_amd.config import make_args
+from gptst_amd import _C, graph, ops, synth
+from gptst_amd.config import make_args, predictor_args
 from gptst_amd.predictors import MTGNN, mtgnn_hip as H
 from golden_util import load
 from mtgnn_util import clear_topk_cuts, same_support
@@ -62,7 +64,31 @@ TAP_CASES = {
     "skip0":          (2, 20, 1, 20, 64, 64, tuple(range(20)), False, False, False, False, False),
     "skip0_dropout":  (2, 20, 1, 20, 64, 64, tuple(range(20)), False, False, False, False, True),
     "one_tap":        (2, 2, 2, 37, 32, 64, (0,), False, False, False, False, False),
+    # two row tiles per wave (mt_tapgemm_kernel<2>), several 64-row chunks per split of the weight gradient, a second grid-stride pass of the
+    # gate backward: what every real batch takes.  N = 461 and 253 are no multiples of 16
+    "wide_tpw2":      (3, 13, 12, 461, 16, 128, (0, 1), True, False, False, False, False),
+    "wide_tpw2_b6":   (6, 13, 12, 461, 16, 128, (0, 1), True, False, False, False, False),
+    "inception_tpw2": (20, 19, 13, 253, 32, 32, tuple(range(7)), True, True, True, False, False),       # the workload's layer 0 at B = 20
+    "wgrad_cw256":    (2, 19, 13, 193, 32, 128, tuple(range(7)), True, False, False, False, False),    # 79 chunks, 40 splits, the last of one
 }
+# what the launch plans must make of a case (absent: one iteration everywhere, as in the cases above the comment): tiles per wave of the
+# forward and of the mirrored data backward, chunks per split of the weight gradient at least, and whether the gate backward makes a second pass
+PLANS = {
+    "wide_tpw2":      dict(fwd=2, bwd=1, cps=2, gate2=False),
+    "wide_tpw2_b6":   dict(fwd=2, bwd=1, cps=3, gate2=True),
+    "inception_tpw2": dict(fwd=2, bwd=2, cps=5, gate2=False),
+    "wgrad_cw256":    dict(fwd=1, bwd=1, cps=2, gate2=False),
+}
+ONE_PASS = dict(fwd=1, bwd=1, cps=1, gate2=False)
+
+
+def _plan(c):
+    """the same four figures from the library: the plan query of include/gptst_hip_testing.h, the split rule, the grid of the gate backward"""
+    v = _C.lib().value
+    ns = v("gptst_stgcn_wgrad_nsplit", c.rows, c.cw, c.ntap * c.ci)
+    nchunks = -(-c.rows // 64)
+    return dict(fwd=v("gptst_mtgnn_tapgemm_tpw", c.rows, c.co, int(c.gated)), bwd=v("gptst_mtgnn_tapgemm_tpw", c.srows, c.ci, 0),
+                cps=-(-nchunks // ns), gate2=c.gated and c.rows * c.co // 4 > 4096 * 256)
 
 
 @functools.lru_cache(maxsize=None)
@@ -106,6 +132,7 @@ def _tap_case(name):
 @pytest.mark.parametrize("name", list(TAP_CASES))
 def test_tapgemm_forward(name, parity):
     c = _tap_case(name)
+    assert _plan(c) == PLANS.get(name, ONE_PASS), _plan(c)
     big, Y = _guarded(c.rows, c.co)
     args = (_g(c.X), _g(c.W), _g(c.b), c.offs, c.B, c.Tsrc, c.Tdst, c.N)
     if c.gated:
@@ -126,6 +153,7 @@ def test_tapgemm_backward(name, parity):
     """dPre (the gate's backward from the kept tanh and sigmoid), dW of every tap (the zero-pattern taps too) and db, dX with a second
     gradient added in the epilogue at the residual's offset; a second run gives the same bits"""
     c = _tap_case(name)
+    assert _plan(c) == PLANS.get(name, ONE_PASS), _plan(c)
     X, W, XM = _g(c.X), _g(c.W), _g(c.XM)
 
     def run():
@@ -168,6 +196,29 @@ def test_graphgrad(N, unit_list, parity):
     _check(parity, errs)
 
 
+#            N  units ks  c   units per split, and whether the last split is shorter
+GG_STEPS = [(170, 57, 4, 32, 3, False), (170, 58, 4, 32, 3, True), (37, 600, 4, 16, 3, False), (37, 1, 4, 64, 1, False)]
+
+
+@pytest.mark.parametrize("N,units,ks,c,ups,ragged", GG_STEPS)
+def test_graphgrad_several_steps(N, units, ks, c, ups, ragged, parity):
+    """a workgroup's register-prefetch pipeline (the next stage's loads beside this stage's MFMAs) over two stages and more: several units per
+    split (36 and 4 tiles of 64 x 64 per split against 1024 workgroups), or the two 32-channel groups of c = 64 alone.  Every case above
+    this one has one unit per split and c <= 32, so one stage"""
+    ns = _C.lib().value("gptst_mtgnn_graphgrad_nsplit", units, N, ks)
+    got_ups = -(-units // ns)
+    steps = got_ups * (-(-c // 32))
+    assert got_ups == ups and steps >= 2 and (units - (ns - 1) * ups < ups) == ragged, (ns, got_ups, steps)
+    g = torch.Generator().manual_seed(N + units)
+    D = torch.randn(units * N, 16 + ks * c, dtype=torch.float64, generator=g)
+    X = torch.randn(units * N, c, dtype=torch.float64, generator=g)
+    want = torch.einsum("uvkc,uwc->kvw", D[:, 16:].view(units, N, ks, c), X.view(units, N, c))
+    got = ops.mtgnn_graphgrad(_g(D), _g(X), N, c, ks, dcol0=16)
+    assert got.shape == (ks, N, N)
+    _check(parity, {"u%d c%d ks%d" % (units, c, ks): _err(got, want)})
+    assert torch.equal(ops.mtgnn_graphgrad(_g(D), _g(X), N, c, ks, dcol0=16), got)
+
+
 # ---- 3. the whole model ----------------------------------------------------------------------------------------------------------------------
 CONF = dict(input_window=12, output_window=12, gcn_true=True, buildA_true=True, gcn_depth=2, node_dim=40, dilation_exponential=1,
             conv_channels=32, residual_channels=32, skip_channels=64, end_channels=128, layers=3, propalpha=0.05, tanhalpha=3,
@@ -208,11 +259,15 @@ def _inject(m, masks, rows_layout):
 
 
 @functools.lru_cache(maxsize=None)
-def _model_pair(B, N, out, k, p, C=64):
+def _model_pair(B, N, out, k, p, C=64, ds=None):
     """the torch module in fp64 on the CPU (default init; biases and LayerNorm weights moved off 0 / 1; no tie at a top-k cut), its HIP twin, a
-    batch, and the fp64 results"""
+    batch, and the fp64 results.  ds: the predictor's arguments are those of conf/MTGNN/<ds>.conf (and N, out, k, p must be its values)"""
     torch.manual_seed(7 + N + out)
-    m64 = MTGNN(_ap(N, out, k, p), "cpu", C, out).double().train()
+    ap = _ap(N, out, k, p)
+    if ds is not None:
+        ap = SimpleNamespace(**vars(predictor_args(ds, "MTGNN")), adj_mx=np.asarray(graph.synthetic_adjacency(N, 2), dtype=np.float32))
+        assert (ap.num_nodes, ap.output_dim, ap.subgraph_size, ap.dropout) == (N, out, k, p)
+    m64 = MTGNN(ap, "cpu", C, out).double().train()
     with torch.no_grad():
         for name, q in m64.named_parameters():
             if name.startswith("norm.") or name.endswith(".bias"):
@@ -223,7 +278,7 @@ def _model_pair(B, N, out, k, p, C=64):
     masks = _masks(m64, B, p, N)
     _inject(m64, masks, False)
     ref = _run(m64, x64, w64)
-    m = MTGNN(_ap(N, out, k, p), DEV, C, out, backend="hip").to(DEV).train()
+    m = MTGNN(ap, DEV, C, out, backend="hip").to(DEV).train()
     m.load_state_dict({n: v.float() for n, v in m64.state_dict().items()}, strict=True)
     _inject(m, masks, True)
     return m, m64, _g(x64), _g(w64), ref
@@ -249,6 +304,19 @@ def test_whole_model_against_fp64_torch(B, N, out, k, p, parity):
             assert same_support(m.adjacency(), m64.adjacency())
     got = _run(m, x, w)
     assert m.backend_used == "hip" and got[0].shape == (B, 12, N, out)
+    _check(parity, _errs(got, ref))
+
+
+@pytest.mark.parametrize("ds,N,out,k", [("METR_LA", 207, 1, 20), ("NYC_BIKE", 250, 2, 40), ("NYC_TAXI", 266, 2, 20)])
+def test_shipped_mtgnn_configuration_against_fp64_torch(ds, N, out, k, parity):
+    """the predictor as ``-mode eval -model MTGNN`` builds it from conf/MTGNN/<dataset>.conf (NYC_BIKE: subgraph_size 40, end_channels 64) over
+    a synthetic adjacency, one batch element of the 64-wide embedding, the conf's dropout 0.3 with injected masks"""
+    m, m64, x, w, ref = _model_pair(1, N, out, k, 0.3, 64, ds)
+    assert (m.end_conv_1.out_channels == 64) == (ds == "NYC_BIKE")
+    with torch.no_grad():                                # a precondition on the input: both precisions keep the same top-k set
+        assert same_support(m.adjacency(), m64.adjacency())
+    got = _run(m, x, w)
+    assert m.backend_used == "hip" and got[0].shape == (1, 12, N, out)
     _check(parity, _errs(got, ref))
 
 

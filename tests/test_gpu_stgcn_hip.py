@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from gptst_amd import graph, synth
-from gptst_amd.config import make_args
+from gptst_amd import _C, graph, ops, synth
+from gptst_amd.config import make_args, predictor_args
 from gptst_amd.predictors import STGCN, stgcn as S, stgcn_hip as H
 from golden_util import load
 from oracle import gptst_oracle as O
@@ -45,9 +45,49 @@ def _gpu_copy(m64):
 TCONV = [(64, 32, 3, "GLU"), (32, 64, 3, "relu"), (32, 128, 3, "relu"), (128, 128, 3, "GLU"), (128, 128, 1, "sigmoid")]
 
 
+def _cps(rows, cw, ktot):
+    """64-row chunks one split of the weight gradient sums: ceil(ceil(rows / 64) / nsplit)"""
+    ns = _C.lib().value("gptst_stgcn_wgrad_nsplit", rows, cw, ktot)
+    nchunks = -(-rows // 64)
+    return -(-nchunks // ns)
+
+
+def _tconv_plan(ci, co, kt, act, rows):
+    """what the launch plans of csrc/stgcn.hip make of a temporal convolution and its backward: tiles per wave of the forward and of the data
+    backward (the plan queries of include/gptst_hip_testing.h), 64-row chunks per split of the weight gradient, float4s of the gate backward"""
+    v = _C.lib().value
+    cw, ktot = (2 * co if act == "GLU" else co), kt * ci + (ci if ci > co else 0)
+    ntap = ktot // ci
+    return SimpleNamespace(ktot=ktot, fwd=v("gptst_stgcn_tapgemm_tpw", rows, co, ktot, H._ACT[act]),
+                           bwd=v("gptst_stgcn_tapgemm_tpw", rows, ci, ntap * cw, H.ACT_NONE), cps=_cps(rows, cw, ktot), n4=rows * co // 4)
+
+
 @pytest.mark.parametrize("btn", [(2, 12, 20), (1, 3, 37)])
 @pytest.mark.parametrize("ci,co,kt,act", TCONV)
 def test_temporal_convolution(ci, co, kt, act, btn, parity):
+    _tconv_case(ci, co, kt, act, btn, parity)
+
+
+# Shapes at which a wave's loop over its row tiles, a split's loop over its 64-row chunks and the gate backward's grid-stride loop run more than
+# once, as they do at every real batch (130 560 rows and more).  N = 461 is no multiple of 16; 16 596 rows are 1 038 tiles and 33 192 rows
+# 2 075 tiles, against 1 024 waves: the tile count is no multiple of the wave count, so the last wave ends early and some get no tile.
+#              ci   co  kt  act    (B, T, N)     tiles per wave: forward, data backward
+TCONV_MULTI = [(128, 128, 3, "GLU", (3, 12, 461), 2, 2),
+               (128, 128, 3, "GLU", (6, 12, 461), 3, 3),          # and 1 062 144 float4s in the gate backward: a second grid-stride pass
+               (128, 64, 3, "GLU", (3, 12, 461), 2, 2)]           # Ktot = 512 > 384 (the align block joins K): the narrow kernel, forward too
+
+
+@pytest.mark.parametrize("ci,co,kt,act,btn,fwd,bwd", TCONV_MULTI)
+def test_temporal_convolution_multi_tile(ci, co, kt, act, btn, fwd, bwd, parity):
+    plan = _tconv_plan(ci, co, kt, act, btn[0] * btn[1] * btn[2])
+    assert (plan.fwd, plan.bwd) == (fwd, bwd) and plan.cps >= 2, vars(plan)
+    assert (plan.ktot > 384) == (ci > co)
+    if btn[0] == 6:
+        assert plan.n4 > 4096 * 256, plan.n4
+    _tconv_case(ci, co, kt, act, btn, parity)
+
+
+def _tconv_case(ci, co, kt, act, btn, parity):
     B, T, N = btn
     torch.manual_seed(ci + co + kt + N)
     m64 = S._TConv(kt, ci, co, act).double()
@@ -67,9 +107,35 @@ def test_temporal_convolution(ci, co, kt, act, btn, parity):
     _check(parity, errs)
 
 
+def test_wgrad_three_chunks_per_split_and_a_short_last_split(parity):
+    """ops.stgcn_wgrad alone, cw = 256 and Ktot = 384 (24 tiles, so at most 42 splits) over 5 424 rows = 85 chunks (the last one of 48 rows):
+    29 splits of 3 chunks, the last split with ONE chunk.  dW and db against the fp64 sums with the taps' 'same' padding in T"""
+    B, T, N, ci, cw, taps = 2, 12, 226, 128, 256, (-1, 0, 1)
+    rows, ktot = B * T * N, 3 * ci
+    ns = _C.lib().value("gptst_stgcn_wgrad_nsplit", rows, cw, ktot)
+    nchunks, cps = -(-rows // 64), _cps(rows, cw, ktot)
+    assert (nchunks, ns, cps) == (85, 29, 3) and nchunks - (ns - 1) * cps == 1
+    g = torch.Generator().manual_seed(226)
+    D, X = torch.randn(rows, cw, dtype=torch.float64, generator=g), torch.randn(rows, ci, dtype=torch.float64, generator=g)
+    x4, want = X.view(B, T, N, ci), []
+    for dt in taps:                                                                # X[b, t + dt, n] where that is inside [0, T), else 0
+        sh = torch.zeros_like(x4)
+        sh[:, max(0, -dt):T - max(0, dt)] = x4[:, max(0, dt):T - max(0, -dt)]
+        want.append(D.t() @ sh.view(rows, ci))
+    dW, db = ops.stgcn_wgrad(D.float().to(DEV), X.float().to(DEV), taps, T, N)
+    _check(parity, {"dW": _err(dW, torch.cat(want, 1)), "db": _err(db, D.sum(0))})
+
+
 # ---- 2. graph convolution ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("N", [20, 37, 170])
+def _nodemix_lds(N):
+    """bytes of dynamic LDS of the node-mix launch: 36 floats for each of the 16 ceil(N / 16) padded nodes (SG_NM_P of csrc/stgcn.hip)"""
+    return 16 * ((N + 15) // 16) * 36 * 4
+
+
+@pytest.mark.parametrize("N", [20, 37, 170, 461])
 def test_graph_convolution(N, parity):
+    """(N = 461: a slab of 66 816 bytes, beyond the 64 KB a launch gets without asking for more)"""
+    assert (_nodemix_lds(N) > 64 * 1024) == (N == 461)
     B, T, c = 1, 2, 32
     torch.manual_seed(N)
     lk = torch.randn(3, N, N, dtype=torch.float64) / N ** 0.5            # non-symmetric: a transposed L_k in the backward shows
@@ -86,10 +152,37 @@ def test_graph_convolution(N, parity):
                     "b": _err(m.b.grad, m64.b.grad)})
 
 
+def test_nodemix_reduce_beyond_64_kb_of_lds(parity):
+    """ops.stgcn_nodemix alone at N = 461: Y = sum_k L_k Z_k + R for three non-symmetric graphs, 48 channels (a whole 32-channel group and a half
+    one) and two units, against fp64"""
+    N, ks, c, units = 461, 3, 48, 2
+    assert _nodemix_lds(N) == 66816 > 64 * 1024
+    g = torch.Generator().manual_seed(461)
+    L = torch.randn(ks, N, N, dtype=torch.float64, generator=g) / N ** 0.5
+    Z, R = torch.randn(units * N, ks * c, dtype=torch.float64, generator=g), torch.randn(units * N, c, dtype=torch.float64, generator=g)
+    want = torch.einsum("knm,umkc->unc", L, Z.view(units, N, ks, c)).reshape(units * N, c) + R
+    Np = 16 * ((N + 15) // 16)
+    Lp = torch.zeros(ks, Np, Np, dtype=torch.float64)
+    Lp[:, :N, :N] = L
+    got = ops.stgcn_nodemix(Lp.float().to(DEV), Z.float().to(DEV), N, c, reduce=True, res=R.float().to(DEV))
+    _check(parity, {"y": _err(got, want)})
+
+
 # ---- 3. LayerNorm ------------------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("N,C", [(20, 64), (37, 128), (170, 128)])
 def test_layernorm(N, C, parity):
-    units = 3
+    _layernorm_case(N, C, 3, parity)
+
+
+def test_layernorm_several_units_per_split(parity):
+    """40 units against at most 16 splits: 14 splits of 3 units, the last one with a single unit (3 units, as above, are one unit per split)"""
+    ns = _C.lib().value("gptst_stgcn_ln_nsplit", 40)
+    ups = -(-40 // ns)
+    assert ups >= 2 and 40 - (ns - 1) * ups == 1, (ns, ups)
+    _layernorm_case(20, 64, 40, parity)
+
+
+def _layernorm_case(N, C, units, parity):
     torch.manual_seed(N + C)
     ln64 = torch.nn.LayerNorm([N, C]).double()
     with torch.no_grad():
@@ -129,10 +222,10 @@ def test_whole_model_against_the_reference_vectors(parity):
     _check(parity, errs)
 
 
-def _model_pair(B, T, N, dim_out, seed):
+def _model_pair(B, T, N, dim_out, seed, ap=None):
     """the torch module in fp64 on the CPU (default init, LayerNorm parameters perturbed), its HIP twin, and a batch with its fp64 results"""
     torch.manual_seed(seed)
-    ap = _ap(N)
+    ap = _ap(N) if ap is None else ap
     m64 = STGCN(ap, "cpu", 64, dim_out).double()
     with torch.no_grad():
         for k, p in m64.named_parameters():
@@ -149,7 +242,23 @@ def _model_pair(B, T, N, dim_out, seed):
 
 @pytest.mark.parametrize("B,T,N,dim_out", [(3, 12, 37, 2), (1, 12, 170, 1), (2, 3, 16, 1)])
 def test_whole_model_against_fp64_torch(B, T, N, dim_out, parity):
-    m64, x64, w64, y64, m = _model_pair(B, T, N, dim_out, 5 + N)
+    _whole_model(_model_pair(B, T, N, dim_out, 5 + N), parity)
+
+
+@pytest.mark.parametrize("ds", ["METR_LA", "NYC_BIKE", "NYC_TAXI"])
+def test_shipped_stgcn_configuration_against_fp64_torch(ds, parity):
+    """the predictor as ``-mode eval -model STGCN`` builds it from conf/STGCN/<dataset>.conf (207, 250 and 266 nodes; the output width is the
+    dataset's) over a synthetic graph, one batch element of the 64-wide embedding"""
+    pa = predictor_args(ds, "STGCN")
+    N, dim_out = pa.num_nodes, make_args(ds).output_dim
+    assert (N, dim_out) == {"METR_LA": (207, 1), "NYC_BIKE": (250, 2), "NYC_TAXI": (266, 2)}[ds]
+    ap = SimpleNamespace(Ks=pa.Ks, Kt=pa.Kt, num_nodes=N, G=graph.stgcn_graph(graph.synthetic_adjacency(N, 2)), blocks1=list(pa.blocks1),
+                         drop_prob=pa.drop_prob, outputl_ks=pa.outputl_ks)
+    _whole_model(_model_pair(1, pa.input_window, N, dim_out, 5 + N, ap), parity)
+
+
+def _whole_model(pair, parity):
+    m64, x64, w64, y64, m = pair
     m.train()
     x = x64.detach().float().to(DEV).requires_grad_(True)
     y = m(x)

@@ -8,8 +8,8 @@ import numpy as np
 import pytest
 import torch
 
-from gptst_amd import graph, ops, synth
-from gptst_amd.config import make_args
+from gptst_amd import _C, graph, ops, synth
+from gptst_amd.config import make_args, predictor_args
 from gptst_amd.predictors import TGCN, tgcn_hip as H
 from golden_util import load
 from oracle import gptst_oracle as O
@@ -37,8 +37,16 @@ def _g(t):
 
 
 # ---- 1. the four step launches, each alone -------------------------------------------------------------------------------------------------
-STEP_SHAPES = [(1, 16, 32), (3, 37, 112), (2, 170, 112)]
+# (1, 461, 112): 464 padded nodes, a slab of 126 208 bytes plus the M tile: every one of the four launches asks for more than the 64 KB of dynamic
+# LDS a launch gets by default, up to 155 392 bytes (backward state, two tiles), just under the 160 KB a workgroup can have
+STEP_SHAPES = [(1, 16, 32), (3, 37, 112), (2, 170, 112), (1, 461, 112)]
 T2, T1 = 2, 1                # two steps in the seq tensors, the launch works on the second: a wrong (b, t) row offset shows
+
+
+def test_step_shapes_reach_beyond_64_kb_of_lds():
+    v = _C.lib().value
+    assert v("gptst_tgcn_lds_bytes", 461, 112, 1) == (464 * 68 + 16 * 228) * 4 > 126208 > 64 * 1024        # (one tile: the plan for B = 1)
+    assert all(v("gptst_tgcn_lds_bytes", N, Hp, B) <= 64 * 1024 for B, N, Hp in STEP_SHAPES[:3])
 
 
 def _step_inputs(B, N, Hp, seed):
@@ -165,6 +173,42 @@ def test_whole_model_against_fp64_torch(B, T, N, C, Hd, out, parity):
     got = _run(m, x, w)
     assert m.backend_used == "hip" and got[0].shape == (B, T, N, out)
     _check(parity, _errs(got, ref))
+
+
+@pytest.mark.parametrize("ds", ["METR_LA", "NYC_BIKE", "NYC_TAXI"])
+def test_shipped_tgcn_configuration_against_fp64_torch(ds, parity):
+    """the predictor as ``-mode eval -model TGCN`` builds it from conf/TGCN/<dataset>.conf (207, 250 and 266 nodes) over a synthetic graph, one
+    batch element of the 64-wide embedding"""
+    pa = predictor_args(ds, "TGCN")
+    assert (pa.num_nodes, pa.output_dim) == {"METR_LA": (207, 1), "NYC_BIKE": (250, 2), "NYC_TAXI": (266, 2)}[ds]
+    m, x, w, ref = _model_pair(1, pa.input_window, pa.num_nodes, 64, pa.rnn_units, pa.output_dim, 5 + pa.num_nodes)
+    m.train()
+    got = _run(m, x, w)
+    assert m.backend_used == "hip" and got[0].shape == (1, pa.output_window, pa.num_nodes, pa.output_dim)
+    _check(parity, _errs(got, ref))
+
+
+def test_lds_limit_depends_on_the_batch(parity):
+    """N = 500 with 128 units: 512 padded nodes, a slab of 139 264 bytes.  A batch of 2 is planned with one row tile per workgroup, 155 904 bytes,
+    and runs on the kernels; a batch of 17 is planned with two, 172 544 bytes, beyond the 160 KB of a workgroup: ``supported`` says no, and the
+    SAME module answers through torch, bit for bit what a torch-backend twin gives"""
+    N, Hd, C, T = 500, 128, 64, 3
+    v = _C.lib().value
+    assert v("gptst_tgcn_lds_bytes", N, Hd, 2) == 155904 <= H.LDS_MAX < v("gptst_tgcn_lds_bytes", N, Hd, 17) == 172544
+    m, x, w, ref = _model_pair(2, T, N, C, Hd, 1, 5 + N + Hd)
+    m.train()
+    assert H.supported(m, x)
+    got = _run(m, x, w)
+    assert m.backend_used == "hip"
+    _check(parity, _errs(got, ref))
+    mt = TGCN(_ap(N, T, Hd, 1), DEV, C).to(DEV)
+    mt.load_state_dict(m.state_dict(), strict=True)
+    x17 = torch.randn(17, T, N, C, device=DEV)
+    assert not H.supported(m, x17)
+    yh, yt = m(x17), mt(x17)
+    assert m.backend_used == "torch" and mt.backend_used == "torch" and yh.shape == (17, T, N, 1) and torch.equal(yh, yt)
+    m(x)                                                                          # and the small batch is served by the kernels again
+    assert m.backend_used == "hip"
 
 
 def test_whole_model_against_the_reference_vectors(parity):
