@@ -78,6 +78,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-tgcn_backend", default=FINETUNE_DEFAULTS["tgcn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the MTGNN predictor (predictors/mtgnn_hip.py)
     ap.add_argument("-mtgnn_backend", default=FINETUNE_DEFAULTS["mtgnn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the ASTGCN predictor (predictors/astgcn_hip.py)
+    ap.add_argument("-astgcn_backend", default=FINETUNE_DEFAULTS["astgcn_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -89,7 +91,8 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
-FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch")
+FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
+                         astgcn_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -128,14 +131,18 @@ _MTGNN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data
                ("model", "end_channels", int), ("model", "layers", int), ("model", "propalpha", float), ("model", "tanhalpha", int),
                ("model", "layer_norm_affline", _EVAL), ("model", "use_curriculum_learning", _EVAL), ("model", "task_level", int),
                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
-_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS}
+# reference model/ASTGCN/args.py.  `xavier` is True in all four confs: the attention and Theta parameters have no other initialisation.
+_ASTGCN_KEYS = [("data", "num_nodes", int), ("data", "len_input", int), ("data", "num_for_predict", int), ("model", "nb_block", int),
+                ("model", "K", int), ("model", "nb_chev_filter", int), ("model", "nb_time_filter", int), ("model", "time_strides", int),
+                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN and MTGNN are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN and ASTGCN are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN and MTGNN predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN and ASTGCN predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)

@@ -5,6 +5,7 @@ gradient dict ``g`` (views into one flat buffer) and returns the input gradients
 state_dict keys to tensors.  Citations: reference model/Pretrain_model/GPTST.py.
 """
 import contextlib
+import gc
 import os
 import threading
 from typing import Any, NamedTuple
@@ -1121,3 +1122,27 @@ def warm_up(fn):
             fn()
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
+
+
+_GC_LOCK, _GC_HELD = threading.Lock(), [0, False]      # captures under way (ranks emulated by threads capture side by side), collector was on
+
+
+@contextlib.contextmanager
+def quiet_gc():
+    """Around a graph capture: collect Python's dead cycles first, then keep the cyclic collector off until the last capture under way has ended.
+    A collection that starts in the middle of a capture runs the destructors of whatever dead cycle it finds — another stepper's CUDAGraph
+    objects, tensors of another stream, events — on the capturing thread, and the runtime aborts the process on calls a capture does not allow.
+    ``torch.cuda.graph`` collects on entry only under ``torch.compiler.config.force_cudagraph_gc`` and never holds the collector off."""
+    with _GC_LOCK:
+        if _GC_HELD[0] == 0:
+            gc.collect()
+            _GC_HELD[1] = gc.isenabled()
+            gc.disable()
+        _GC_HELD[0] += 1
+    try:
+        yield
+    finally:
+        with _GC_LOCK:
+            _GC_HELD[0] -= 1
+            if _GC_HELD[0] == 0 and _GC_HELD[1]:
+                gc.enable()

@@ -22,6 +22,16 @@ class Fusion(nn.Module):                                                   # mod
         return self.output_fc(z * flow_eb + (1 - z) * time_eb)
 
 
+def xavier_downstream_(model):
+    """The reference Run.py:79-85 in eval mode: ``xavier_uniform_`` for dim > 1, else ``uniform_``, in ``named_parameters`` order, over what is
+    trained on top of the pretrained encoder — the fusion gate, ``lin_test`` and the predictor.  Never the encoder: in the reference it is frozen
+    when the pass runs; under ``finetune_encoder`` its parameters do require gradients here, and re-drawing them would throw the pretraining away."""
+    for k, p in model.named_parameters():
+        if p.requires_grad and not k.startswith("pretrain_model."):
+            nn.init.xavier_uniform_(p) if p.dim() > 1 else nn.init.uniform_(p)
+    return model
+
+
 class EnhanceFrontEnd(nn.Module):
     """``Enhance_model`` in ``mode='eval'`` (model/Model.py:40-46,91-107): frozen pretrained encoder -> fusion with a linear lift
     of the raw flow -> predictor.  ``predictor=None`` returns the fused embedding.  ``finetune_encoder=True`` unfreezes the encoder path

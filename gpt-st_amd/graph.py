@@ -63,6 +63,13 @@ def stgcn_graph(A, Ks=3):
     return torch.tensor(cheb_polynomials(scaled_laplacian(A), Ks), dtype=torch.float32)
 
 
+def astgcn_graph(A, K):
+    """The (K, N, N) fp32 Chebyshev polynomials ``predictors.ASTGCN`` masks with its spatial attention (reference ASTGCN.py:8-47,284-286).  The
+    reference takes lambda_max from ARPACK (scipy ``eigs(k=1, which='LR')``), this project from the dense eigenvalues: the two agree to ARPACK's
+    stopping tolerance (tests/golden/make_golden_astgcn.py prints the difference it measures)."""
+    return torch.tensor(cheb_polynomials(scaled_laplacian(A), K), dtype=torch.float32)
+
+
 def normalized_adjacency(A):
     """TGCN's graph (reference TGCN.py:8-25, ``calculate_normalized_laplacian``): with A~ = A + I and D = diag(row sums of A~), the reference's
     operand order (A~ D^-1/2)^T D^-1/2 = D^-1/2 A~^T D^-1/2 — for a non-symmetric A the TRANSPOSE of the textbook D^-1/2 A~ D^-1/2."""

@@ -156,14 +156,14 @@ class GraphedPretrain:
             self.ctrl.copy_(torch.tensor(list(range(self.HS)) + [self.M // 8, self.M // 8], dtype=torch.int32))      # plausible budgets for the warm-up
             engine.warm_up(self._fwd_body)
             self.gf = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.gf, capture_error_mode="thread_local"):
+            with engine.quiet_gc(), torch.cuda.graph(self.gf, capture_error_mode="thread_local"):
                 self._fwd_body()
 
     def _capture_bwd(self, has_kl):
         with torch.no_grad():
             engine.warm_up(lambda: self._bwd_body(has_kl))
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local"):
+            with engine.quiet_gc(), torch.cuda.graph(g, pool=self.gf.pool(), capture_error_mode="thread_local"):
                 self._bwd_body(has_kl)
         self.gb[has_kl] = g
 

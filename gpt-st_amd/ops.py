@@ -1299,3 +1299,60 @@ def mtgnn_graphgrad(D, X, N, c, ks, dcol0=0):
     _call("gptst_mtgnn_graphgrad", _p(D), D.shape[1], dcol0, _p(X), c, c, ks, _p(part), ns, units, N, tag="c%d ks%d" % (c, ks),
           nbytes=rows * (ks + 1) * c * 4 + part.numel() * 4)
     return part.sum(0)
+
+
+# ---- the downstream ASTGCN predictor (csrc/astgcn.hip) ----------------------------------------------------------------------------------
+def astgcn_attmix(Tp, S, In, T, c, reduce, res=None):
+    """node mixing with the per-sample masked graph T_k * S_b (never written).  Tp (ks, Np, Np) zero-padded, S (B, N, N).
+    reduce False: In (rows, c) -> (rows, ks c), Out[(b,t,n), k c + ch] = sum_m T_k[m,n] S[b,m,n] In[(b,t,m), ch];
+    True: In (rows, ks c) -> (rows, c), Out[(b,t,m), ch] = sum_k sum_n T_k[m,n] S[b,m,n] In[(b,t,n), k c + ch] + res"""
+    _chk(Tp, S, In, res)
+    ks, Np = Tp.shape[0], Tp.shape[1]
+    B, N = S.shape[0], S.shape[1]
+    rows = In.shape[0]
+    assert In.shape[1] == (ks * c if reduce else c) and rows == B * T * N and S.shape[2] == N
+    Out = torch.empty(rows, c if reduce else ks * c, device=In.device, dtype=torch.float32)
+    _call("gptst_astgcn_attmix", _p(Tp), Np, ks, _p(S), _p(In), _p(Out), _p(res), c, int(reduce), B, T, N, tag="c%d r%d" % (c, int(reduce)),
+          nbytes=_nb(In, Out, res, S, Tp))
+    return Out
+
+
+def astgcn_attgrad(Tp, X, G, B, T, N):
+    """-> dS (B, N, N) = sum_k T_k[m,n] sum_{t,ch} X[(b,t,m), ch] G[(b,t,n), k c + ch]: the gradient of astgcn_attmix (reduce False: X = In,
+    G = dOut) with respect to S"""
+    _chk(Tp, X, G)
+    ks, Np = Tp.shape[0], Tp.shape[1]
+    c = X.shape[1]
+    assert X.shape[0] == B * T * N and G.shape == (B * T * N, ks * c)
+    dS = torch.empty(B, N, N, device=X.device, dtype=torch.float32)
+    _call("gptst_astgcn_attgrad", _p(Tp), Np, ks, _p(X), _p(G), _p(dS), c, B, T, N, tag="c%d" % c, nbytes=_nb(X, G, dS, Tp))
+    return dS
+
+
+def astgcn_rowln_fwd(X, gamma, beta, eps, keep=True):
+    """LayerNorm over the c values of each row of X (rows, c) -> (Y, mean, rstd) (mean, rstd None when not kept)"""
+    _chk(X, gamma, beta)
+    rows, c = X.shape
+    Y = torch.empty_like(X)
+    mean, rstd = (torch.empty(rows, device=X.device, dtype=torch.float32) for _ in range(2)) if keep else (None, None)
+    _call("gptst_astgcn_rowln_fwd", _p(X), _p(gamma), _p(beta), _p(Y), _p(mean), _p(rstd), rows, c, float(eps), tag="c%d" % c, nbytes=_nb(X, Y))
+    return Y, mean, rstd
+
+
+def astgcn_rowln_bwd(dY, X, gamma, mean, rstd):
+    """-> dX of the LayerNorm over each row"""
+    _chk(dY, X, gamma, mean, rstd)
+    rows, c = X.shape
+    dX = torch.empty_like(X)
+    _call("gptst_astgcn_rowln_bwd", _p(dY), _p(X), _p(gamma), _p(mean), _p(rstd), _p(dX), rows, c, tag="c%d" % c, nbytes=_nb(dY, X, dX))
+    return dX
+
+
+def astgcn_rowln_bwd_param(dY, X, mean, rstd):
+    """-> (dgamma, dbeta) (c values each): row-split partials summed in a fixed order"""
+    _chk(dY, X, mean, rstd)
+    rows, c = X.shape
+    ns = _C.lib().value("gptst_astgcn_rowln_nsplit", rows)
+    pg, pb = (torch.empty(ns, c, device=X.device, dtype=torch.float32) for _ in range(2))
+    _call("gptst_astgcn_rowln_bwd_param", _p(dY), _p(X), _p(mean), _p(rstd), _p(pg), _p(pb), ns, rows, c, tag="c%d" % c, nbytes=_nb(dY, X))
+    return pg.sum(0), pb.sum(0)

@@ -466,7 +466,7 @@ class PretrainStep:
         keep = (self.model.flat.clone(), self.m.clone(), self.v.clone())
         engine.warm_up(lambda: self._body(phase))
         try:
-            with self._launch_mode():
+            with self._launch_mode(), engine.quiet_gc():
                 g1 = torch.cuda.CUDAGraph()
                 if self._needs_exchange(phase) and not self._dp_in_graph():
                     with torch.cuda.graph(g1, capture_error_mode="thread_local"):      # other threads (RCCL watchdog) may call the runtime meanwhile
@@ -598,7 +598,7 @@ class PretrainStep:
             torch.cuda.synchronize()
             raise RuntimeError("a group of %d steps would need ~%.0f GB of activations (device: %.0f GB)" % (K, per_step * K / 2**30, total / 2**30))
         try:
-            with self._launch_mode():
+            with self._launch_mode(), engine.quiet_gc():
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g, capture_error_mode="thread_local"):
                     for j in range(K):

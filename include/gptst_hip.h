@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 20  /* 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 21  /* 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -507,6 +507,27 @@ int gptst_mtgnn_wgrad(const float* D, int cw, const float* X, int ldx, int ci, c
 int gptst_mtgnn_graphgrad_nsplit(int units, int N, int ks);
 int gptst_mtgnn_graphgrad(const float* D, int ldd, int dcol0, const float* X, int ldx, int c, int ks, float* part, int nsplit, int units,
                           int N, void* stream);
+/* ---- the downstream ASTGCN predictor (astgcn.hip; reference model/ASTGCN/ASTGCN.py, gpt-st_amd/predictors/astgcn_hip.py) --------------------
+ * Rows as for STGCN: (b T + t) N + n.  Tp (ks, Np, Np): the Chebyshev polynomials zero-padded to Np = 16 ceil(N / 16); S (B, N, N): the spatial
+ * attention of every sample, unpadded; ks <= 3; c a multiple of 16.  The masked graph T_k * S_b is formed in LDS and never written.
+ * attmix, reduce = 0: In (rows, c) -> Out (rows, ks c), Out[(b,t,n), k c + ch] = sum_m T_k[m,n] S[b,m,n] In[(b,t,m), ch];
+ *         reduce = 1: In (rows, ks c) -> Out (rows, c), Out[(b,t,m), ch] = sum_k sum_n T_k[m,n] S[b,m,n] In[(b,t,n), k c + ch] + R (R may be NULL).
+ *         ESHAPE when Np > 320 (the masked tiles and the slab, Np (20 ks + 68) floats, fit 160 KB of LDS up to there).
+ * attgrad: dS (B, N, N), dS[b,m,n] = sum_k T_k[m,n] sum_{t,ch} X[(b,t,m), ch] G[(b,t,n), k c + ch]; X (rows, c), G (rows, ks c).
+ * rowln_*: LayerNorm over the c <= 128 values of each row; mean, rstd (rows; both NULL: not kept); bwd_param: pg, pb (nsplit, c) = row-split
+ *   partials of dgamma, dbeta in a fixed order, nsplit = gptst_astgcn_rowln_nsplit(rows); the caller sums the splits. */
+int gptst_astgcn_attmix(const float* Tp, int Np, int ks, const float* S, const float* In, float* Out, const float* R, int c, int reduce,
+                        int B, int T, int N, void* stream);
+int gptst_astgcn_attgrad(const float* Tp, int Np, int ks, const float* X, const float* G, float* dS, int c, int B, int T, int N,
+                         void* stream);
+int gptst_astgcn_rowln_fwd(const float* X, const float* gamma, const float* beta, float* Y, float* mean, float* rstd, long rows, int c,
+                           float eps, void* stream);
+int gptst_astgcn_rowln_bwd(const float* dY, const float* X, const float* gamma, const float* mean, const float* rstd, float* dX, long rows,
+                           int c, void* stream);
+int gptst_astgcn_rowln_nsplit(long rows);
+int gptst_astgcn_rowln_bwd_param(const float* dY, const float* X, const float* mean, const float* rstd, float* pg, float* pb, int nsplit,
+                                 long rows, int c, void* stream);
+
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column
  * sums of X | sums of a'] for the caller to fold (one kind-1 pool job next to the other reductions of a step). */
