@@ -16,6 +16,7 @@
 // fp32 MFMA 16x16x4 throughout (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics.
 #include "common.h"
 #include "gptst_hip.h"
+#include "tap_wgrad_dev.h"
 
 #define MT_THREADS 256
 #define MT_KC 128                  // K chunk of the tap GEMM: 64 weight rows of 128 floats in LDS (33 KB)
@@ -171,71 +172,32 @@ __global__ __launch_bounds__(256) void mt_gate_bwd_kernel(const float* __restric
 
 // ---- weight gradient: part[z][o][k] = sum over the rows of split z of D[row][o] X[row's source row at tap(k)][k mod ci]; bpart[z][o] = column
 // sums of D.  D is in the destination frame, X in the source frame (sg_wgrad_kernel with the two frames and the tap table). ----
-#define MT_WG_P 80
-
 struct MtWg {
     const float* D; int cw; const float* X; int ldx; int ci; const float* XM; MtTaps tap; int Ktot;
     float* part; float* bpart; int rows, Tsrc, Tdst, N, cps, nchunks;
 };
 
+// the source of a destination row for this thread's columns: the same (b, n) at to + off in the source frame, times its mask
+struct MtWgSrc {
+    const MtWg& p; bool kv; int xc, off;
+    __device__ __forceinline__ MtWgSrc(const MtWg& p_, int kcol) : p(p_), kv(kcol < p_.Ktot) {
+        const int tp = kv ? kcol / p.ci : 0;
+        xc = kcol - tp * p.ci; off = p.tap.off[tp];
+    }
+    __device__ __forceinline__ float4 operator()(int row, bool rv) const {
+        const int n = row % p.N, bt = row / p.N, ts = bt % p.Tdst + off;
+        float4 x = f4zero();
+        if (rv && kv && ts >= 0 && ts < p.Tsrc) {
+            const long e = (((long)(bt / p.Tdst) * p.Tsrc + ts) * p.N + n) * p.ldx + xc;
+            x = ld4(p.X + e);
+            if (p.XM != nullptr) { const float4 m = ld4(p.XM + e); x = make_float4(x.x * m.x, x.y * m.y, x.z * m.z, x.w * m.w); }
+        }
+        return x;
+    }
+};
+
 __global__ __launch_bounds__(256) void mt_wgrad_kernel(MtWg p) {
-    __shared__ __attribute__((aligned(16))) float Dl[64 * MT_WG_P];
-    __shared__ __attribute__((aligned(16))) float Xl[64 * MT_WG_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
-    const int kb = blockIdx.x, cb = blockIdx.y, z = blockIdx.z;
-    const int ch0 = z * p.cps, ch1 = min(p.nchunks, ch0 + p.cps);
-    const int c4 = tid & 15, rb = tid >> 4;
-    const int dcol = cb * 64 + 4 * c4, kcol = kb * 64 + 4 * c4;
-    const bool dv = dcol < p.cw, kv = kcol < p.Ktot;
-    const int tp = kv ? kcol / p.ci : 0;
-    const int xc = kcol - tp * p.ci, off = p.tap.off[tp];
-    f32x4 acc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    float4 dr[4], xr[4];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = chunk * 64 + i * 16 + rb;
-            const bool rv = row < p.rows;
-            dr[i] = (rv && dv) ? ld4(p.D + (size_t)row * p.cw + dcol) : f4zero();
-            const int n = row % p.N, bt = row / p.N, ts = bt % p.Tdst + off;
-            xr[i] = f4zero();
-            if (rv && kv && ts >= 0 && ts < p.Tsrc) {
-                const long e = (((long)(bt / p.Tdst) * p.Tsrc + ts) * p.N + n) * p.ldx + xc;
-                xr[i] = ld4(p.X + e);
-                if (p.XM != nullptr) { const float4 m = ld4(p.XM + e); xr[i] = make_float4(xr[i].x * m.x, xr[i].y * m.y, xr[i].z * m.z, xr[i].w * m.w); }
-            }
-        }
-    };
-    if (ch0 < ch1) fetch(ch0);
-    for (int chunk = ch0; chunk < ch1; ++chunk) {
-        __syncthreads();                                   // the previous chunk's reads of the tiles are done
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { st4(Dl + (i * 16 + rb) * MT_WG_P + 4 * c4, dr[i]); st4(Xl + (i * 16 + rb) * MT_WG_P + 4 * c4, xr[i]); }
-        __syncthreads();
-        if (chunk + 1 < ch1) fetch(chunk + 1);
-        if (p.bpart != nullptr && kb == 0 && tid < 64) {
-            for (int rl = 0; rl < 64; ++rl) bsum += Dl[rl * MT_WG_P + tid];
-        }
-#pragma unroll 4
-        for (int s = 0; s < 16; ++s) {
-            const float a = Dl[(4 * s + kk) * MT_WG_P + 16 * wave + j];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Xl[(4 * s + kk) * MT_WG_P + 16 * nt + j], acc[nt], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int k = kb * 64 + 16 * nt + j;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = cb * 64 + 16 * wave + kk * 4 + r;
-            if (o < p.cw && k < p.Ktot) p.part[((size_t)z * p.cw + o) * p.Ktot + k] = acc[nt][r];
-        }
-    }
-    if (p.bpart != nullptr && kb == 0 && tid < 64 && cb * 64 + tid < p.cw) p.bpart[(size_t)z * p.cw + cb * 64 + tid] = bsum;
+    tap_wgrad_body(p.D, p.cw, p.Ktot, p.part, p.bpart, p.rows, p.cps, p.nchunks, MtWgSrc(p, blockIdx.x * 64 + 4 * (threadIdx.x & 15)));
 }
 
 // ---- gradient of the node mix with respect to its graphs: a 64 x 64 tile of dM_k per workgroup, 32 channels of one unit per stage ----

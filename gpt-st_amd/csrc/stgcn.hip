@@ -12,6 +12,7 @@
 // fp32 MFMA 16x16x4 throughout (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics.
 #include "common.h"
 #include "gptst_hip.h"
+#include "tap_wgrad_dev.h"
 
 #define SG_ACT_NONE 0
 #define SG_ACT_RELU 1
@@ -158,67 +159,26 @@ __global__ __launch_bounds__(256) void sg_gate_bwd_kernel(const float* __restric
 }
 
 // ---- weight gradient of a tap GEMM: part[z][o][k] = sum over the rows of split z of D[row][o] X_shift[row][k]; bpart[z][o] = column sums of D ----
-#define SG_WG_P 80          // pitch of the 64 x 64 LDS tiles: 80 mod 64 = 16, so the four k-rows of an operand read land on disjoint banks
-
 struct SgWg {
     const float* D; int cw; const float* X; int ldx; int ci; SgTap tap; int Ktot;
     float* part; float* bpart; int rows, T, N, cps, nchunks;
 };
 
+// the source of a row for this thread's columns: the row dt * N rows away, where its time step is inside [0, T)
+struct SgWgSrc {
+    const SgWg& p; bool kv; int xc, dt;
+    __device__ __forceinline__ SgWgSrc(const SgWg& p_, int kcol) : p(p_), kv(kcol < p_.Ktot) {
+        const int tp = kv ? kcol / p.ci : 0;
+        xc = kcol - tp * p.ci; dt = p.tap.dt[tp];
+    }
+    __device__ __forceinline__ float4 operator()(int row, bool rv) const {
+        const int ts = (row / p.N) % p.T + dt;
+        return (rv && kv && ts >= 0 && ts < p.T) ? ld4(p.X + ((long)row + (long)dt * p.N) * p.ldx + xc) : f4zero();
+    }
+};
+
 __global__ __launch_bounds__(256) void sg_wgrad_kernel(SgWg p) {
-    __shared__ __attribute__((aligned(16))) float Dl[64 * SG_WG_P];
-    __shared__ __attribute__((aligned(16))) float Xl[64 * SG_WG_P];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
-    const int kb = blockIdx.x, cb = blockIdx.y, z = blockIdx.z;
-    const int ch0 = z * p.cps, ch1 = min(p.nchunks, ch0 + p.cps);
-    // this thread's four float4 of either tile: row rl = i*16 + tid/16, columns 4 (tid % 16)
-    const int c4 = tid & 15, rb = tid >> 4;
-    const int dcol = cb * 64 + 4 * c4, kcol = kb * 64 + 4 * c4;
-    const bool dv = dcol < p.cw, kv = kcol < p.Ktot;
-    const int tp = kv ? kcol / p.ci : 0;
-    const int xc = kcol - tp * p.ci, dt = p.tap.dt[tp];
-    f32x4 acc[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float bsum = 0.f;
-    float4 dr[4], xr[4];
-    auto fetch = [&](int chunk) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const int row = chunk * 64 + i * 16 + rb;
-            const bool rv = row < p.rows;
-            dr[i] = (rv && dv) ? ld4(p.D + (size_t)row * p.cw + dcol) : f4zero();
-            const int ts = (row / p.N) % p.T + dt;
-            xr[i] = (rv && kv && ts >= 0 && ts < p.T) ? ld4(p.X + ((long)row + (long)dt * p.N) * p.ldx + xc) : f4zero();
-        }
-    };
-    if (ch0 < ch1) fetch(ch0);
-    for (int chunk = ch0; chunk < ch1; ++chunk) {
-        __syncthreads();                                   // the previous chunk's reads of the tiles are done
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { st4(Dl + (i * 16 + rb) * SG_WG_P + 4 * c4, dr[i]); st4(Xl + (i * 16 + rb) * SG_WG_P + 4 * c4, xr[i]); }
-        __syncthreads();
-        if (chunk + 1 < ch1) fetch(chunk + 1);
-        if (p.bpart != nullptr && kb == 0 && tid < 64) {
-            for (int rl = 0; rl < 64; ++rl) bsum += Dl[rl * SG_WG_P + tid];
-        }
-#pragma unroll 4
-        for (int s = 0; s < 16; ++s) {
-            const float a = Dl[(4 * s + kk) * SG_WG_P + 16 * wave + j];
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a, Xl[(4 * s + kk) * SG_WG_P + 16 * nt + j], acc[nt], 0, 0, 0);
-        }
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int k = kb * 64 + 16 * nt + j;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int o = cb * 64 + 16 * wave + kk * 4 + r;
-            if (o < p.cw && k < p.Ktot) p.part[((size_t)z * p.cw + o) * p.Ktot + k] = acc[nt][r];
-        }
-    }
-    if (p.bpart != nullptr && kb == 0 && tid < 64 && cb * 64 + tid < p.cw) p.bpart[(size_t)z * p.cw + cb * 64 + tid] = bsum;
+    tap_wgrad_body(p.D, p.cw, p.Ktot, p.part, p.bpart, p.rows, p.cps, p.nchunks, SgWgSrc(p, blockIdx.x * 64 + 4 * (threadIdx.x & 15)));
 }
 
 // ---- node mixing with the Chebyshev polynomials: one (b, t) unit and four 16-node tiles per workgroup ----

@@ -25,6 +25,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _backend
+
 
 class _TemporalAttention(nn.Module):
     """E (B, T, T) = softmax over dim 1 of Ve sigmoid(((x^T U1) U2)(U3 x) + be)   (ASTGCN.py:134-163)"""
@@ -107,9 +109,7 @@ class ASTGCN(nn.Module):
 
     def __init__(self, args, device, dim_in, dim_out, backend="torch"):
         super().__init__()
-        if backend not in ("torch", "hip"):
-            raise ValueError("ASTGCN backend must be 'torch' or 'hip', got %r" % (backend,))
-        self.backend, self.backend_used = backend, None
+        self.backend, self.backend_used = _backend.check("ASTGCN", backend), None
         a = args
         self.num_for_predict, self.dim_out, self.time_strides = a.num_for_predict, dim_out, a.time_strides
         self.register_buffer("cheb", a.G[:a.K].to(torch.float32), persistent=False)
@@ -125,15 +125,9 @@ class ASTGCN(nn.Module):
         return self.final_conv(h).reshape(h.shape[0], self.num_for_predict, self.dim_out, -1).transpose(-1, -2)
 
     def forward(self, x):                                                  # x (B, T, N, dim_in)
-        if self.backend == "hip":
-            from . import astgcn_hip
-            if astgcn_hip.supported(self, x):
-                self.backend_used = "hip"
-                if self.training and torch.is_grad_enabled():
-                    return astgcn_hip.forward(self, x, keep=True)
-                with torch.no_grad():                                      # eval mode: nothing is kept for a backward
-                    return astgcn_hip.forward(self, x, keep=False)
-        self.backend_used = "torch"
+        y = _backend.hip_forward(self, "astgcn_hip", x)
+        if y is not None:
+            return y
         h = x.permute(0, 2, 3, 1)
         for blk in self.BlockList:
             h = blk(h, self.cheb)

@@ -23,6 +23,8 @@ import torch.nn.functional as F
 
 from .. import _C, ops
 from ..ops import ACT_NONE, ACT_RELU
+from . import rows_hip
+from .rows_hip import TapFn, is_hip_input, widths_ok
 
 
 class _MixFn(torch.autograd.Function):
@@ -58,33 +60,6 @@ class _MixFn(torch.autograd.Function):
         return dx, dS, dTheta, None, None, None, None
 
 
-class _TapFn(torch.autograd.Function):
-    """y = act(sum_j x[t + taps[j]] W_j + b + res);  W (co, len(taps) * ci); res (rows, co) or None; act none or relu"""
-
-    @staticmethod
-    def forward(ctx, x, W, b, res, taps, act, T, N, keep):
-        keep = keep and any(ctx.needs_input_grad)
-        y = ops.stgcn_tapgemm(x, W, b, taps, act, T, N, res=res, res_w=W.shape[0] if res is not None else 0)
-        if keep:
-            ctx.cfg = (taps, act, T, N)
-            ctx.save_for_backward(x, W, y if act == ACT_RELU else None)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, W, y = ctx.saved_tensors
-        taps, act, T, N = ctx.cfg
-        dPre = ops.stgcn_gate_bwd(dy.contiguous(), act, out=y) if act == ACT_RELU else dy.contiguous()
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dW, db = ops.stgcn_wgrad(dPre, x, taps, T, N)
-        if ctx.needs_input_grad[0]:
-            co, ci = W.shape[0], x.shape[1]
-            Wb = W.view(co, len(taps), ci).permute(2, 1, 0).reshape(ci, len(taps) * co).contiguous()      # block j = W_j^T
-            dx = ops.stgcn_tapgemm(dPre, Wb, None, tuple(-t for t in taps), ACT_NONE, T, N)
-        return dx, dW, db, (dPre if ctx.needs_input_grad[3] else None), None, None, None, None, None
-
-
 class _RowLNFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta, eps, keep):
@@ -106,15 +81,8 @@ class _RowLNFn(torch.autograd.Function):
 
 
 def padded_graph(model):
-    """the polynomials zero-padded to 16-node tiles: built when the module's `cheb` is another tensor than last time, or was written to"""
-    g, c = model.cheb, getattr(model, "_tp_cache", None)
-    if c is None or c[0] is not g or c[1] != g._version:
-        ks, n = g.shape[0], g.shape[1]
-        npad = 16 * ((n + 15) // 16)
-        tp = g.new_zeros(ks, npad, npad)
-        tp[:, :n, :n] = g
-        model._tp_cache = c = (g, g._version, tp)
-    return c[2]
+    """the polynomials zero-padded to 16-node tiles"""
+    return rows_hip.padded_graph(model, model.cheb, "_tp_cache", False)
 
 
 def attention(blk, x4):
@@ -151,7 +119,7 @@ def head(model, h):
 def supported(model, x):
     """the HIP path serves: CUDA fp32 input, channel widths that are multiples of 16 up to 128, K <= 3, time_strides == 1, and a node count whose
     masked tiles and slab fit the LDS of a CU (N <= 320)"""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+    if not is_hip_input(x):
         return False
     blk0 = model.BlockList[0]
     ks, n = model.cheb.shape[0], model.cheb.shape[1]
@@ -164,7 +132,7 @@ def supported(model, x):
     widths = [x.shape[-1]]
     for blk in model.BlockList:
         widths += [blk.time_conv.in_channels, blk.time_conv.out_channels]
-    return all(w % 16 == 0 and 16 <= w <= 128 for w in widths)
+    return widths_ok(widths)
 
 
 def forward(model, x, keep=True):
@@ -179,8 +147,8 @@ def forward(model, x, keep=True):
         S = attention(blk, h)
         g = _MixFn.apply(rows, S, pack_theta(blk), tp, T, N, keep)
         rc = blk.residual_conv
-        R = _TapFn.apply(rows, rc.weight.view(rc.out_channels, rc.in_channels).contiguous(), rc.bias.contiguous(), None, (0,), ACT_NONE, T, N, keep)
-        y = _TapFn.apply(g, pack_time_conv(blk), blk.time_conv.bias.contiguous(), R, (-1, 0, 1), ACT_RELU, T, N, keep)
+        R = TapFn.apply(rows, rc.weight.view(rc.out_channels, rc.in_channels).contiguous(), rc.bias.contiguous(), None, (0,), ACT_NONE, 0, T, N, keep)
+        y = TapFn.apply(g, pack_time_conv(blk), blk.time_conv.bias.contiguous(), R, (-1, 0, 1), ACT_RELU, R.shape[1], T, N, keep)
         y = _RowLNFn.apply(y, blk.ln.weight.contiguous(), blk.ln.bias.contiguous(), blk.ln.eps, keep)
         h = y.view(B, T, N, y.shape[-1])
     return head(model, h)

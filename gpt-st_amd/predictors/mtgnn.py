@@ -27,6 +27,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _backend
+
 KERNEL_SET = (2, 3, 6, 7)                                                  # the inception's tap counts; the widest sets the output length
 
 
@@ -131,9 +133,7 @@ class MTGNN(nn.Module):
 
     def __init__(self, args_predictor, device, dim_in, dim_out, backend="torch"):
         super().__init__()
-        if backend not in ("torch", "hip"):
-            raise ValueError("MTGNN backend must be 'torch' or 'hip', got %r" % (backend,))
-        self.backend, self.backend_used = backend, None
+        self.backend, self.backend_used = _backend.check("MTGNN", backend), None
         a = args_predictor
         self.num_nodes, self.feature_dim, self.output_dim = a.num_nodes, dim_in, dim_out
         self.input_window, self.output_window = a.input_window, a.output_window
@@ -188,15 +188,9 @@ class MTGNN(nn.Module):
         return self.gc(self.idx) if self.buildA_true else self.predefined_A
 
     def forward(self, source):                                             # (B, input_window, N, dim_in)
-        if self.backend == "hip":
-            from . import mtgnn_hip
-            if mtgnn_hip.supported(self, source):
-                self.backend_used = "hip"
-                if self.training and torch.is_grad_enabled():
-                    return mtgnn_hip.forward(self, source, keep=True)
-                with torch.no_grad():                                      # eval mode: nothing is kept for a backward
-                    return mtgnn_hip.forward(self, source, keep=False)
-        self.backend_used = "torch"
+        y = _backend.hip_forward(self, "mtgnn_hip", source)
+        if y is not None:
+            return y
         x = source.transpose(1, 3)                                         # (B, dim_in, N, T)
         assert x.shape[3] == self.input_window, "input sequence length not equal to preset sequence length"
         if self.input_window < self.receptive_field:

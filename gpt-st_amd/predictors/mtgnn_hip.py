@@ -30,9 +30,8 @@ import torch.nn.functional as F
 
 from .. import _C, ops
 from .mtgnn import KERNEL_SET, MixProp
-from .stgcn_hip import _LNFn
+from .rows_hip import LNFn, is_hip_input, mirror as _mirror, nodemix_fits, pad16, widths_ok
 
-LDS_MAX = 160 * 1024
 MAX_TAPS = 32
 
 
@@ -78,12 +77,6 @@ def norm_weight(ln, numel, like):
     if not ln.elementwise_affine:
         return like.new_ones(numel), like.new_zeros(numel)
     return ln.weight.permute(2, 1, 0).reshape(-1), ln.bias.permute(2, 1, 0).reshape(-1)
-
-
-def _mirror(W, ntap):
-    """W (cw, ntap * ci) -> (ci, ntap * cw) with block j = W_j^T: the weight of the data backward"""
-    cw = W.shape[0]
-    return W.view(cw, ntap, -1).permute(2, 1, 0).reshape(-1, ntap * cw).contiguous()
 
 
 class _ConvFn(torch.autograd.Function):
@@ -160,14 +153,14 @@ def supported(model, x):
     """the HIP path serves: CUDA fp32 4-D input of the module's own (T, N, dim_in); dim_in and every channel width a multiple of 16 up to 128
     (conv_channels divisible by 4 follows); gcn_true with gcn_depth 2; a time axis of at most 32 steps (the tap table); N whose node-mix
     slab fits the LDS"""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+    if not is_hip_input(x):
         return False
     if tuple(x.shape[1:]) != (model.input_window, model.num_nodes, model.feature_dim) or not model.gcn_true or model.gcn_depth != 2:
         return False
     widths = (model.feature_dim, model.conv_channels, model.residual_channels, model.skip_channels)
-    if any(w % 16 or not 16 <= w <= 128 for w in widths) or model.total_window > MAX_TAPS or model.frames[-1] < 1:
+    if not widths_ok(widths) or model.total_window > MAX_TAPS or model.frames[-1] < 1:
         return False
-    return 16 * ((model.num_nodes + 15) // 16) * 36 * 4 <= LDS_MAX
+    return nodemix_fits(model.num_nodes)
 
 
 def forward(model, x, keep=True):
@@ -182,7 +175,7 @@ def forward(model, x, keep=True):
     xr = xp.view(B * Tt * N, Cin)
     adp = m.adjacency()
     L4 = mix_graphs(adp, m.propalpha)
-    pad = 16 * ((N + 15) // 16) - N
+    pad = pad16(N) - N
     L5p = F.pad(torch.cat([torch.eye(N, dtype=L4.dtype, device=L4.device)[None], L4.detach()]), (0, pad, 0, pad)).contiguous()
     L5pT = L5p.transpose(1, 2).contiguous()
 
@@ -202,7 +195,7 @@ def forward(model, x, keep=True):
         skip = conv(m.skip_convs[i], g, Tdst, prev=skip)
         ln = m.norm[i]
         gamma, beta = norm_weight(ln, Tdst * N * R, h)
-        h = _LNFn.apply(h, gamma.contiguous(), beta.contiguous(), B, ln.eps, keep)
+        h = LNFn.apply(h, gamma.contiguous(), beta.contiguous(), B, ln.eps, keep)
     To = m.frames[-1] - len(time_weight(m.skipE)[2]) + 1
     e = conv(m.skipE, h, m.frames[-1])                                                                  # (B To N, S)
     z = F.relu(e.view(B, To, N, S) + skip.view(B, 1, N, S)).view(B * To * N, S)                          # T = output_dim + T = 1: broadcasts

@@ -18,6 +18,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import _backend
+
 
 class _Align(nn.Module):
     """Residual branch between channel counts: 1x1 conv down (stgcn.py:15-16), zero-pad up (:21-22), identity otherwise."""
@@ -120,9 +122,7 @@ class STGCN(nn.Module):
 
     def __init__(self, args_predictor, device, dim_in, dim_out, backend="torch"):
         super().__init__()
-        if backend not in ("torch", "hip"):
-            raise ValueError("STGCN backend must be 'torch' or 'hip', got %r" % (backend,))
-        self.backend, self.backend_used = backend, None
+        self.backend, self.backend_used = _backend.check("STGCN", backend), None
         a = args_predictor
         lk = a.G.to(device)
         blocks0 = [dim_in, a.blocks1[1], a.blocks1[0]]                    # stgcn.py:134
@@ -131,14 +131,8 @@ class STGCN(nn.Module):
         self.output = _Head(a.blocks1[2], a.outputl_ks, a.num_nodes, dim_out)
 
     def forward(self, x):                                                  # x (B, T, N, dim_in)
-        if self.backend == "hip":
-            from . import stgcn_hip
-            if stgcn_hip.supported(self, x):
-                self.backend_used = "hip"
-                if self.training and torch.is_grad_enabled():
-                    return stgcn_hip.forward(self, x, keep=True)
-                with torch.no_grad():                                      # eval mode: nothing is kept for a backward
-                    return stgcn_hip.forward(self, x, keep=False)
-        self.backend_used = "torch"
+        y = _backend.hip_forward(self, "stgcn_hip", x)
+        if y is not None:
+            return y
         y = self.output(self.st_conv2(self.st_conv1(x.permute(0, 3, 1, 2))))
         return y.permute(0, 2, 3, 1)                                      # (B, T, N, dim_out)

@@ -20,40 +20,9 @@ import torch
 
 from .. import _C, ops
 from ..ops import ACT_GLU, ACT_NONE, ACT_RELU, ACT_SIGMOID
+from .rows_hip import LNFn, TapFn, is_hip_input, padded_graph, widths_ok
 
 _ACT = {"GLU": ACT_GLU, "relu": ACT_RELU, "sigmoid": ACT_SIGMOID}
-
-
-class _TapFn(torch.autograd.Function):
-    """y = act(sum_j x[t + taps[j]] W_j + b + x[:, :res_w]);  W (co | 2 co, len(taps) * ci)"""
-
-    @staticmethod
-    def forward(ctx, x, W, b, taps, act, res_w, T, N, keep):
-        keep = keep and any(ctx.needs_input_grad)
-        res = x if res_w > 0 else None
-        S = A = None
-        if act == ACT_GLU and keep:
-            y, S, A = ops.stgcn_tapgemm(x, W, b, taps, act, T, N, res=res, res_w=res_w, keep=True)
-        else:
-            y = ops.stgcn_tapgemm(x, W, b, taps, act, T, N, res=res, res_w=res_w)
-        if keep:
-            ctx.cfg = (taps, act, res_w, T, N)
-            ctx.save_for_backward(x, W, S, A, None if act == ACT_GLU else y)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, W, S, A, y = ctx.saved_tensors
-        taps, act, res_w, T, N = ctx.cfg
-        dPre = ops.stgcn_gate_bwd(dy.contiguous(), act, out=y, S=S, A=A)
-        dW = db = dx = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dW, db = ops.stgcn_wgrad(dPre, x, taps, T, N)
-        if ctx.needs_input_grad[0]:
-            cw, ci = W.shape[0], x.shape[1]
-            Wb = W.view(cw, len(taps), ci).permute(2, 1, 0).reshape(ci, len(taps) * cw).contiguous()      # block j = W_j^T
-            dx = ops.stgcn_tapgemm(dPre, Wb, None, tuple(-t for t in taps), ACT_NONE, T, N, res=dPre if res_w > 0 else None, res_w=res_w)
-        return dx, dW, db, None, None, None, None, None, None
 
 
 class _SConvFn(torch.autograd.Function):
@@ -85,27 +54,6 @@ class _SConvFn(torch.autograd.Function):
         return dx, dTheta, db, None, None, None, None, None
 
 
-class _LNFn(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, x, gamma, beta, units, eps, keep):
-        keep = keep and any(ctx.needs_input_grad)
-        y, mean, rstd = ops.stgcn_ln_fwd(x, gamma, beta, units, eps, keep=keep)
-        if keep:
-            ctx.units = units
-            ctx.save_for_backward(x, gamma, mean, rstd)
-        return y
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, gamma, mean, rstd = ctx.saved_tensors
-        dy = dy.contiguous()
-        dx = ops.stgcn_ln_bwd(dy, x, gamma, mean, rstd, ctx.units) if ctx.needs_input_grad[0] else None
-        dg = db = None
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dg, db = (g.view_as(gamma) for g in ops.stgcn_ln_bwd_param(dy, x, mean, rstd, ctx.units))
-        return dx, dg, db, None, None, None
-
-
 def _tconv(m, x, T, N, keep=True):
     """predictors.stgcn._TConv on rows: the conv's taps (and the 1x1 align as one more centre tap) packed tap-major into one GEMM weight"""
     w = m.conv.weight                                                   # (cw, ci, kt, 1)
@@ -119,36 +67,24 @@ def _tconv(m, x, T, N, keep=True):
         if cw > m.c_out:
             wa, ba = torch.cat([wa, wa.new_zeros(cw - m.c_out, ci)]), torch.cat([ba, ba.new_zeros(cw - m.c_out)])
         W, b, taps, res_w = torch.cat([W, wa], 1), b + ba, taps + (0,), 0
-    return _TapFn.apply(x, W.contiguous(), b.contiguous(), taps, _ACT[m.act], res_w, T, N, keep)
-
-
-def _padded_graph(m):
-    """(L, L^T) of a graph convolution zero-padded to 16-node tiles: built when the module's `Lk` is another tensor than last time, or was written to"""
-    lk, c = m.Lk, getattr(m, "_lp_cache", None)
-    if c is None or c[0] is not lk or c[1] != lk._version:
-        ks, n = lk.shape[0], lk.shape[1]
-        npad = 16 * ((n + 15) // 16)
-        lp = lk.new_zeros(ks, npad, npad)
-        lp[:, :n, :n] = lk
-        m._lp_cache = c = (lk, lk._version, lp, lp.transpose(1, 2).contiguous())
-    return c[2], c[3]
+    return TapFn.apply(x, W.contiguous(), b.contiguous(), None, taps, _ACT[m.act], res_w, T, N, keep)
 
 
 def _sconv(m, x, T, N, keep=True):
     c_in, c_out, ks = m.theta.shape
     Theta = m.theta.permute(1, 2, 0).reshape(c_out, ks * c_in).contiguous()
-    lp, lpt = _padded_graph(m)
+    lp, lpt = padded_graph(m, m.Lk, "_lp_cache", True)
     return _SConvFn.apply(x, Theta, m.b.reshape(c_out).contiguous(), lp, lpt, T, N, keep)
 
 
 def _ln(ln, x, units, keep=True):
-    return _LNFn.apply(x, ln.weight.contiguous(), ln.bias.contiguous(), units, ln.eps, keep)
+    return LNFn.apply(x, ln.weight.contiguous(), ln.bias.contiguous(), units, ln.eps, keep)
 
 
 def supported(model, x):
     """the HIP path serves: CUDA fp32 input, channel widths that are multiples of 16 up to 128, Kt and outputl_ks of 1 or 3, Ks <= 3, and
     inactive dropout (drop_prob == 0 or eval mode)"""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+    if not is_hip_input(x):
         return False
     blocks = (model.st_conv1, model.st_conv2)
     widths = [x.shape[-1]]
@@ -162,7 +98,7 @@ def supported(model, x):
             return False
     if model.output.tconv1.conv.kernel_size[0] not in (1, 3) or x.shape[-1] != model.st_conv1.tconv1.conv.in_channels:
         return False
-    return all(w % 16 == 0 and 16 <= w <= 128 for w in widths)
+    return widths_ok(widths)
 
 
 def forward(model, x, keep=True):

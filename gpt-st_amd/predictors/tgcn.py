@@ -16,6 +16,8 @@ torch ops.  ``backend_used`` records which of the two the last forward took.
 import torch
 import torch.nn as nn
 
+from . import _backend
+
 
 class _Cell(nn.Module):
     """the parameter holder ``tgcn_model``: W0 (C + H, 2 H), b0 (2 H), W1 (C + H, H), b1 (H), registered in the reference's order (TGCN.py:41-56)"""
@@ -52,9 +54,7 @@ class TGCN(nn.Module):
 
     def __init__(self, args_predictor, device, dim_in, backend="torch"):
         super().__init__()
-        if backend not in ("torch", "hip"):
-            raise ValueError("TGCN backend must be 'torch' or 'hip', got %r" % (backend,))
-        self.backend, self.backend_used = backend, None
+        self.backend, self.backend_used = _backend.check("TGCN", backend), None
         a = args_predictor
         self.num_nodes, self.input_dim, self.output_dim, self.gru_units = a.num_nodes, dim_in, a.output_dim, a.rnn_units
         self.input_window, self.output_window = a.input_window, a.output_window
@@ -67,15 +67,9 @@ class TGCN(nn.Module):
         return y.permute(0, 2, 1, 3)
 
     def forward(self, x):                                                  # x (B, T, N, dim_in)
-        if self.backend == "hip":
-            from . import tgcn_hip
-            if tgcn_hip.supported(self, x):
-                self.backend_used = "hip"
-                if self.training and torch.is_grad_enabled():
-                    return tgcn_hip.forward(self, x, keep=True)
-                with torch.no_grad():                                      # eval mode: nothing is kept for a backward
-                    return tgcn_hip.forward(self, x, keep=False)
-        self.backend_used = "torch"
+        y = _backend.hip_forward(self, "tgcn_hip", x)
+        if y is not None:
+            return y
         h = x.new_zeros(x.shape[0], self.num_nodes, self.gru_units)
         for t in range(x.shape[1]):
             h = self.tgcn_model(x[:, t], h)

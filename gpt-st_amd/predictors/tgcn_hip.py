@@ -19,13 +19,7 @@ import torch.nn.functional as F
 
 from .. import _C, ops
 from ..ops import ACT_NONE
-
-LDS_MAX = 160 * 1024
-
-
-def padded(H):
-    return 16 * ((H + 15) // 16)
-
+from .rows_hip import LDS_MAX, is_hip_input, nodemix_fits, pad16 as padded, padded_graph, widths_ok
 
 def pack(W0, b0, W1, b1, C, H):
     """The parameters (reference layout: W (C + H, gates * H), gate-major columns) in the kernels' GEMM form, outputs as rows:
@@ -36,18 +30,6 @@ def pack(W0, b0, W1, b1, C, H):
         P = F.pad(W.t().reshape(gates, H, C + H), (0, Hp - H, 0, Hp - H))           # (gates, Hp, C + Hp)
         return P.reshape(gates * Hp, C + Hp), F.pad(b.view(gates, H), (0, Hp - H)).reshape(gates * Hp)
     return one(W0, b0, 2) + one(W1, b1, 1)
-
-
-def _padded_graph(cell):
-    """(L, L^T) zero-padded to 16-node tiles, (1, Np, Np) each: rebuilt when the cell's `L` is another tensor than last time, or was written to"""
-    L, c = cell.L, getattr(cell, "_lp_cache", None)
-    if c is None or c[0] is not L or c[1] != L._version:
-        n = L.shape[0]
-        npad = 16 * ((n + 15) // 16)
-        lp = L.new_zeros(1, npad, npad)
-        lp[0, :n, :n] = L
-        cell._lp_cache = c = (L, L._version, lp, lp.transpose(1, 2).contiguous())
-    return c[2], c[3]
 
 
 class _RecurrenceFn(torch.autograd.Function):
@@ -112,16 +94,15 @@ class _RecurrenceFn(torch.autograd.Function):
 def supported(model, x):
     """the HIP path serves: CUDA fp32 4-D input of the module's own (T, N, C), dim_in a multiple of 16 up to 128, rnn_units <= 128 (any value: it is
     padded), and any N whose operand slabs fit the 160 KB of LDS"""
-    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 4):
+    if not is_hip_input(x):
         return False
     B, T, N, C = x.shape
     H = model.gru_units
     if (T, N, C) != (model.input_window, model.num_nodes, model.input_dim) or model.tgcn_model.L.shape[0] != N:
         return False
-    if C % 16 or not 16 <= C <= 128 or not 1 <= H <= 128 or not 1 <= B <= 65535:
+    if not widths_ok([C]) or not 1 <= H <= 128 or not 1 <= B <= 65535:
         return False
-    npad = 16 * ((N + 15) // 16)
-    return npad * 36 * 4 <= LDS_MAX and 0 < _C.lib().value("gptst_tgcn_lds_bytes", N, padded(H), B) <= LDS_MAX
+    return nodemix_fits(N) and 0 < _C.lib().value("gptst_tgcn_lds_bytes", N, padded(H), B) <= LDS_MAX
 
 
 def forward(model, x, keep=True):
@@ -130,7 +111,7 @@ def forward(model, x, keep=True):
     _C.lib()
     B, T, N, C = x.shape
     cell, H = model.tgcn_model, model.gru_units
-    lp, lpt = _padded_graph(cell)
+    lp, lpt = padded_graph(cell, cell.L, "_lp_cache", True)
     hT = _RecurrenceFn.apply(x.contiguous().view(B * T * N, C), *pack(cell.weights_0, cell.bias_0, cell.weights_1, cell.bias_1, C, H), lp, lpt,
                              (B, T, N), keep)
     return model.head(hT.view(B, N, -1)[:, :, :H])

@@ -19,25 +19,11 @@ from gptst_amd.config import make_args, predictor_args
 from gptst_amd.predictors import MTGNN, mtgnn_hip as H
 from golden_util import load
 from mtgnn_util import clear_topk_cuts, same_support
+from downstream_util import _check, _err
 from oracle import gptst_oracle as O
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-TOL = 1e-4
-
-
-def _err(got, want):
-    want = want.detach().double().cpu()
-    return float((got.detach().double().cpu() - want).abs().max() / want.abs().max().clamp_min(1e-30))
-
-
-def _check(parity, errs):
-    for k, v in errs.items():
-        parity(k, v)
-    worst = max(errs, key=errs.get)
-    print("worst of %d: %s %.2e" % (len(errs), worst, errs[worst]))
-    over = {k: v for k, v in errs.items() if not v < TOL}
-    assert not over, over
 
 
 def _g(t):

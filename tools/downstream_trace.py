@@ -1,0 +1,96 @@
+"""Which C-ABI calls does a downstream predictor's HIP forward + backward make, in which order — and what does it compute, bit for bit?
+
+    python tools/downstream_trace.py [config ...] > trace.txt
+
+For every configuration below: the predictor with backend="hip" in train mode from a fixed seed, one forward + backward; the ordered
+(name, tag) of every call through ops._call (ops.TIMER), then one SHA-256 each of the output, the input gradient and every parameter
+gradient in named_parameters order.  Only the public predictor classes are used, so two trees agree on what the predictors do exactly when
+their outputs are identical line for line (tools/launch_trace.py does the same for the pretraining step).  A second or so of GPU time each.
+"""
+import hashlib
+import os
+import sys
+from types import SimpleNamespace
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+from gptst_amd import graph, ops  # noqa: E402
+from gptst_amd.config import predictor_args  # noqa: E402
+from gptst_amd.enhance import xavier_downstream_  # noqa: E402
+from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, TGCN  # noqa: E402
+
+DEV = "cuda:0"
+T, C = 12, 64
+
+
+def stgcn(N):
+    ap = SimpleNamespace(Ks=3, Kt=3, num_nodes=N, G=graph.stgcn_graph(graph.synthetic_adjacency(N, 2)), blocks1=[64, 32, 128], drop_prob=0, outputl_ks=3)
+    return STGCN(ap, DEV, C, 1, backend="hip").to(DEV)
+
+
+def tgcn(N):                                      # rnn_units 100: channels padded to 112
+    ap = SimpleNamespace(num_nodes=N, input_window=T, output_window=T, rnn_units=100, output_dim=1, G=graph.tgcn_graph(graph.synthetic_adjacency(N, 2)))
+    return TGCN(ap, DEV, C, backend="hip").to(DEV)
+
+
+def mtgnn(N):                                     # dropout 0.3: the masked paths, the masks drawn on the device from the seed
+    conf = vars(predictor_args("PEMS08", "MTGNN"))
+    ap = SimpleNamespace(**{**conf, "num_nodes": N, "subgraph_size": min(conf["subgraph_size"], N), "dropout": 0.3}, adj_mx=None)
+    return MTGNN(ap, DEV, C, 1, backend="hip").to(DEV)
+
+
+def astgcn(N):
+    ap = predictor_args("PEMS08", "ASTGCN")
+    ap.num_nodes, ap.G = N, graph.astgcn_graph(graph.synthetic_adjacency(N, 2), ap.K)
+    m = ASTGCN(ap, DEV, C, 1, backend="hip")
+    xavier_downstream_(m)                         # the conf's xavier pass: the model has no other initial state
+    with torch.no_grad():                         # and the score vectors centred, so that the sigmoids pass gradient
+        for blk in m.BlockList:
+            for p in (blk.TAt.U1, blk.TAt.U3, blk.SAt.W1, blk.SAt.W3):
+                p.copy_(0.25 * (p - 0.5))
+    return m
+
+
+def sha(t):
+    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+
+
+def run(make, B, N):
+    torch.manual_seed(0)
+    m = make(N).train()
+    x = torch.randn(B, T, N, C, device=DEV, requires_grad=True)
+    y = m(x)                                      # (untraced: the first call loads the library)
+    w = torch.randn_like(y)
+    for p in m.parameters():
+        p.grad = None
+    x.grad = None
+    torch.manual_seed(1)
+    ops.TIMER = []
+    try:
+        y = m(x)
+        (y * w).sum().backward()
+        torch.cuda.synchronize()
+        calls = [rec[:2] for rec in ops.TIMER]
+    finally:
+        ops.TIMER = None
+    assert m.backend_used == "hip"
+    print("-- forward + backward: %d calls" % len(calls))
+    for name, tag in calls:
+        print("   %s %s" % (name, tag))
+    print("-- sha256 y %s" % sha(y))
+    print("-- sha256 dx %s" % sha(x.grad))
+    for k, p in m.named_parameters():
+        print("-- sha256 d %s %s" % (k, "none" if p.grad is None else sha(p.grad)))
+
+
+CONFIGS = {}
+for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn)):
+    CONFIGS[_name + "_b2_n37"] = lambda make=_make: run(make, 2, 37)            # a padded node tile, several row tiles
+    CONFIGS[_name + "_b1_n170"] = lambda make=_make: run(make, 1, 170)
+
+if __name__ == "__main__":
+    for name in sys.argv[1:] or list(CONFIGS):
+        print("==== %s" % name, flush=True)
+        CONFIGS[name]()
+        sys.stdout.flush()

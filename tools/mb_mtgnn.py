@@ -7,29 +7,20 @@ usage (GPU box, repo root):
                                                   7 rounds after warm-up; each launch of the HIP pass with the flops / bytes of its shapes; the
                                                   EvalTrainer loop body, frozen and fine-tuned; [--out FILE] (default profiles/mtgnn_hip_ab.txt)
     python tools/mb_mtgnn.py --trace torch|hip    30 forward + backward passes of one backend and nothing else (for tools/prof.sh)"""
-import os
+import contextlib
 import statistics
 import sys
-import time
 from types import SimpleNamespace
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from gptst_amd import ops, synth                 # noqa: E402
-from gptst_amd.config import make_args, predictor_args   # noqa: E402
-from gptst_amd.predictors import MTGNN           # noqa: E402
+import mb_downstream as mb
+from mb_downstream import PEAK_TBS, PEAK_TFLOPS, dev, fb, say
+from gptst_amd import ops
+from gptst_amd.config import predictor_args
+from gptst_amd.predictors import MTGNN
 
-dev = torch.device("cuda:0")
-B, T, N, C = 64, 12, 170, 64
-PEAK_TFLOPS, PEAK_TBS = 157.3, 8.0               # fp32 MFMA, HBM3E
-LINES = []
-
-
-def say(s=""):
-    print(s, flush=True)
-    LINES.append(s)
+B, T, N, C = SHAPE = 64, 12, 170, 64
 
 
 def ap():
@@ -41,117 +32,19 @@ def predictor(backend):
     return MTGNN(ap(), dev, C, 1, backend=backend).to(dev).train()
 
 
-def fb(m, x, w):
-    for p in m.parameters():
-        p.grad = None
-    (m(x) * w).sum().backward()
+def step_predictor(backend, args):
+    torch.manual_seed(0)
+    return MTGNN(ap(), dev, args.hidden_dim, args.output_dim, backend=backend)
 
 
-def events(fn, reps):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(reps):
-        fn()
-    e1.record()
-    torch.cuda.synchronize()
-    return e0.elapsed_time(e1) / reps
-
-
-def med(v):
-    return "%.3f (%.3f - %.3f)" % (statistics.median(v), min(v), max(v))
-
-
-def verdict(res):
-    """faster only where the one's slowest round lies below the other's fastest"""
-    h, t = res["hip"], res["torch"]
-    return "hip faster" if max(h) < min(t) else ("hip slower" if min(h) > max(t) else "no difference outside the spread")
-
-
-def trace(backend):
-    m = predictor(backend)
-    x, w = torch.randn(B, T, N, C, device=dev, requires_grad=True), torch.randn(B, T, N, 1, device=dev)
-    for _ in range(30):
-        fb(m, x, w)
-    torch.cuda.synchronize()
-
-
-def ab_predictor():
-    ms = {k: predictor(k) for k in ("torch", "hip")}
-    ms["hip"].load_state_dict(ms["torch"].state_dict(), strict=True)
-    x, w = torch.randn(B, T, N, C, device=dev, requires_grad=True), torch.randn(B, T, N, 1, device=dev)
-    for m in ms.values():                          # the outputs are compared without dropout: the backends draw their masks from different streams
+@contextlib.contextmanager
+def no_dropout(ms):
+    """the outputs are compared without dropout: the backends draw their masks from different streams"""
+    for m in ms.values():
         m._keep = lambda tag, like: None
-    y = {k: m(x).detach() for k, m in ms.items()}
-    say("outputs of the two backends at this shape (no dropout): max |diff| %.2e of max |y| %.2e"
-        % (float((y["hip"] - y["torch"]).abs().max()), float(y["torch"].abs().max())))
-    assert ms["hip"].backend_used == "hip"
+    yield
     for m in ms.values():
         del m._keep
-        for _ in range(5):
-            fb(m, x, w)
-
-    def fwd(m):
-        with torch.no_grad():
-            m(x)
-    tf, tb = {k: [] for k in ms}, {k: [] for k in ms}
-    for _ in range(7):
-        for k, m in ms.items():
-            tb[k].append(events(lambda: fb(m, x, w), 20))
-            tf[k].append(events(lambda: fwd(m), 20))
-    say("predictor, training mode, dropout 0.3, device events, 7 alternating rounds of 20 passes, ms median (min - max):")
-    for k in ms:
-        say("  %-5s forward + backward %s   forward only (no_grad) %s" % (k, med(tb[k]), med(tf[k])))
-    say("  forward + backward: %s;  forward only: %s" % (verdict(tb), verdict(tf)))
-    return ms["hip"], x, w
-
-
-def ab_step():
-    from gptst_amd.enhance import EnhanceFrontEnd
-    from gptst_amd.eval_trainer import EvalTrainer
-    from oracle import gptst_oracle as O
-    import logging
-    say("EvalTrainer loop body (zero_grad, forward, masked MAE, backward, clip, Adam), host clock around 20 steps ending in a synchronise,")
-    say("5 alternating rounds after 5 warm-up steps, ms per step median (min - max):")
-    for finetune in (False, True):
-        runs = {}
-        for backend in ("torch", "hip"):
-            args = make_args("PEMS08", mode="eval", num_nodes=N, scaler_zeros=synth.scaler_zeros(), log_dir="/tmp", debug=True, model="MTGNN_test",
-                             mtgnn_backend=backend, batch_size=B)
-            torch.manual_seed(0)
-            model = EnhanceFrontEnd(args, predictor=MTGNN(ap(), dev, args.hidden_dim, args.output_dim, backend=backend),
-                                    finetune_encoder=finetune).to(dev)
-            model.load_pretrained_model(O.init_state_dict(args, 11))
-            tr = EvalTrainer(model, args, None, None, None, synth.SCALER_MEAN, synth.SCALER_STD)
-            tr.logger.setLevel(logging.WARNING)
-            runs[backend] = (model, tr)
-        src = synth.make_batch(B, T, N, 1, interval=5, seed=21).to(dev)
-        tgt = synth.make_batch(B, T, N, 1, interval=5, seed=22, start_slot=12).to(dev)
-
-        def step(model, tr):
-            tr.opt.zero_grad()
-            loss = tr._loss(model(src, tgt)[0], tgt)
-            loss.backward()
-            torch.nn.utils.clip_grad_norm_([p for p in model.parameters() if p.requires_grad], tr.args.max_grad_norm)
-            tr.opt.step()
-        res = {k: [] for k in runs}
-        for k, (model, tr) in runs.items():
-            model.train()
-            for _ in range(5):
-                step(model, tr)
-        torch.cuda.synchronize()
-        for _ in range(5):
-            for k, (model, tr) in runs.items():
-                t0 = time.perf_counter()
-                for _ in range(20):
-                    step(model, tr)
-                torch.cuda.synchronize()
-                res[k].append((time.perf_counter() - t0) * 1e3 / 20)
-        for k in runs:
-            assert runs[k][0].predictor.backend_used == k
-            say("  %-10s %-5s %s" % ("fine-tuned" if finetune else "frozen", k, med(res[k])))
-        say("  %-10s %s" % ("", verdict(res)))
-        del runs
-        torch.cuda.empty_cache()
 
 
 def flops_of(name, a):
@@ -205,25 +98,19 @@ def per_kernel(m, x, w):
         v = acc[key]
         us = statistics.median(t for t, _ in v)
         n = len(v) // 10
-        fl, by = flops_of(key[0], v[0][1]), key[2]
-        tf, tb = fl / PEAK_TFLOPS / 1e6, by / PEAK_TBS / 1e6
-        bound = max(tf, tb)
         total += us * n
-        say("  %-22s %-24s %2d %9.1f %9.2f %9.1f %9.1f %6.1f%%  %s" % (key[0][6:], key[1], n, us, fl / 1e9, by / 1e6, bound, 100 * bound / us,
-                                                                    "MFMA" if tf >= tb else "HBM"))
+        mb.kernel_row("  %-22s %-24s %2d %9.1f %9.2f %9.1f %9.1f %6.1f%%  %s", key[0], key[1], n, us, flops_of(key[0], v[0][1]), key[2])
     say("  sum of the launches above: %.1f us per pass" % total)
 
 
 if __name__ == "__main__":
     if "--trace" in sys.argv:
-        trace(sys.argv[sys.argv.index("--trace") + 1])
+        mb.trace(predictor, SHAPE, sys.argv[sys.argv.index("--trace") + 1])
         sys.exit(0)
     say("MTGNN predictor at (B, T, N, C) = (%d, %d, %d, %d -> %d x 1), rows of layer 0 = %d, %s" % (B, T, N, C, T, B * 13 * N, torch.cuda.get_device_name(0)))
-    mh, x, w = ab_predictor()
+    mh, x, w, _ = mb.ab_predictor(predictor, SHAPE, compared=no_dropout, compared_note=" (no dropout)", mode_note="training mode, dropout 0.3, ")
     per_kernel(mh, x, w)
     del mh, x, w
     torch.cuda.empty_cache()
-    ab_step()
-    out = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "mtgnn_hip_ab.txt")
-    os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
-    open(out, "w").write("\n".join(LINES) + "\n")
+    mb.ab_step(step_predictor, SHAPE, "MTGNN", "mtgnn_backend")
+    mb.write_out("mtgnn_hip_ab.txt")
