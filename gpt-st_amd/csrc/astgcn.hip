@@ -255,13 +255,21 @@ __global__ __launch_bounds__(256) void ag_rowln_bwd_param_kernel(const float* __
 
 // ---- entry points ----
 static size_t ag_mix_smem(int Np, int ks) { return ((size_t)ks * Np * AG_MP + (size_t)Np * AG_SP) * sizeof(float); }
+// the (Np, ks) the mix serves: the prefetch array holds a slab of Np <= 16 AG_PRE rows, the masked tiles and the slab fit the 160 KB of a CU
+static bool ag_mix_fits(int Np, int ks) { return Np <= 16 * AG_PRE && ks <= AG_MAXK && ag_mix_smem(Np, ks) <= 160 * 1024; }
+
+// (include/gptst_hip_testing.h) bytes of dynamic LDS of the launch gptst_astgcn_attmix makes for this shape
+extern "C" int gptst_astgcn_attmix_lds(int Np, int ks) {
+    if (Np <= 0 || ks <= 0) return GPTST_EARG;
+    if (Np % 16 || !ag_mix_fits(Np, ks)) return GPTST_ESHAPE;
+    return (int)ag_mix_smem(Np, ks);
+}
 
 extern "C" int gptst_astgcn_attmix(const float* Tp, int Np, int ks, const float* S, const float* In, float* Out, const float* R, int c, int reduce,
                                    int B, int T, int N, void* stream) {
     if (!Tp || !S || !In || !Out || B <= 0 || T <= 0 || N <= 0 || ks <= 0 || (R != nullptr && !reduce)) return GPTST_EARG;
-    if (Np != 16 * ((N + 15) / 16) || Np > 16 * AG_PRE || ks > AG_MAXK || c < 16 || c % 16 || B > 65535) return GPTST_ESHAPE;
+    if (Np != 16 * ((N + 15) / 16) || !ag_mix_fits(Np, ks) || c < 16 || c % 16 || B > 65535) return GPTST_ESHAPE;
     const size_t smem = ag_mix_smem(Np, ks);
-    if (smem > 160 * 1024) return GPTST_ESHAPE;
     typedef void (*kern_t)(AgMix);
     static const kern_t kerns[2][AG_MAXK] = {{ag_attmix_kernel<1, false>, ag_attmix_kernel<2, false>, ag_attmix_kernel<3, false>},
                                              {ag_attmix_kernel<1, true>, ag_attmix_kernel<2, true>, ag_attmix_kernel<3, true>}};

@@ -30,6 +30,9 @@ int gptst_handoff_inject(int n);
  * gradients follow from the *_nsplit queries of gptst_hip.h: cps = ceil(ceil(rows / 64) / nsplit), ups = ceil(units / nsplit). */
 int gptst_stgcn_tapgemm_tpw(int rows, int co, int Ktot, int act);
 int gptst_mtgnn_tapgemm_tpw(long rows, int co, int gated);
+/* bytes of dynamic LDS of the launch gptst_astgcn_attmix makes for Np padded nodes and ks polynomials, answered by the function the launch sizes
+ * with; GPTST_EARG / GPTST_ESHAPE for the (Np, ks) the launch refuses (tests/test_gpu_astgcn_hip.py) */
+int gptst_astgcn_attmix_lds(int Np, int ks);
 #if defined(__GNUC__)
 #pragma GCC visibility pop
 #endif

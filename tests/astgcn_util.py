@@ -36,6 +36,28 @@ def move_score_vectors_(model):
                 p.copy_(0.25 * (p - 0.5))
 
 
+def scale_u1_(model, n):
+    """after move_score_vectors_: TAt.U1 <- min(1, 64 / n) min(1, 64 / f) U1 in every block, f the block's input width.  The temporal score sums
+    U1 over the n nodes and U2, U3 over the f features, so the temporal sigmoid's input grows with both: with the pass above alone the first one
+    saturates from 250 nodes on (0.44 of its inputs inside |z| < 4 at 250, 0.36 at 266 and 320), and the second block's at 112 features (0.39)"""
+    with torch.no_grad():
+        for blk in model.BlockList:
+            blk.TAt.U1.mul_(min(1.0, 64.0 / n) * min(1.0, 64.0 / blk.TAt.U3.shape[0]))
+
+
+def tap(x4, W, b, taps):
+    """the definition of ops.stgcn_tapgemm on (B, T, N, ci): sum_j x[t + taps[j]] W_j + b, zero outside [0, T); W (co, len(taps) ci) tap-major"""
+    T = x4.shape[1]
+    cols = []
+    for dt in taps:
+        s = torch.zeros_like(x4)
+        lo, hi = max(0, -dt), min(T, T - dt)
+        s[:, lo:hi] = x4[:, lo + dt:hi + dt]
+        cols.append(s)
+    y = torch.cat(cols, -1) @ W.t()
+    return y if b is None else y + b
+
+
 @contextlib.contextmanager
 def recorded_sigmoids(into):
     """every input torch.sigmoid sees inside the block is appended to `into` (the model calls it once per attention layer)"""

@@ -59,17 +59,7 @@ def _attmix(Tk, S, x4):
     return torch.einsum("kmn,bmn,btmc->btnkc", Tk, S, x4)
 
 
-def _tap(x4, W, b, taps):
-    """the definition of ops.stgcn_tapgemm on (B, T, N, ci): sum_j x[t + taps[j]] W_j + b, zero outside [0, T); W (co, len(taps) ci) tap-major"""
-    T = x4.shape[1]
-    cols = []
-    for dt in taps:
-        s = torch.zeros_like(x4)
-        lo, hi = max(0, -dt), min(T, T - dt)
-        s[:, lo:hi] = x4[:, lo + dt:hi + dt]
-        cols.append(s)
-    y = torch.cat(cols, -1) @ W.t()
-    return y if b is None else y + b
+_tap = au.tap
 
 
 def _restated(m, x):
