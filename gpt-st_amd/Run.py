@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -46,7 +46,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -114,15 +114,15 @@ def main_shard(args, dev):
 
 
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41 and model/MTGNN/args.py:6-39 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39 and model/STSGCN/args.py:6-51 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, TGCN
-    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN"):
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN and -model ASTGCN (SURVEY.md §8f rank 4)")
+    from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, STSGCN, TGCN
+    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN"):
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN and -model STSGCN (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -146,6 +146,9 @@ def main_eval(args, dev):
     elif str(args.model) == "ASTGCN":                                            # ASTGCN.py:272-286: the polynomials of the raw adjacency
         ap = SimpleNamespace(**vars(pargs), G=graph.astgcn_graph(A, pargs.K))
         predictor = ASTGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.astgcn_backend))
+    elif str(args.model) == "STSGCN":                                            # model/Model.py:58-60, STSGCN/args.py:41-50: the raw adjacency
+        ap = SimpleNamespace(**vars(pargs), A=np.asarray(A, dtype=np.float32))
+        predictor = STSGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stsgcn_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

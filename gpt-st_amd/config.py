@@ -80,6 +80,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-mtgnn_backend", default=FINETUNE_DEFAULTS["mtgnn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the ASTGCN predictor (predictors/astgcn_hip.py)
     ap.add_argument("-astgcn_backend", default=FINETUNE_DEFAULTS["astgcn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the STSGCN predictor (predictors/stsgcn_hip.py)
+    ap.add_argument("-stsgcn_backend", default=FINETUNE_DEFAULTS["stsgcn_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -92,7 +94,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
-                         astgcn_backend="torch")
+                         astgcn_backend="torch", stsgcn_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -135,14 +137,20 @@ _MTGNN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data
 _ASTGCN_KEYS = [("data", "num_nodes", int), ("data", "len_input", int), ("data", "num_for_predict", int), ("model", "nb_block", int),
                 ("model", "K", int), ("model", "nb_chev_filter", int), ("model", "nb_time_filter", int), ("model", "time_strides", int),
                 ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
-_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS}
+# reference model/STSGCN/args.py:12-35.  `filter_list` is a literal (a list of lists of widths); `rho` is parsed and, as in the reference, read by nothing.
+_STSGCN_KEYS = [("data", "num_nodes", int), ("data", "input_window", int), ("data", "output_window", int), ("model", "filter_list", _EVAL),
+                ("model", "rho", int), ("model", "feature_dim", int), ("model", "module_type", str), ("model", "activation", str),
+                ("model", "temporal_emb", _EVAL), ("model", "spatial_emb", _EVAL), ("model", "use_mask", _EVAL), ("model", "steps", int),
+                ("model", "first_layer_embedding_size", int),
+                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+_PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS, "STSGCN": _STSGCN_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN and ASTGCN are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN and STSGCN are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN and ASTGCN predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN and STSGCN predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)

@@ -1,0 +1,380 @@
+// The downstream STSGCN predictor (reference model/STSGCN/STSGCN.py; gpt-st_amd/predictors/stsgcn.py) on HIP, forward and backward.
+// Channels last, nothing is permuted.  A layer over T frames has W = T - 2 windows of three frames; three row layouts occur:
+//   frames     (b, t, n)       (B T N rows)      the layer's input, and the gradient that leaves it
+//   expanded   (b, w, k, n)    (B W 3 N rows)    block (w, k), k = 0..2, stands for frame w + k of window w
+//   middle     (b, w, n)       (B W N rows)      the last operation's output and the running max: already the next layer's frames
+//
+//   mix        the localized adjacency of a window without its (3N, 3N) matrix: with A^ = the adjacency with a unit diagonal,
+//                  mix(S)_k = A^ S_k + [k >= 1] S_{k-1} + [k <= 1] S_{k+1}
+//              in five forms.  Forward: frames -> expanded (A^ H_t is formed once per frame and serves the up to three blocks with
+//              w + k = t; no expanded copy of the input exists), expanded -> expanded, expanded -> middle (the last operation needs only
+//              k = 1).  Adjoints, called with A^T: expanded -> expanded (the same expression), middle -> expanded (blocks 0 and 2 take
+//              the gradient unmixed), expanded -> frames (frame t gathers the blocks with w + k = t, in the order k = 0, 1, 2, before
+//              the product, and its neighbour terms after it).  The slab-in-LDS product is sg_nodemix_kernel's (stgcn.hip).
+//   wingemm    grouped GEMM: row (b, w, ., n) multiplies the weight of window w (stacked (W, cw, ci); one for all: stride 0).  A 16-row
+//              tile never straddles two windows: tiles are counted inside each (b, w) group.  Epilogue GLU (S = sigma(Q) and A = P + b
+//              kept when asked) or none; on the middle block the GLU epilogue also updates the running max `best` and the winner
+//              index `which`: operation 0 writes, later ones replace on strictly greater.
+//   gate_bwd   dPre of operation j = ([upstream] + dBest [which == j] on the middle block) through the GLU derivative
+//   winwgrad   dW (W, cw, ci), db (W, cw) per window: tap_wgrad_body (tap_wgrad_dev.h) with a row map that walks one window's rows
+//
+// fp32 MFMA 16x16x4 throughout (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics.
+// No launch asks for more than the 64 KB of dynamic LDS a launch gets by default: the mix serves N <= 448.
+#include "common.h"
+#include "gptst_hip.h"
+#include "tap_wgrad_dev.h"
+
+#define SS_ACT_NONE 0
+#define SS_ACT_GLU 3
+#define SS_NM_P 36          // pitch of the slab (as SG_NM_P)
+#define SS_MAX_NP 448       // 448 * 36 * 4 = 64 512 bytes
+#define SS_GEMM_THREADS 512
+
+#define SS_F2E 0
+#define SS_E2E 1
+#define SS_E2M 2
+#define SS_M2E 3
+#define SS_E2F 4
+
+__device__ __forceinline__ float ss_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+
+// ---- the mix --------------------------------------------------------------------------------------------------------------------------
+struct SsMix { const float* L; int Np; const float* In; float* Out; int c; int mode; int T; int N; };
+
+// what a workgroup's unit does, as first rows (of N) in In / Out: slab = sum of the nsrc source blocks; output o = [acc[o]] L slab + the
+// sum of its nadd[o] blocks of In
+struct SsPlan { int nsrc, nout; long src[3]; long out[3]; int acc[3]; int nadd[3]; long add[3][4]; };
+
+__device__ __forceinline__ void ss_plan(const SsMix& p, int u, SsPlan& q) {
+    const int T = p.T, W = p.T - 2;
+    const long N = p.N;
+    auto frame = [&](int b, int t) { return ((long)b * T + t) * N; };
+    auto blk = [&](int b, int w, int k) { return (((long)b * W + w) * 3 + k) * N; };
+    auto mid = [&](int b, int w) { return ((long)b * W + w) * N; };
+    q.nsrc = q.nout = 0;
+    if (p.mode == SS_F2E) {
+        const int b = u / T, t = u % T;
+        q.src[q.nsrc++] = frame(b, t);
+        for (int k = 0; k < 3; ++k) {
+            const int w = t - k;
+            if (w < 0 || w >= W) continue;
+            const int o = q.nout++;
+            int na = 0;
+            q.out[o] = blk(b, w, k); q.acc[o] = 1;
+            if (k >= 1) q.add[o][na++] = frame(b, t - 1);
+            if (k <= 1) q.add[o][na++] = frame(b, t + 1);
+            q.nadd[o] = na;
+        }
+    } else if (p.mode == SS_E2E) {
+        const int b = u / (3 * W), w = (u / 3) % W, k = u % 3;
+        int na = 0;
+        q.src[q.nsrc++] = blk(b, w, k);
+        q.out[0] = blk(b, w, k); q.acc[0] = 1; q.nout = 1;
+        if (k >= 1) q.add[0][na++] = blk(b, w, k - 1);
+        if (k <= 1) q.add[0][na++] = blk(b, w, k + 1);
+        q.nadd[0] = na;
+    } else if (p.mode == SS_E2M) {
+        const int b = u / W, w = u % W;
+        q.src[q.nsrc++] = blk(b, w, 1);
+        q.out[0] = mid(b, w); q.acc[0] = 1; q.nout = 1;
+        q.add[0][0] = blk(b, w, 0); q.add[0][1] = blk(b, w, 2); q.nadd[0] = 2;
+    } else if (p.mode == SS_M2E) {
+        const int b = u / W, w = u % W;
+        q.src[q.nsrc++] = mid(b, w);
+        q.nout = 3;
+        for (int k = 0; k < 3; ++k) {
+            q.out[k] = blk(b, w, k); q.acc[k] = k == 1; q.nadd[k] = k == 1 ? 0 : 1; q.add[k][0] = mid(b, w);
+        }
+    } else {                                                    // SS_E2F
+        const int b = u / T, t = u % T;
+        for (int k = 0; k < 3; ++k) {
+            const int w = t - k;
+            if (w >= 0 && w < W) q.src[q.nsrc++] = blk(b, w, k);
+        }
+        int na = 0;
+        q.out[0] = frame(b, t); q.acc[0] = 1; q.nout = 1;
+        if (t < W) q.add[0][na++] = blk(b, t, 1);                           // forward: Z[w, k] took H[w + k - 1] for k >= 1
+        if (t - 1 >= 0 && t - 1 < W) q.add[0][na++] = blk(b, t - 1, 2);
+        if (t - 1 >= 0 && t - 1 < W) q.add[0][na++] = blk(b, t - 1, 0);     // and H[w + k + 1] for k <= 1
+        if (t - 2 >= 0 && t - 2 < W) q.add[0][na++] = blk(b, t - 2, 1);
+        q.nadd[0] = na;
+    }
+}
+
+// one unit and four 16-node tiles per workgroup; 32 channels of the unit's source rows in LDS at a time, L (Np, Np) read from L2
+__global__ __launch_bounds__(256) void ss_mix_kernel(SsMix p) {
+    extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][SS_NM_P]
+    __shared__ SsPlan q;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
+    const int n0 = (blockIdx.y * 4 + wave) * 16;
+    const bool active = n0 < p.Np;
+    if (tid == 0) ss_plan(p, blockIdx.x, q);
+    __syncthreads();
+    const int nsrc = q.nsrc, nout = q.nout;
+    for (int cg = 0; cg * 32 < p.c; ++cg) {
+        __syncthreads();                                                    // the previous group's reads of the slab are done
+        for (int f = tid; f < p.Np * 8; f += 256) {
+            const int m = f >> 3, c4 = f & 7;
+            float4 v = f4zero();
+            if (m < p.N && 32 * cg + 4 * c4 < p.c) {
+                for (int s = 0; s < nsrc; ++s) {
+                    const float4 a = ld4(p.In + (size_t)(q.src[s] + m) * p.c + 32 * cg + 4 * c4);
+                    v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
+                }
+            }
+            st4(slab + m * SS_NM_P + 4 * c4, v);
+        }
+        __syncthreads();
+        if (!active) continue;
+        f32x4 acc[2];
+        acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        const float* lp = p.L + (size_t)(n0 + j) * p.Np + 4 * kk;
+        for (int m0 = 0; m0 < p.Np; m0 += 16) {
+            const float4 a = ld4(lp + m0);
+            const float av[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const float* sp = slab + (m0 + 4 * kk + e) * SS_NM_P + j;
+                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[0], acc[0], 0, 0, 0);
+                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[16], acc[1], 0, 0, 0);
+            }
+        }
+        // ---- epilogue in the accumulator layout: reg r = (node n0 + kk*4 + r, channel 32 cg + 16 ct + j) ----
+        for (int o = 0; o < nout; ++o) {
+            const long ob = q.out[o];
+            const int useacc = q.acc[o], na = q.nadd[o];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                const int ch = 32 * cg + 16 * ct + j;
+                if (ch >= p.c) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int n = n0 + kk * 4 + r;
+                    if (n >= p.N) continue;
+                    float v = useacc ? acc[ct][r] : 0.f;
+                    for (int a = 0; a < na; ++a) v += p.In[(size_t)(q.add[o][a] + n) * p.c + ch];
+                    p.Out[(size_t)(ob + n) * p.c + ch] = v;
+                }
+            }
+        }
+    }
+}
+
+// ---- the grouped GEMM -----------------------------------------------------------------------------------------------------------------
+struct SsGemm {
+    const float* X; int ci; const float* Wt; long wstride; const float* bias; int bstride;
+    float* Y; int co; float* S; float* A; int act;
+    float* best; int* which; int opj;
+    int B, W, R, N, midoff, tpw;
+};
+
+// blockIdx.z = the window; a wave owns 16-row tiles of the window's B groups of R rows and NCT column tiles of 16.  GLU: the first NCT/2
+// tiles are P channels, the other half the Q channels of the same outputs (as sg_tapgemm_kernel).
+template <int NCT>
+__global__ __launch_bounds__(SS_GEMM_THREADS) void ss_wingemm_kernel(SsGemm p) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    constexpr int OCW = 16 * NCT;
+    const int P = p.ci + 4;
+    float* Wl = smem;                       // [OCW][P]
+    float* bl = Wl + OCW * P;               // [OCW]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
+    const int w = blockIdx.z;
+    const bool glu = p.act == SS_ACT_GLU;
+    const int half = OCW / 2;
+    const int c0 = blockIdx.y * (glu ? half : OCW);
+    const float* Wg = p.Wt + (size_t)w * p.wstride;
+    const float* bg = p.bias != nullptr ? p.bias + (size_t)w * p.bstride : nullptr;
+    const int k4 = p.ci >> 2;
+    for (int f = tid; f < OCW * k4; f += SS_GEMM_THREADS) {
+        const int l = f / k4, c4 = f - l * k4;
+        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
+        const int wr = glu && l >= half ? p.co + ch : ch;
+        st4(Wl + l * P + 4 * c4, ch < p.co ? ld4(Wg + (size_t)wr * p.ci + 4 * c4) : f4zero());
+    }
+    if (tid < OCW) {
+        const int l = tid;
+        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
+        const int wr = glu && l >= half ? p.co + ch : ch;
+        bl[l] = (bg != nullptr && ch < p.co) ? bg[wr] : 0.f;
+    }
+    __syncthreads();
+    const int tpg = (p.R + 15) / 16, ntiles = p.B * tpg, nq = p.ci >> 4;
+    const int t0 = (blockIdx.x * (SS_GEMM_THREADS / 64) + wave) * p.tpw, t1 = min(ntiles, t0 + p.tpw);
+    for (int t = t0; t < t1; ++t) {
+        const int b = t / tpg, ri0 = (t - b * tpg) * 16;
+        const size_t gbase = ((size_t)b * p.W + w) * p.R;                   // first row of the (b, w) group
+        const bool rv = ri0 + j < p.R;
+        const float* xp = p.X + (gbase + ri0 + j) * p.ci + 4 * kk;
+        const float* wl = Wl + j * P + 4 * kk;
+        f32x4 acc[NCT];
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) acc[ct] = (f32x4){0.f, 0.f, 0.f, 0.f};
+        for (int qd = 0; qd < nq; ++qd) {
+            const float4 a0 = rv ? ld4(xp + 16 * qd) : f4zero();
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const float4 bq = ld4(wl + 16 * ct * P + 16 * qd);
+                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.x, bq.x, acc[ct], 0, 0, 0);
+                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.y, bq.y, acc[ct], 0, 0, 0);
+                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.z, bq.z, acc[ct], 0, 0, 0);
+                acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(a0.w, bq.w, acc[ct], 0, 0, 0);
+            }
+        }
+        // ---- epilogue in the accumulator layout: reg r = (row ri0 + kk*4 + r of the group, column 16 ct + j) ----
+        if (glu) {
+#pragma unroll
+            for (int ct = 0; ct < NCT / 2; ++ct) {
+                const int ch = c0 + 16 * ct + j;
+                if (ch >= p.co) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ri = ri0 + kk * 4 + r;
+                    if (ri >= p.R) continue;
+                    const size_t e = (gbase + ri) * p.co + ch;
+                    const float pv = acc[ct][r] + bl[16 * ct + j];
+                    const float s = ss_sigmoid(acc[ct + NCT / 2][r] + bl[half + 16 * ct + j]);
+                    const float y = pv * s;
+                    p.Y[e] = y;
+                    if (p.S != nullptr) { p.S[e] = s; p.A[e] = pv; }
+                    if (p.best != nullptr && ri >= p.midoff && ri < p.midoff + p.N) {
+                        const size_t m = (((size_t)b * p.W + w) * p.N + (ri - p.midoff)) * p.co + ch;
+                        if (p.opj == 0 || y > p.best[m]) {                   // an exact tie keeps the earlier operation
+                            p.best[m] = y;
+                            if (p.which != nullptr) p.which[m] = p.opj;
+                        }
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const int ch = c0 + 16 * ct + j;
+                if (ch >= p.co) continue;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ri = ri0 + kk * 4 + r;
+                    if (ri >= p.R) continue;
+                    p.Y[(gbase + ri) * p.co + ch] = acc[ct][r] + bl[16 * ct + j];
+                }
+            }
+        }
+    }
+}
+
+// ---- dPre (rows, 2 co) of operation j: g = [up] + dBest [which == j] on the middle block;  [g S | g A S (1 - S)] ----
+__global__ __launch_bounds__(256) void ss_gate_bwd_kernel(const float* __restrict__ up, const float* __restrict__ dBest, const int* __restrict__ which,
+                                                          int opj, const float* __restrict__ S, const float* __restrict__ A,
+                                                          float* __restrict__ dPre, long n4, int co4, int R, int N, int midoff) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long)gridDim.x * 256) {
+        const long row = i / co4;
+        const int c4 = (int)(i - row * co4);
+        const long grp = row / R;
+        const int ri = (int)(row - grp * R);
+        float4 g = up != nullptr ? ld4(up + 4 * i) : f4zero();
+        if (ri >= midoff && ri < midoff + N) {
+            const long m = ((grp * N + (ri - midoff)) * co4 + c4) * 4;
+            const float4 d = ld4(dBest + m);
+            const int4 wh = *reinterpret_cast<const int4*>(which + m);
+            g.x += wh.x == opj ? d.x : 0.f; g.y += wh.y == opj ? d.y : 0.f; g.z += wh.z == opj ? d.z : 0.f; g.w += wh.w == opj ? d.w : 0.f;
+        }
+        const float4 s = ld4(S + 4 * i), a = ld4(A + 4 * i);
+        float* d = dPre + (row * 2 * co4 + c4) * 4;
+        st4(d, make_float4(g.x * s.x, g.y * s.y, g.z * s.z, g.w * s.w));
+        st4(d + 4 * co4, make_float4(g.x * a.x * (s.x * (1.f - s.x)), g.y * a.y * (s.y * (1.f - s.y)), g.z * a.z * (s.z * (1.f - s.z)),
+                                     g.w * a.w * (s.w * (1.f - s.w))));
+    }
+}
+
+// ---- the weight gradient per window ----
+struct SsWgrad { const float* D; int cw; const float* X; int ci; float* part; float* bpart; int B, W, R, ns, cps, nchunks; };
+
+// blockIdx.z = window * ns + split; virtual row v of a window = row v % R of the group (v / R, window)
+struct SsWgRows {
+    int w, s, W, R, ns;
+    __device__ __forceinline__ SsWgRows(const SsWgrad& p) : w(blockIdx.z / p.ns), s(blockIdx.z % p.ns), W(p.W), R(p.R), ns(p.ns) {}
+    __device__ __forceinline__ int split() const { return s; }
+    __device__ __forceinline__ int slot() const { return w * ns + s; }
+    __device__ __forceinline__ size_t operator()(int v) const { const int b = v / R; return ((size_t)b * W + w) * R + (v - b * R); }
+};
+
+struct SsWgSrc {
+    const SsWgrad& p; const SsWgRows& rows; int kcol; bool kv;
+    __device__ __forceinline__ SsWgSrc(const SsWgrad& p_, const SsWgRows& r_, int kcol_) : p(p_), rows(r_), kcol(kcol_), kv(kcol_ < p_.ci) {}
+    __device__ __forceinline__ float4 operator()(int v, bool rv) const { return (rv && kv) ? ld4(p.X + rows(v) * p.ci + kcol) : f4zero(); }
+};
+
+__global__ __launch_bounds__(256) void ss_winwgrad_kernel(SsWgrad p) {
+    const SsWgRows rows(p);
+    tap_wgrad_body(p.D, p.cw, p.ci, p.part, p.bpart, p.B * p.R, p.cps, p.nchunks, SsWgSrc(p, rows, blockIdx.x * 64 + 4 * (threadIdx.x & 15)), rows);
+}
+
+// ---- entry points ----
+extern "C" int gptst_stsgcn_mix(const float* L, int Np, const float* In, float* Out, int c, int mode, int B, int T, int N, void* stream) {
+    if (!L || !In || !Out || In == Out || B <= 0 || T < 3 || N <= 0 || mode < 0 || mode > 4) return GPTST_EARG;
+    if (Np != 16 * ((N + 15) / 16) || Np > SS_MAX_NP || c < 16 || c % 16) return GPTST_ESHAPE;
+    const long W = T - 2;
+    const long units = mode == SS_F2E || mode == SS_E2F ? (long)B * T : mode == SS_E2E ? (long)B * W * 3 : (long)B * W;
+    if (units > 0x7fffffffL) return GPTST_ESHAPE;
+    const size_t smem = (size_t)Np * SS_NM_P * sizeof(float);
+    SsMix p{L, Np, In, Out, c, mode, T, N};
+    hipLaunchKernelGGL(ss_mix_kernel, dim3((unsigned)units, (Np / 16 + 3) / 4), dim3(256), smem, (hipStream_t)stream, p);
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}
+
+extern "C" int gptst_stsgcn_wingemm(const float* X, int ci, const float* Wt, const float* bias, int shared, float* Y, int co, float* S, float* A,
+                                    int act, float* best, int* which, int opj, int B, int W, int R, int N, void* stream) {
+    if (!X || !Wt || !Y || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N) || (S != nullptr) != (A != nullptr)
+        || (act != SS_ACT_NONE && act != SS_ACT_GLU) || ((S != nullptr || best != nullptr) && act != SS_ACT_GLU) || (which != nullptr && !best)
+        || opj < 0)
+        return GPTST_EARG;
+    if (ci < 16 || ci % 16 || ci > 256 || co < 16 || co % 16 || W > 65535) return GPTST_ESHAPE;
+    const bool wide = ((size_t)64 * (ci + 4) + 64) * sizeof(float) <= 64 * 1024;
+    const int ocw = wide ? 64 : 32, per = act == SS_ACT_GLU ? ocw / 2 : ocw, cw = act == SS_ACT_GLU ? 2 * co : co;
+    const int colblocks = (co + per - 1) / per;
+    const long ntiles = (long)B * ((R + 15) / 16);
+    const int wpb = SS_GEMM_THREADS / 64;
+    long rowblocks = 1024 / ((long)colblocks * W); if (rowblocks < 1) rowblocks = 1;
+    long tpw = (ntiles + wpb * rowblocks - 1) / (wpb * rowblocks); if (tpw < 1) tpw = 1;
+    rowblocks = (ntiles + wpb * tpw - 1) / (wpb * tpw);
+    if (ntiles > 0x7fffffffL || colblocks > 65535) return GPTST_ESHAPE;
+    const size_t smem = ((size_t)ocw * (ci + 4) + ocw) * sizeof(float);
+    SsGemm p{X, ci, Wt, shared ? 0L : (long)cw * ci, bias, shared ? 0 : cw, Y, co, S, A, act, best, which, opj, B, W, R, N, R == N ? 0 : N, (int)tpw};
+    if (wide) hipLaunchKernelGGL(ss_wingemm_kernel<4>, dim3((unsigned)rowblocks, colblocks, W), dim3(SS_GEMM_THREADS), smem, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(ss_wingemm_kernel<2>, dim3((unsigned)rowblocks, colblocks, W), dim3(SS_GEMM_THREADS), smem, (hipStream_t)stream, p);
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}
+
+extern "C" int gptst_stsgcn_gate_bwd(const float* up, const float* dBest, const int* which, int opj, const float* S, const float* A, float* dPre,
+                                     int B, int W, int R, int N, int co, void* stream) {
+    if (!dBest || !which || !S || !A || !dPre || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N) || opj < 0) return GPTST_EARG;
+    if (co < 4 || co % 4) return GPTST_ESHAPE;
+    const long n4 = (long)B * W * R * co / 4;
+    long blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(ss_gate_bwd_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, up, dBest, which, opj, S, A, dPre, n4, co / 4, R, N,
+                       R == N ? 0 : N);
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}
+
+// splits of one window's B R rows
+extern "C" int gptst_stsgcn_winwgrad_nsplit(int wrows, int cw, int ci, int W) {
+    if (wrows <= 0 || cw <= 0 || ci <= 0 || W <= 0) return GPTST_EARG;
+    const int nchunks = (wrows + 63) / 64, tiles = ((cw + 63) / 64) * ((ci + 63) / 64) * W;
+    int ns = 1024 / tiles; if (ns < 1) ns = 1; if (ns > nchunks) ns = nchunks;
+    const int cps = (nchunks + ns - 1) / ns;
+    return (nchunks + cps - 1) / cps;
+}
+
+extern "C" int gptst_stsgcn_winwgrad(const float* D, int cw, const float* X, int ci, float* part, float* bpart, int nsplit, int B, int W, int R,
+                                     void* stream) {
+    if (!D || !X || !part || B <= 0 || W <= 0 || R <= 0 || (long)B * R > 0x7fffffffL) return GPTST_EARG;
+    if (ci < 16 || ci % 16 || cw < 16 || cw % 16 || (long)W * nsplit > 65535) return GPTST_ESHAPE;
+    if (nsplit != gptst_stsgcn_winwgrad_nsplit(B * R, cw, ci, W)) return GPTST_EARG;
+    const int nchunks = (B * R + 63) / 64, cps = (nchunks + nsplit - 1) / nsplit;
+    SsWgrad p{D, cw, X, ci, part, bpart, B, W, R, nsplit, cps, nchunks};
+    hipLaunchKernelGGL(ss_winwgrad_kernel, dim3((ci + 63) / 64, (cw + 63) / 64, W * nsplit), dim3(256), 0, (hipStream_t)stream, p);
+    GPTST_CHECK_LAUNCH();
+    return GPTST_OK;
+}

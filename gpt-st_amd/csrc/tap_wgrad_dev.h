@@ -4,18 +4,27 @@
 // caller's: `src(row, rv)` returns this thread's float4 of Xs[row] (columns kcol .. kcol + 3 with kcol = blockIdx.x * 64 + 4 * (tid % 16)),
 // zeros where the row (rv = row < rows), the column or the tap's time step is outside.
 // Grid (ceil(Ktot / 64), ceil(cw / 64), splits), 256 threads; split z owns the 64-row chunks [z cps, min(nchunks, (z + 1) cps)).
+// A caller whose rows of D are not one contiguous run (ss_winwgrad_kernel, stsgcn.hip: the rows of one window of a (b, w, ...) tensor) passes a
+// row map as well: `rmap.split()` is the split whose chunks this workgroup owns, `rmap.slot()` the partial it writes, `rmap(row)` the row of D.
 #pragma once
 #include "common.h"
 
 #define TAP_WG_P 80         // pitch of the 64 x 64 LDS tiles: 80 mod 64 = 16, so the four k-rows of an operand read land on disjoint banks
 
-template <class Src>
+// all rows, in order: split blockIdx.z owns its chunks and its partial, row r of D is r
+struct TapWgAllRows {
+    __device__ __forceinline__ int split() const { return blockIdx.z; }
+    __device__ __forceinline__ int slot() const { return blockIdx.z; }
+    __device__ __forceinline__ size_t operator()(int row) const { return (size_t)row; }
+};
+
+template <class Src, class Rows>
 __device__ __forceinline__ void tap_wgrad_body(const float* D, int cw, int Ktot, float* part, float* bpart, int rows, int cps, int nchunks,
-                                               const Src& src) {
+                                               const Src& src, const Rows& rmap) {
     __shared__ __attribute__((aligned(16))) float Dl[64 * TAP_WG_P];
     __shared__ __attribute__((aligned(16))) float Xl[64 * TAP_WG_P];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
-    const int kb = blockIdx.x, cb = blockIdx.y, z = blockIdx.z;
+    const int kb = blockIdx.x, cb = blockIdx.y, z = rmap.split(), slot = rmap.slot();
     const int ch0 = z * cps, ch1 = min(nchunks, ch0 + cps);
     // this thread's four float4 of either tile: row rl = i*16 + tid/16, columns 4 (tid % 16)
     const int c4 = tid & 15, rb = tid >> 4;
@@ -31,7 +40,7 @@ __device__ __forceinline__ void tap_wgrad_body(const float* D, int cw, int Ktot,
         for (int i = 0; i < 4; ++i) {
             const int row = chunk * 64 + i * 16 + rb;
             const bool rv = row < rows;
-            dr[i] = (rv && dv) ? ld4(D + (size_t)row * cw + dcol) : f4zero();
+            dr[i] = (rv && dv) ? ld4(D + rmap(row) * cw + dcol) : f4zero();
             xr[i] = src(row, rv);
         }
     };
@@ -58,8 +67,14 @@ __device__ __forceinline__ void tap_wgrad_body(const float* D, int cw, int Ktot,
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int o = cb * 64 + 16 * wave + kk * 4 + r;
-            if (o < cw && k < Ktot) part[((size_t)z * cw + o) * Ktot + k] = acc[nt][r];
+            if (o < cw && k < Ktot) part[((size_t)slot * cw + o) * Ktot + k] = acc[nt][r];
         }
     }
-    if (bpart != nullptr && kb == 0 && tid < 64 && cb * 64 + tid < cw) bpart[(size_t)z * cw + cb * 64 + tid] = bsum;
+    if (bpart != nullptr && kb == 0 && tid < 64 && cb * 64 + tid < cw) bpart[(size_t)slot * cw + cb * 64 + tid] = bsum;
+}
+
+template <class Src>
+__device__ __forceinline__ void tap_wgrad_body(const float* D, int cw, int Ktot, float* part, float* bpart, int rows, int cps, int nchunks,
+                                               const Src& src) {
+    tap_wgrad_body(D, cw, Ktot, part, bpart, rows, cps, nchunks, src, TapWgAllRows());
 }

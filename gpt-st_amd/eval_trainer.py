@@ -1,6 +1,6 @@
 """``-mode eval`` training loop (reference model/BasicTrainer.py:38-123 non-pretrain branches, :125-197, :209-248): a downstream predictor
-is trained on the enhanced embedding — frozen (or, -finetune_encoder True, fine-tuned) HIP encoder -> Fusion -> predictor (enhance.EnhanceFrontEnd) — with the masked-MAE loss on
-de-normalised values (Run.py:91-101, lib/metrics.py:11-18), gradient clipping and Adam + MultiStepLR (Run.py:134-141); the best model
+is trained on the enhanced embedding — frozen (or, -finetune_encoder True, fine-tuned) HIP encoder -> Fusion -> predictor (enhance.EnhanceFrontEnd) — with the conf's loss on
+de-normalised values (``mask_mae``: Run.py:91-101, lib/metrics.py:11-18; ``mask_huber``: Run.py:103-113, lib/metrics.py:20-29), gradient clipping and Adam + MultiStepLR (Run.py:134-141); the best model
 on the validation loss is kept (early stopping as in the reference) and tested per horizon on the test loader, the metric sums
 accumulated on the device by gptst_metrics_accum.  The trainable part is ordinary torch autograd (downstream plumbing, not the hot path)."""
 import copy
@@ -16,6 +16,18 @@ def masked_mae(pred, true, mean, std, thresh):
     p, y = pred * std + mean, true * std + mean
     keep = y > thresh
     return (y - p).abs()[keep].mean()
+
+
+def masked_huber(pred, true, mean, std, thresh, delta=1.0):
+    """scaler_huber_loss without a mask (Run.py:103-113, lib/metrics.py:20-29): de-normalise, keep cells with true > thresh, mean of
+    r^2 / 2 where r = |pred - true| <= delta, of delta r - delta^2 / 2 beyond."""
+    p, y = pred * std + mean, true * std + mean
+    keep = y > thresh
+    r = (p[keep] - y[keep]).abs()
+    return torch.where(r <= delta, 0.5 * r * r, delta * r - 0.5 * delta * delta).mean()
+
+
+LOSSES = {"mask_mae": masked_mae, "mask_huber": masked_huber}
 
 
 class EvalTrainer:
@@ -41,7 +53,10 @@ class EvalTrainer:
         return [dict(params=rest), dict(params=enc, lr=args.lr_init * float(getattr(args, "encoder_lr_scale", 1.0)))]
 
     def _loss(self, out, target):
-        return masked_mae(out, target[..., :self.args.output_dim], self.mean, self.std, self.args.mape_thresh)
+        name = str(self.args.loss_func)
+        if name not in LOSSES:
+            raise ValueError("-mode eval has the loss functions %s, got loss_func %r" % (", ".join(sorted(LOSSES)), name))
+        return LOSSES[name](out, target[..., :self.args.output_dim], self.mean, self.std, self.args.mape_thresh)
 
     def train_epoch(self, epoch):                                             # BasicTrainer.py:67-123, mode != 'pretrain'
         a = self.args

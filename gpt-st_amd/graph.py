@@ -70,6 +70,15 @@ def astgcn_graph(A, K):
     return torch.tensor(cheb_polynomials(scaled_laplacian(A), K), dtype=torch.float32)
 
 
+def stsgcn_graph(A):
+    """A^ (N, N) fp32 = A with every diagonal entry 1: the diagonal block of the reference's ``construct_adj`` (STSGCN.py:237-253), whose
+    (3N, 3N) localized adjacency is A^ on the three diagonal blocks and the identity on the blocks of adjacent steps.  ``predictors.STSGCN``
+    builds that matrix for its torch backend (``stsgcn.window_adjacency``); the HIP backend multiplies by A^ alone."""
+    a = np.array(A, dtype=np.float64)
+    np.fill_diagonal(a, 1.0)
+    return torch.tensor(a, dtype=torch.float32)
+
+
 def normalized_adjacency(A):
     """TGCN's graph (reference TGCN.py:8-25, ``calculate_normalized_laplacian``): with A~ = A + I and D = diag(row sums of A~), the reference's
     operand order (A~ D^-1/2)^T D^-1/2 = D^-1/2 A~^T D^-1/2 — for a non-symmetric A the TRANSPOSE of the textbook D^-1/2 A~ D^-1/2."""

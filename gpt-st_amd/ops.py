@@ -1356,3 +1356,63 @@ def astgcn_rowln_bwd_param(dY, X, mean, rstd):
     pg, pb = (torch.empty(ns, c, device=X.device, dtype=torch.float32) for _ in range(2))
     _call("gptst_astgcn_rowln_bwd_param", _p(dY), _p(X), _p(mean), _p(rstd), _p(pg), _p(pb), ns, rows, c, tag="c%d" % c, nbytes=_nb(dY, X))
     return pg.sum(0), pb.sum(0)
+
+
+# ---- the downstream STSGCN predictor (csrc/stsgcn.hip) ----------------------------------------------------------------------------------
+# row layouts of a layer over T frames, W = T - 2 windows: frames (B T N), expanded (B W 3 N): block (w, k) stands for frame w + k, middle (B W N)
+MIX_F2E, MIX_E2E, MIX_E2M, MIX_M2E, MIX_E2F = 0, 1, 2, 3, 4
+_MIX_ROWS = {MIX_F2E: ("f", "e"), MIX_E2E: ("e", "e"), MIX_E2M: ("e", "m"), MIX_M2E: ("m", "e"), MIX_E2F: ("e", "f")}
+
+
+def stsgcn_mix(Lp, In, mode, B, T, N):
+    """mix(S)_k = L S_k + [k >= 1] S_{k-1} + [k <= 1] S_{k+1} without the (3N, 3N) matrix; Lp (Np, Np) = A^ zero-padded (its transpose for the
+    adjoints).  mode: MIX_F2E frames -> expanded, MIX_E2E, MIX_E2M (the middle block only), MIX_M2E (adjoint of E2M), MIX_E2F (adjoint of F2E)."""
+    _chk(Lp, In)
+    W, c = T - 2, In.shape[1]
+    rows = {"f": B * T * N, "e": B * W * 3 * N, "m": B * W * N}
+    src, dst = _MIX_ROWS[mode]
+    assert In.shape[0] == rows[src] and Lp.dim() == 2, (In.shape, mode, B, T, N)
+    Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
+    _call("gptst_stsgcn_mix", _p(Lp), Lp.shape[0], _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
+    return Out
+
+
+def stsgcn_wingemm(X, Wt, bias, act, B, W, R, N, keep=False, best=None, which=None, opj=0):
+    """Y (B W R, co) = act(X Wt[w]^T + bias[w]) for the rows of window w; Wt (W, cw, ci) — or (1, cw, ci): one weight for all windows — and bias
+    (W | 1, cw) or None; act ACT_GLU (cw = 2 co) or ACT_NONE.  keep (GLU): -> (Y, S, A).  best (B W N, co) / which (int32): the running max on
+    the middle block and the operation that holds it, updated in place (opj = 0 writes, later operations replace where strictly greater)."""
+    _chk(X, Wt, bias, best)
+    ci = X.shape[1]
+    cw = Wt.shape[1]
+    co = cw // 2 if act == ACT_GLU else cw
+    assert X.shape[0] == B * W * R and Wt.shape[2] == ci and Wt.shape[0] in (1, W) and (bias is None or bias.shape == Wt.shape[:2])
+    assert which is None or (which.dtype == torch.int32 and which.is_contiguous() and which.shape == best.shape)
+    assert best is None or best.shape == (B * W * N, co)
+    Y = torch.empty(B * W * R, co, device=X.device, dtype=torch.float32)
+    S, A = (torch.empty_like(Y), torch.empty_like(Y)) if keep else (None, None)
+    _call("gptst_stsgcn_wingemm", _p(X), ci, _p(Wt), _p(bias), int(Wt.shape[0] == 1 and W > 1), _p(Y), co, _p(S), _p(A), act, _p(best), _p(which), opj,
+          B, W, R, N, tag="ci%d co%d act%d R%d W%d" % (ci, co, act, R // N, W), nbytes=_nb(X, Wt, Y, S, A))
+    return (Y, S, A) if keep else Y
+
+
+def stsgcn_gate_bwd(up, dBest, which, opj, S, A, B, W, R, N):
+    """dPre (B W R, 2 co) of operation opj: g = up (or 0) + dBest [which == opj] on the middle block, through the GLU derivative"""
+    _chk(up, dBest, S, A)
+    co = S.shape[1]
+    assert S.shape[0] == B * W * R and dBest.shape == (B * W * N, co) and which.dtype == torch.int32 and which.shape == dBest.shape
+    dPre = torch.empty(B * W * R, 2 * co, device=S.device, dtype=torch.float32)
+    _call("gptst_stsgcn_gate_bwd", _p(up), _p(dBest), _p(which), opj, _p(S), _p(A), _p(dPre), B, W, R, N, co, tag="co%d R%d W%d" % (co, R // N, W),
+          nbytes=_nb(up, dBest, S, A, dPre))
+    return dPre
+
+
+def stsgcn_winwgrad(D, X, B, W, R):
+    """-> (dW (W, cw, ci), db (W, cw)) per window: row-split partials summed in a fixed order"""
+    _chk(D, X)
+    cw, ci = D.shape[1], X.shape[1]
+    assert D.shape[0] == X.shape[0] == B * W * R
+    ns = _C.lib().value("gptst_stsgcn_winwgrad_nsplit", B * R, cw, ci, W)
+    part = torch.empty(W, ns, cw, ci, device=D.device, dtype=torch.float32)
+    bpart = torch.empty(W, ns, cw, device=D.device, dtype=torch.float32)
+    _call("gptst_stsgcn_winwgrad", _p(D), cw, _p(X), ci, _p(part), _p(bpart), ns, B, W, R, tag="cw%d ci%d R%d W%d" % (cw, ci, R, W), nbytes=_nb(D, X, part))
+    return part.sum(1), bpart.sum(1)
