@@ -147,6 +147,8 @@ __device__ __forceinline__ float lrelu(float x) { return x > 0.f ? x : LRELU_SLO
 // derivative selected by the sign of the OUTPUT (slope > 0 keeps the sign; x == 0 -> slope, as ATen).
 __device__ __forceinline__ float lrelu_grad_from_out(float out) { return out > 0.f ? 1.f : LRELU_SLOPE; }
 
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // store of a tensor whose consumer is far away (the saved mix R of hyperTem: read by the backward ~0.5 ms later).  -DHT_R_NT: nontemporal.

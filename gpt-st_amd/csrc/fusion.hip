@@ -18,7 +18,6 @@
 
 struct FuW { const float* Ws; const float* bs; const float* Wh; const float* bh; const float* Wo; const float* bo; const float* Wt; const float* bt; };
 
-__device__ __forceinline__ float fu_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // x_t[c] for the four channels c0..c0+3 of a row whose `base` flow values are s[]
 __device__ __forceinline__ float4 fu_lift4(const float* __restrict__ Wtl, const float* __restrict__ btl, const float (&s)[FU_MAXB], int base, int c0) {
@@ -133,7 +132,7 @@ __global__ __launch_bounds__(256, 2) void fusion_gate_fwd_kernel(const float* __
         for (int ct = 0; ct < 4; ++ct)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const float z = fu_sigmoid(acc[ct][r] + bgl[16 * ct + j]);
+                const float z = sigmoidf_(acc[ct][r] + bgl[16 * ct + j]);
                 zv[ct][r] = z;
                 hv[ct][r] = fmaf(z, fd[ct][r] - xd[ct][r], xd[ct][r]);          // z F + (1 - z) x_t
             }

@@ -23,8 +23,6 @@
 #define MT_P (MT_KC + 4)
 #define MT_MAX_TAPS 32
 
-__device__ __forceinline__ float mt_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-
 struct MtTaps { int n; int off[MT_MAX_TAPS]; };
 
 struct MtTg {
@@ -129,7 +127,7 @@ __global__ __launch_bounds__(MT_THREADS) void mt_tapgemm_kernel(MtTg p) {
                     const int ch = c0 + 16 * ct + j;
                     if (ch >= p.co) continue;
                     const float tn = tanhf(acc[i][ct][r] + bl[16 * ct + j]);
-                    const float s = mt_sigmoid(acc[i][ct + 2][r] + bl[32 + 16 * ct + j]);
+                    const float s = sigmoidf_(acc[i][ct + 2][r] + bl[32 + 16 * ct + j]);
                     const size_t o = (size_t)row * p.co + ch;
                     p.Y[o] = p.OM != nullptr ? tn * s * p.OM[o] : tn * s;
                     if (p.Tn != nullptr) { p.Tn[o] = tn; p.S[o] = s; }
@@ -332,10 +330,8 @@ extern "C" int gptst_mtgnn_wgrad(const float* D, int cw, const float* X, int ldx
 
 extern "C" int gptst_mtgnn_graphgrad_nsplit(int units, int N, int ks) {
     if (units <= 0 || N <= 0 || ks <= 0) return GPTST_EARG;
-    const int t = (N + 63) / 64, tiles = t * t * ks;
-    int ns = 1024 / tiles; if (ns < 1) ns = 1; if (ns > units) ns = units;
-    const int ups = (units + ns - 1) / ns;
-    return (units + ups - 1) / ups;
+    const int t = (N + 63) / 64;
+    return wgrad_split_rule(t * t * ks, units);
 }
 
 extern "C" int gptst_mtgnn_graphgrad(const float* D, int ldd, int dcol0, const float* X, int ldx, int c, int ks, float* part, int nsplit, int units,

@@ -4,24 +4,27 @@
 //   tapgemm     Y = act(sum_j X[t + dt_j] W_j + b + res)     temporal convolutions ('same' zero padding in T: a tap is a row offset of
 //               dt_j * N rows, a tap outside [0, T) is not loaded), their data backward (the taps mirrored, W transposed by the caller),
 //               and the two channel GEMMs of the graph convolution.  GLU / relu / sigmoid in the epilogue; the 1x1 align is one more tap.
-//   gate_bwd    dPre from dOut and what the forward kept (GLU: sigma(Q) and P + res; relu / sigmoid: the output itself)
+//               The staging of the weight rows (with the GLU row interleave) is row_gemm_stage (row_gemm_dev.h), shared with
+//               ss_wingemm_kernel (stsgcn.hip), and so is the launch plan; the tile loop and the epilogue are this kernel's own.
+//   gate_bwd    dPre from dOut and what the forward kept (GLU: sigma(Q) and P + res, stored by glu_bwd_store as in stsgcn.hip; relu /
+//               sigmoid: the output itself)
 //   wgrad       dW[o][k] = sum_rows dPre[row][o] X_shift[row][k] (rectangular, shifted) + column sums of dPre: row-split partials, fixed order
 //   nodemix     per (b, t): Z_k = L_k X (expand) or  Y = sum_k L_k Z_k + R (reduce); a 32-channel slab of the unit in LDS, L_k read from L2
+//               (the product is node_mix_slab, node_mix_dev.h, which ss_mix_kernel of stsgcn.hip runs too)
 //   ln_fwd/bwd  LayerNorm over (N, C) per (b, t); variance about the mean; dgamma / dbeta as unit-split partials
 //
 // fp32 MFMA 16x16x4 throughout (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics.
 #include "common.h"
 #include "gptst_hip.h"
+#include "node_mix_dev.h"
+#include "row_gemm_dev.h"
 #include "tap_wgrad_dev.h"
 
 #define SG_ACT_NONE 0
 #define SG_ACT_RELU 1
 #define SG_ACT_SIGMOID 2
 #define SG_ACT_GLU 3
-#define SG_TG_THREADS 512
 #define SG_MAX_DEVICES 64
-
-__device__ __forceinline__ float sg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct SgTap { int n; int dt[4]; };
 
@@ -33,36 +36,21 @@ struct SgTg {
     int rows, T, N, tpw;
 };
 
-// a wave owns 16-row tiles and NCT column tiles of 16; the workgroup's 16*NCT weight rows (all K) sit in LDS.  GLU: the first NCT/2 tiles
-// are P channels, the other half the Q channels of the same outputs, so a lane holds P and Q of one (row, channel) pair.
+// a wave owns 16-row tiles and NCT column tiles of 16; the workgroup's 16*NCT weight rows (all K) sit in LDS, staged by row_gemm_stage
+// (row_gemm_dev.h).  GLU: the first NCT/2 tiles are P channels, the other half the Q channels of the same outputs, so a lane holds P and Q of
+// one (row, channel) pair.
 template <int NCT>
-__global__ __launch_bounds__(SG_TG_THREADS) void sg_tapgemm_kernel(SgTg p) {
+__global__ __launch_bounds__(ROW_GEMM_THREADS) void sg_tapgemm_kernel(SgTg p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int OCW = 16 * NCT;
+    constexpr int OCW = 16 * NCT, half = OCW / 2;
     const int P = p.Ktot + 4;
-    float* Wl = smem;                       // [OCW][P]
-    float* bl = Wl + OCW * P;               // [OCW]
+    const float* Wl = smem;                 // [OCW][P]
+    const float* bl = Wl + OCW * P;         // [OCW]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const bool glu = p.act == SG_ACT_GLU;
-    const int half = OCW / 2;
-    const int c0 = blockIdx.y * (glu ? half : OCW);
-    // ---- stage the weight rows of this column block (rows past the last channel: zero) ----
-    const int k4 = p.Ktot >> 2;
-    for (int f = tid; f < OCW * k4; f += SG_TG_THREADS) {
-        const int l = f / k4, c4 = f - l * k4;
-        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
-        const int wr = glu && l >= half ? p.co + ch : ch;
-        st4(Wl + l * P + 4 * c4, ch < p.co ? ld4(p.W + (size_t)wr * p.Ktot + 4 * c4) : f4zero());
-    }
-    if (tid < OCW) {
-        const int l = tid;
-        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
-        const int wr = glu && l >= half ? p.co + ch : ch;
-        bl[l] = (p.bias != nullptr && ch < p.co) ? p.bias[wr] : 0.f;
-    }
-    __syncthreads();
+    const int c0 = row_gemm_stage<NCT>(smem, p.W, p.bias, p.Ktot, p.co, glu);
     const int ntiles = (p.rows + 15) / 16, nq = p.ci >> 4;
-    const int t0 = (blockIdx.x * (SG_TG_THREADS / 64) + wave) * p.tpw, t1 = min(ntiles, t0 + p.tpw);
+    const int t0 = (blockIdx.x * (ROW_GEMM_THREADS / 64) + wave) * p.tpw, t1 = min(ntiles, t0 + p.tpw);
     for (int t = t0; t < t1; ++t) {
         const int row0 = t * 16, ra = row0 + j;
         const bool rv = ra < p.rows;
@@ -111,7 +99,7 @@ __global__ __launch_bounds__(SG_TG_THREADS) void sg_tapgemm_kernel(SgTg p) {
                     if (row >= p.rows) continue;
                     float pv = acc[ct][r] + bl[16 * ct + j];
                     if (ch < p.res_w) pv += p.R[(size_t)row * p.ldr + ch];
-                    const float s = sg_sigmoid(acc[ct + NCT / 2][r] + bl[half + 16 * ct + j]);
+                    const float s = sigmoidf_(acc[ct + NCT / 2][r] + bl[half + 16 * ct + j]);
                     p.Y[(size_t)row * p.co + ch] = pv * s;
                     if (p.S != nullptr) { p.S[(size_t)row * p.co + ch] = s; p.A[(size_t)row * p.co + ch] = pv; }
                 }
@@ -128,7 +116,7 @@ __global__ __launch_bounds__(SG_TG_THREADS) void sg_tapgemm_kernel(SgTg p) {
                     float v = acc[ct][r] + bl[16 * ct + j];
                     if (ch < p.res_w) v += p.R[(size_t)row * p.ldr + ch];
                     if (p.act == SG_ACT_RELU) v = fmaxf(v, 0.f);
-                    else if (p.act == SG_ACT_SIGMOID) v = sg_sigmoid(v);
+                    else if (p.act == SG_ACT_SIGMOID) v = sigmoidf_(v);
                     p.Y[(size_t)row * p.co + ch] = v;
                 }
             }
@@ -146,10 +134,7 @@ __global__ __launch_bounds__(256) void sg_gate_bwd_kernel(const float* __restric
             const long row = i / co4;
             const int c4 = (int)(i - row * co4);
             const float4 s = ld4(S + 4 * i), a = ld4(A + 4 * i);
-            float* d = dPre + (row * 2 * co4 + c4) * 4;
-            st4(d, make_float4(g.x * s.x, g.y * s.y, g.z * s.z, g.w * s.w));
-            st4(d + 4 * co4, make_float4(g.x * a.x * (s.x * (1.f - s.x)), g.y * a.y * (s.y * (1.f - s.y)), g.z * a.z * (s.z * (1.f - s.z)),
-                                         g.w * a.w * (s.w * (1.f - s.w))));
+            glu_bwd_store(dPre + (row * 2 * co4 + c4) * 4, co4, g, s, a);
         } else {
             const float4 o = ld4(out + 4 * i);
             if (act == SG_ACT_RELU) st4(dPre + 4 * i, make_float4(o.x > 0.f ? g.x : 0.f, o.y > 0.f ? g.y : 0.f, o.z > 0.f ? g.z : 0.f, o.w > 0.f ? g.w : 0.f));
@@ -183,12 +168,10 @@ __global__ __launch_bounds__(256) void sg_wgrad_kernel(SgWg p) {
 
 // ---- node mixing with the Chebyshev polynomials: one (b, t) unit and four 16-node tiles per workgroup ----
 // L (ks, Np, Np) zero-padded to Np = 16 ceil(N / 16);  expand: Out[:, k c + ch] = (L_k In)[:, ch];  reduce: Out = sum_k L_k In[:, k c + ch] + R
-#define SG_NM_P 36
-
 struct SgNm { const float* L; int Np; int ks; const float* In; float* Out; const float* R; int c; int reduce; int N; };
 
 __global__ __launch_bounds__(256) void sg_nodemix_kernel(SgNm p) {
-    extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][SG_NM_P]: 32 channels of the unit's rows
+    extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][NODE_MIX_P]: 32 channels of the unit's rows
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const int unit = blockIdx.x, nt = blockIdx.y * 4 + wave, n0 = nt * 16;
     const bool active = n0 < p.Np;
@@ -204,23 +187,13 @@ __global__ __launch_bounds__(256) void sg_nodemix_kernel(SgNm p) {
                 for (int f = tid; f < p.Np * 8; f += 256) {
                     const int m = f >> 3, c4 = f & 7;
                     const bool v = m < p.N && 32 * cg + 4 * c4 < p.c;
-                    st4(slab + m * SG_NM_P + 4 * c4, v ? ld4(p.In + (rbase + m) * ldi + col0 + 4 * c4) : f4zero());
+                    st4(slab + m * NODE_MIX_P + 4 * c4, v ? ld4(p.In + (rbase + m) * ldi + col0 + 4 * c4) : f4zero());
                 }
                 __syncthreads();
             }
             if (!active) continue;
             if (!p.reduce) acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            const float* lp = p.L + ((size_t)k * p.Np + n0 + j) * p.Np + 4 * kk;
-            for (int m0 = 0; m0 < p.Np; m0 += 16) {
-                const float4 a = ld4(lp + m0);
-                const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float* sp = slab + (m0 + 4 * kk + e) * SG_NM_P + j;
-                    acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[0], acc[0], 0, 0, 0);
-                    acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[16], acc[1], 0, 0, 0);
-                }
-            }
+            node_mix_slab(acc, p.L + ((size_t)k * p.Np + n0 + j) * p.Np + 4 * kk, slab, p.Np, j, kk);
             if (!p.reduce) {
 #pragma unroll
                 for (int ct = 0; ct < 2; ++ct) {
@@ -335,20 +308,9 @@ static bool sg_taps_ok(int ntap, const int* dt, int T) {
     return true;
 }
 
-// the launch plan of the tap GEMM: the one place that derives it, for the launch and for the query of the tests
-struct SgTgPlan { bool wide; int ocw, colblocks, rowblocks, tpw; };
-
-static SgTgPlan sg_tapgemm_plan(int rows, int co, int Ktot, int act) {
-    SgTgPlan g;
-    g.wide = Ktot <= 384;                                            // 64 weight rows of up to 388 floats: 99 KB; beyond that 32 rows
-    g.ocw = g.wide ? 64 : 32;
-    const int per = act == SG_ACT_GLU ? g.ocw / 2 : g.ocw;
-    const int ntiles = (rows + 15) / 16, wpb = SG_TG_THREADS / 64;
-    g.colblocks = (co + per - 1) / per;
-    int rowblocks = 512 / g.colblocks; if (rowblocks < 1) rowblocks = 1;
-    g.tpw = (ntiles + wpb * rowblocks - 1) / (wpb * rowblocks); if (g.tpw < 1) g.tpw = 1;
-    g.rowblocks = (ntiles + wpb * g.tpw - 1) / (wpb * g.tpw);
-    return g;
+// the launch plan of the tap GEMM: 64 weight rows of up to 388 floats (99 KB), beyond that 32 rows; about 512 workgroups
+static RowGemmPlan sg_tapgemm_plan(int rows, int co, int Ktot, int act) {
+    return row_gemm_plan((rows + 15) / 16, co, act == SG_ACT_GLU, Ktot <= 384, 1, 512);
 }
 
 // (include/gptst_hip_testing.h) tiles per wave of the launch gptst_stgcn_tapgemm makes for this shape
@@ -366,10 +328,9 @@ extern "C" int gptst_stgcn_tapgemm(const float* X, int ldx, int ci, int ntap, in
         return GPTST_EARG;
     const int Ktot = ntap * ci;
     if (ci < 16 || ci % 16 || co < 16 || co % 16 || ldx % 4 || Ktot > 1024) return GPTST_ESHAPE;
-    const SgTgPlan g = sg_tapgemm_plan(rows, co, Ktot, act);
-    const bool wide = g.wide;
-    const int colblocks = g.colblocks, rowblocks = g.rowblocks, tpw = g.tpw;
-    const size_t smem = ((size_t)g.ocw * (Ktot + 4) + g.ocw) * sizeof(float);
+    const RowGemmPlan pl = sg_tapgemm_plan(rows, co, Ktot, act);
+    const int colblocks = pl.colblocks, rowblocks = pl.rowblocks, tpw = pl.tpw;
+    const size_t smem = ((size_t)pl.ocw * (Ktot + 4) + pl.ocw) * sizeof(float);
     SgTg p{X, ldx, ci, SgTap{ntap, {dt0, dt1, dt2, dt3}}, W, Ktot, bias, res_w > 0 ? R : nullptr, ldr, res_w, Y, co, S, A, act, rows, T, N, tpw};
     // more than 64 KB of dynamic LDS needs the attribute, on every device this process launches on
     static bool attr_set[SG_MAX_DEVICES] = {};
@@ -382,8 +343,8 @@ extern "C" int gptst_stgcn_tapgemm(const float* X, int ldx, int ci, int ntap, in
         if (e != hipSuccess) return (int)e;
         if (dev < SG_MAX_DEVICES) attr_set[dev] = true;       // (a race sets it twice: harmless)
     }
-    if (wide) hipLaunchKernelGGL(sg_tapgemm_kernel<4>, dim3(rowblocks, colblocks), dim3(SG_TG_THREADS), smem, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(sg_tapgemm_kernel<2>, dim3(rowblocks, colblocks), dim3(SG_TG_THREADS), smem, (hipStream_t)stream, p);
+    if (pl.wide) hipLaunchKernelGGL(sg_tapgemm_kernel<4>, dim3(rowblocks, colblocks), dim3(ROW_GEMM_THREADS), smem, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(sg_tapgemm_kernel<2>, dim3(rowblocks, colblocks), dim3(ROW_GEMM_THREADS), smem, (hipStream_t)stream, p);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
 }
@@ -401,10 +362,7 @@ extern "C" int gptst_stgcn_gate_bwd(const float* dOut, const float* out, const f
 
 extern "C" int gptst_stgcn_wgrad_nsplit(int rows, int cw, int Ktot) {
     if (rows <= 0 || cw <= 0 || Ktot <= 0) return GPTST_EARG;
-    const int nchunks = (rows + 63) / 64, tiles = ((cw + 63) / 64) * ((Ktot + 63) / 64);
-    int ns = 1024 / tiles; if (ns < 1) ns = 1; if (ns > nchunks) ns = nchunks;
-    const int cps = (nchunks + ns - 1) / ns;
-    return (nchunks + cps - 1) / cps;
+    return wgrad_split_rule(((cw + 63) / 64) * ((Ktot + 63) / 64), (rows + 63) / 64);
 }
 
 extern "C" int gptst_stgcn_wgrad(const float* D, int cw, const float* X, int ldx, int ci, int ntap, int dt0, int dt1, int dt2, int dt3, float* part,
@@ -424,8 +382,8 @@ extern "C" int gptst_stgcn_wgrad(const float* D, int cw, const float* X, int ldx
 extern "C" int gptst_stgcn_nodemix(const float* L, int Np, int ks, const float* In, float* Out, const float* R, int c, int reduce, int units, int N,
                                    void* stream) {
     if (!L || !In || !Out || units <= 0 || N <= 0 || ks <= 0 || (R != nullptr && !reduce)) return GPTST_EARG;
-    if (Np != 16 * ((N + 15) / 16) || c < 16 || c % 16 || (size_t)Np * SG_NM_P * sizeof(float) > 160 * 1024) return GPTST_ESHAPE;
-    const size_t smem = (size_t)Np * SG_NM_P * sizeof(float);
+    if (Np != 16 * ((N + 15) / 16) || c < 16 || c % 16 || (size_t)Np * NODE_MIX_P * sizeof(float) > 160 * 1024) return GPTST_ESHAPE;
+    const size_t smem = (size_t)Np * NODE_MIX_P * sizeof(float);
     if (smem > 64 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void*)sg_nodemix_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
         if (e != hipSuccess) return (int)e;

@@ -10,33 +10,34 @@
 //              w + k = t; no expanded copy of the input exists), expanded -> expanded, expanded -> middle (the last operation needs only
 //              k = 1).  Adjoints, called with A^T: expanded -> expanded (the same expression), middle -> expanded (blocks 0 and 2 take
 //              the gradient unmixed), expanded -> frames (frame t gathers the blocks with w + k = t, in the order k = 0, 1, 2, before
-//              the product, and its neighbour terms after it).  The slab-in-LDS product is sg_nodemix_kernel's (stgcn.hip).
+//              the product, and its neighbour terms after it).  The slab-in-LDS product is node_mix_slab (node_mix_dev.h), which
+//              sg_nodemix_kernel (stgcn.hip) runs too; the fill of the slab and the epilogue are this kernel's own.
 //   wingemm    grouped GEMM: row (b, w, ., n) multiplies the weight of window w (stacked (W, cw, ci); one for all: stride 0).  A 16-row
 //              tile never straddles two windows: tiles are counted inside each (b, w) group.  Epilogue GLU (S = sigma(Q) and A = P + b
 //              kept when asked) or none; on the middle block the GLU epilogue also updates the running max `best` and the winner
-//              index `which`: operation 0 writes, later ones replace on strictly greater.
-//   gate_bwd   dPre of operation j = ([upstream] + dBest [which == j] on the middle block) through the GLU derivative
+//              index `which`: operation 0 writes, later ones replace on strictly greater.  The staging of the window's weight rows is
+//              row_gemm_stage (row_gemm_dev.h), shared with sg_tapgemm_kernel (stgcn.hip), and so is the launch plan; the tile loop and
+//              the epilogue are this kernel's own.
+//   gate_bwd   dPre of operation j = ([upstream] + dBest [which == j] on the middle block) through the GLU derivative (glu_bwd_store)
 //   winwgrad   dW (W, cw, ci), db (W, cw) per window: tap_wgrad_body (tap_wgrad_dev.h) with a row map that walks one window's rows
 //
 // fp32 MFMA 16x16x4 throughout (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics.
 // No launch asks for more than the 64 KB of dynamic LDS a launch gets by default: the mix serves N <= 448.
 #include "common.h"
 #include "gptst_hip.h"
+#include "node_mix_dev.h"
+#include "row_gemm_dev.h"
 #include "tap_wgrad_dev.h"
 
 #define SS_ACT_NONE 0
 #define SS_ACT_GLU 3
-#define SS_NM_P 36          // pitch of the slab (as SG_NM_P)
-#define SS_MAX_NP 448       // 448 * 36 * 4 = 64 512 bytes
-#define SS_GEMM_THREADS 512
+#define SS_MAX_NP 448       // 448 * NODE_MIX_P * 4 = 64 512 bytes
 
 #define SS_F2E 0
 #define SS_E2E 1
 #define SS_E2M 2
 #define SS_M2E 3
 #define SS_E2F 4
-
-__device__ __forceinline__ float ss_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 // ---- the mix --------------------------------------------------------------------------------------------------------------------------
 struct SsMix { const float* L; int Np; const float* In; float* Out; int c; int mode; int T; int N; };
@@ -103,7 +104,7 @@ __device__ __forceinline__ void ss_plan(const SsMix& p, int u, SsPlan& q) {
 
 // one unit and four 16-node tiles per workgroup; 32 channels of the unit's source rows in LDS at a time, L (Np, Np) read from L2
 __global__ __launch_bounds__(256) void ss_mix_kernel(SsMix p) {
-    extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][SS_NM_P]
+    extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][NODE_MIX_P]
     __shared__ SsPlan q;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const int n0 = (blockIdx.y * 4 + wave) * 16;
@@ -122,23 +123,13 @@ __global__ __launch_bounds__(256) void ss_mix_kernel(SsMix p) {
                     v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
                 }
             }
-            st4(slab + m * SS_NM_P + 4 * c4, v);
+            st4(slab + m * NODE_MIX_P + 4 * c4, v);
         }
         __syncthreads();
         if (!active) continue;
         f32x4 acc[2];
         acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* lp = p.L + (size_t)(n0 + j) * p.Np + 4 * kk;
-        for (int m0 = 0; m0 < p.Np; m0 += 16) {
-            const float4 a = ld4(lp + m0);
-            const float av[4] = {a.x, a.y, a.z, a.w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const float* sp = slab + (m0 + 4 * kk + e) * SS_NM_P + j;
-                acc[0] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[0], acc[0], 0, 0, 0);
-                acc[1] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[e], sp[16], acc[1], 0, 0, 0);
-            }
-        }
+        node_mix_slab(acc, p.L + (size_t)(n0 + j) * p.Np + 4 * kk, slab, p.Np, j, kk);
         // ---- epilogue in the accumulator layout: reg r = (node n0 + kk*4 + r, channel 32 cg + 16 ct + j) ----
         for (int o = 0; o < nout; ++o) {
             const long ob = q.out[o];
@@ -168,38 +159,21 @@ struct SsGemm {
     int B, W, R, N, midoff, tpw;
 };
 
-// blockIdx.z = the window; a wave owns 16-row tiles of the window's B groups of R rows and NCT column tiles of 16.  GLU: the first NCT/2
-// tiles are P channels, the other half the Q channels of the same outputs (as sg_tapgemm_kernel).
+// blockIdx.z = the window, whose weight and bias row_gemm_stage (row_gemm_dev.h) stages; a wave owns 16-row tiles of the window's B groups of R
+// rows and NCT column tiles of 16.  Tiles are counted inside each (b, w) group, so none straddles two windows.
 template <int NCT>
-__global__ __launch_bounds__(SS_GEMM_THREADS) void ss_wingemm_kernel(SsGemm p) {
+__global__ __launch_bounds__(ROW_GEMM_THREADS) void ss_wingemm_kernel(SsGemm p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    constexpr int OCW = 16 * NCT;
+    constexpr int OCW = 16 * NCT, half = OCW / 2;
     const int P = p.ci + 4;
-    float* Wl = smem;                       // [OCW][P]
-    float* bl = Wl + OCW * P;               // [OCW]
+    const float* Wl = smem;                 // [OCW][P]
+    const float* bl = Wl + OCW * P;         // [OCW]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const int w = blockIdx.z;
     const bool glu = p.act == SS_ACT_GLU;
-    const int half = OCW / 2;
-    const int c0 = blockIdx.y * (glu ? half : OCW);
-    const float* Wg = p.Wt + (size_t)w * p.wstride;
-    const float* bg = p.bias != nullptr ? p.bias + (size_t)w * p.bstride : nullptr;
-    const int k4 = p.ci >> 2;
-    for (int f = tid; f < OCW * k4; f += SS_GEMM_THREADS) {
-        const int l = f / k4, c4 = f - l * k4;
-        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
-        const int wr = glu && l >= half ? p.co + ch : ch;
-        st4(Wl + l * P + 4 * c4, ch < p.co ? ld4(Wg + (size_t)wr * p.ci + 4 * c4) : f4zero());
-    }
-    if (tid < OCW) {
-        const int l = tid;
-        const int ch = glu ? (l < half ? c0 + l : c0 + l - half) : c0 + l;
-        const int wr = glu && l >= half ? p.co + ch : ch;
-        bl[l] = (bg != nullptr && ch < p.co) ? bg[wr] : 0.f;
-    }
-    __syncthreads();
+    const int c0 = row_gemm_stage<NCT>(smem, p.Wt + (size_t)w * p.wstride, p.bias != nullptr ? p.bias + (size_t)w * p.bstride : nullptr, p.ci, p.co, glu);
     const int tpg = (p.R + 15) / 16, ntiles = p.B * tpg, nq = p.ci >> 4;
-    const int t0 = (blockIdx.x * (SS_GEMM_THREADS / 64) + wave) * p.tpw, t1 = min(ntiles, t0 + p.tpw);
+    const int t0 = (blockIdx.x * (ROW_GEMM_THREADS / 64) + wave) * p.tpw, t1 = min(ntiles, t0 + p.tpw);
     for (int t = t0; t < t1; ++t) {
         const int b = t / tpg, ri0 = (t - b * tpg) * 16;
         const size_t gbase = ((size_t)b * p.W + w) * p.R;                   // first row of the (b, w) group
@@ -232,7 +206,7 @@ __global__ __launch_bounds__(SS_GEMM_THREADS) void ss_wingemm_kernel(SsGemm p) {
                     if (ri >= p.R) continue;
                     const size_t e = (gbase + ri) * p.co + ch;
                     const float pv = acc[ct][r] + bl[16 * ct + j];
-                    const float s = ss_sigmoid(acc[ct + NCT / 2][r] + bl[half + 16 * ct + j]);
+                    const float s = sigmoidf_(acc[ct + NCT / 2][r] + bl[half + 16 * ct + j]);
                     const float y = pv * s;
                     p.Y[e] = y;
                     if (p.S != nullptr) { p.S[e] = s; p.A[e] = pv; }
@@ -278,10 +252,7 @@ __global__ __launch_bounds__(256) void ss_gate_bwd_kernel(const float* __restric
             g.x += wh.x == opj ? d.x : 0.f; g.y += wh.y == opj ? d.y : 0.f; g.z += wh.z == opj ? d.z : 0.f; g.w += wh.w == opj ? d.w : 0.f;
         }
         const float4 s = ld4(S + 4 * i), a = ld4(A + 4 * i);
-        float* d = dPre + (row * 2 * co4 + c4) * 4;
-        st4(d, make_float4(g.x * s.x, g.y * s.y, g.z * s.z, g.w * s.w));
-        st4(d + 4 * co4, make_float4(g.x * a.x * (s.x * (1.f - s.x)), g.y * a.y * (s.y * (1.f - s.y)), g.z * a.z * (s.z * (1.f - s.z)),
-                                     g.w * a.w * (s.w * (1.f - s.w))));
+        glu_bwd_store(dPre + (row * 2 * co4 + c4) * 4, co4, g, s, a);
     }
 }
 
@@ -315,11 +286,23 @@ extern "C" int gptst_stsgcn_mix(const float* L, int Np, const float* In, float* 
     const long W = T - 2;
     const long units = mode == SS_F2E || mode == SS_E2F ? (long)B * T : mode == SS_E2E ? (long)B * W * 3 : (long)B * W;
     if (units > 0x7fffffffL) return GPTST_ESHAPE;
-    const size_t smem = (size_t)Np * SS_NM_P * sizeof(float);
+    const size_t smem = (size_t)Np * NODE_MIX_P * sizeof(float);
     SsMix p{L, Np, In, Out, c, mode, T, N};
     hipLaunchKernelGGL(ss_mix_kernel, dim3((unsigned)units, (Np / 16 + 3) / 4), dim3(256), smem, (hipStream_t)stream, p);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
+}
+
+// the launch plan of the grouped GEMM: 64 weight rows where they fit the 64 KB a launch gets by default, else 32; about 1024 workgroups over the W windows
+static RowGemmPlan ss_wingemm_plan(int B, int W, int R, int ci, int co, int act) {
+    const bool wide = ((size_t)64 * (ci + 4) + 64) * sizeof(float) <= 64 * 1024;
+    return row_gemm_plan((long)B * ((R + 15) / 16), co, act == SS_ACT_GLU, wide, W, 1024);
+}
+
+// (include/gptst_hip_testing.h) tiles per wave of the launch gptst_stsgcn_wingemm makes for this shape
+extern "C" int gptst_stsgcn_wingemm_tpw(int B, int W, int R, int ci, int co, int act) {
+    if (B <= 0 || W <= 0 || R <= 0 || ci <= 0 || co <= 0 || (act != SS_ACT_NONE && act != SS_ACT_GLU)) return GPTST_EARG;
+    return ss_wingemm_plan(B, W, R, ci, co, act).tpw;
 }
 
 extern "C" int gptst_stsgcn_wingemm(const float* X, int ci, const float* Wt, const float* bias, int shared, float* Y, int co, float* S, float* A,
@@ -328,20 +311,14 @@ extern "C" int gptst_stsgcn_wingemm(const float* X, int ci, const float* Wt, con
         || (act != SS_ACT_NONE && act != SS_ACT_GLU) || ((S != nullptr || best != nullptr) && act != SS_ACT_GLU) || (which != nullptr && !best)
         || opj < 0)
         return GPTST_EARG;
-    if (ci < 16 || ci % 16 || ci > 256 || co < 16 || co % 16 || W > 65535) return GPTST_ESHAPE;
-    const bool wide = ((size_t)64 * (ci + 4) + 64) * sizeof(float) <= 64 * 1024;
-    const int ocw = wide ? 64 : 32, per = act == SS_ACT_GLU ? ocw / 2 : ocw, cw = act == SS_ACT_GLU ? 2 * co : co;
-    const int colblocks = (co + per - 1) / per;
-    const long ntiles = (long)B * ((R + 15) / 16);
-    const int wpb = SS_GEMM_THREADS / 64;
-    long rowblocks = 1024 / ((long)colblocks * W); if (rowblocks < 1) rowblocks = 1;
-    long tpw = (ntiles + wpb * rowblocks - 1) / (wpb * rowblocks); if (tpw < 1) tpw = 1;
-    rowblocks = (ntiles + wpb * tpw - 1) / (wpb * tpw);
-    if (ntiles > 0x7fffffffL || colblocks > 65535) return GPTST_ESHAPE;
-    const size_t smem = ((size_t)ocw * (ci + 4) + ocw) * sizeof(float);
-    SsGemm p{X, ci, Wt, shared ? 0L : (long)cw * ci, bias, shared ? 0 : cw, Y, co, S, A, act, best, which, opj, B, W, R, N, R == N ? 0 : N, (int)tpw};
-    if (wide) hipLaunchKernelGGL(ss_wingemm_kernel<4>, dim3((unsigned)rowblocks, colblocks, W), dim3(SS_GEMM_THREADS), smem, (hipStream_t)stream, p);
-    else hipLaunchKernelGGL(ss_wingemm_kernel<2>, dim3((unsigned)rowblocks, colblocks, W), dim3(SS_GEMM_THREADS), smem, (hipStream_t)stream, p);
+    if (ci < 16 || ci % 16 || ci > 256 || co < 16 || co % 16 || W > 65535 || (long)B * ((R + 15) / 16) > 0x7fffffffL) return GPTST_ESHAPE;
+    const RowGemmPlan pl = ss_wingemm_plan(B, W, R, ci, co, act);
+    const int cw = act == SS_ACT_GLU ? 2 * co : co, colblocks = pl.colblocks, rowblocks = pl.rowblocks;
+    if (colblocks > 65535) return GPTST_ESHAPE;
+    const size_t smem = ((size_t)pl.ocw * (ci + 4) + pl.ocw) * sizeof(float);
+    SsGemm p{X, ci, Wt, shared ? 0L : (long)cw * ci, bias, shared ? 0 : cw, Y, co, S, A, act, best, which, opj, B, W, R, N, R == N ? 0 : N, pl.tpw};
+    if (pl.wide) hipLaunchKernelGGL(ss_wingemm_kernel<4>, dim3(rowblocks, colblocks, W), dim3(ROW_GEMM_THREADS), smem, (hipStream_t)stream, p);
+    else hipLaunchKernelGGL(ss_wingemm_kernel<2>, dim3(rowblocks, colblocks, W), dim3(ROW_GEMM_THREADS), smem, (hipStream_t)stream, p);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
 }
@@ -361,10 +338,7 @@ extern "C" int gptst_stsgcn_gate_bwd(const float* up, const float* dBest, const 
 // splits of one window's B R rows
 extern "C" int gptst_stsgcn_winwgrad_nsplit(int wrows, int cw, int ci, int W) {
     if (wrows <= 0 || cw <= 0 || ci <= 0 || W <= 0) return GPTST_EARG;
-    const int nchunks = (wrows + 63) / 64, tiles = ((cw + 63) / 64) * ((ci + 63) / 64) * W;
-    int ns = 1024 / tiles; if (ns < 1) ns = 1; if (ns > nchunks) ns = nchunks;
-    const int cps = (nchunks + ns - 1) / ns;
-    return (nchunks + cps - 1) / cps;
+    return wgrad_split_rule(((cw + 63) / 64) * ((ci + 63) / 64) * W, (wrows + 63) / 64);
 }
 
 extern "C" int gptst_stsgcn_winwgrad(const float* D, int cw, const float* X, int ci, float* part, float* bpart, int nsplit, int B, int W, int R,

@@ -1,4 +1,5 @@
-// Weight gradient of a tap GEMM, the body sg_wgrad_kernel (stgcn.hip) and mt_wgrad_kernel (mtgnn.hip) share:
+// Weight gradient of a tap GEMM, the body sg_wgrad_kernel (stgcn.hip), mt_wgrad_kernel (mtgnn.hip) and ss_winwgrad_kernel (stsgcn.hip) share
+// (the forward's counterpart, for the two of them whose weight rows sit whole in LDS, is row_gemm_dev.h):
 //   part[z][o][k] = sum over the rows of split z of D[row][o] Xs[row][k],   bpart[z][o] = column sums of D   (bpart may be NULL)
 // Xs[row][k] is X at the row's source row for the tap of column k.  Which row that is — and whether it exists, and a mask on it — is the
 // caller's: `src(row, rv)` returns this thread's float4 of Xs[row] (columns kcol .. kcol + 3 with kcol = blockIdx.x * 64 + 4 * (tid % 16)),
@@ -77,4 +78,13 @@ template <class Src>
 __device__ __forceinline__ void tap_wgrad_body(const float* D, int cw, int Ktot, float* part, float* bpart, int rows, int cps, int nchunks,
                                                const Src& src) {
     tap_wgrad_body(D, cw, Ktot, part, bpart, rows, cps, nchunks, src, TapWgAllRows());
+}
+
+// The split rule of the partial-writing gradients (the *_nsplit entries of stgcn.hip, stsgcn.hip and mtgnn.hip): `items` (64-row chunks, or
+// units) over as many splits as bring the launch's `tiles` output tiles to about 1024 workgroups, at most one split per item; then the
+// splits that the resulting items per split leave non-empty.
+static inline int wgrad_split_rule(int tiles, int items) {
+    int ns = 1024 / tiles; if (ns < 1) ns = 1; if (ns > items) ns = items;
+    const int per = (items + ns - 1) / ns;
+    return (items + per - 1) / per;
 }

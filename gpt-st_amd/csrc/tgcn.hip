@@ -25,7 +25,6 @@
 
 enum { TG_FWD_GATES = 0, TG_FWD_STATE = 1, TG_BWD_CAND = 2, TG_BWD_STATE = 3 };
 
-__device__ __forceinline__ float tg_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 
 struct TgStep {
     const float* L; int Np;                    // (Np, Np) zero-padded: L forward, L^T backward
@@ -139,7 +138,7 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
                 if (n >= p.N) continue;
                 const float v = acc[nt][r];
                 if (MODE == TG_FWD_GATES) {
-                    const float s = tg_sigmoid(v + p.g[(qrow + n) * 2 * Hp + col]);
+                    const float s = sigmoidf_(v + p.g[(qrow + n) * 2 * Hp + col]);
                     if (col < Hp) {                                                  // reset gate
                         const size_t i = (srow + n) * Hp + col;
                         if (p.r_out != nullptr) p.r_out[i] = s;

@@ -24,12 +24,14 @@ int gptst_mask_force_multi(int on);
 /* puts n hand-off expiries on record without poisoning anything (synchronises): what the optimiser's guard and the steppers' recovery see when a
  * bounded in-launch wait ran out (tests/test_gpu_step.py::test_lost_handoff_*). */
 int gptst_handoff_inject(int n);
-/* launch-plan queries: the 16-row tiles one wave works through in the launch gptst_stgcn_tapgemm / gptst_mtgnn_tapgemm makes for this shape
- * (Ktot = taps * ci; act and gated as in the launch).  Each is answered by the function its launch plans with, so a test that needs the
- * multi-tile path can assert that it is on it (tests/test_gpu_stgcn_hip.py, tests/test_gpu_mtgnn_hip.py).  The splits of the weight and graph
- * gradients follow from the *_nsplit queries of gptst_hip.h: cps = ceil(ceil(rows / 64) / nsplit), ups = ceil(units / nsplit). */
+/* launch-plan queries: the 16-row tiles one wave works through in the launch gptst_stgcn_tapgemm / gptst_mtgnn_tapgemm / gptst_stsgcn_wingemm
+ * makes for this shape (Ktot = taps * ci; act and gated as in the launch; R = N or 3 N rows per (b, w) group).  Each is answered by the function
+ * its launch plans with, so a test that needs the multi-tile path can assert that it is on it (tests/test_gpu_stgcn_hip.py,
+ * tests/test_gpu_mtgnn_hip.py, tests/test_gpu_stsgcn_hip.py).  The splits of the weight and graph gradients follow from the *_nsplit queries of
+ * gptst_hip.h: cps = ceil(ceil(rows / 64) / nsplit), ups = ceil(units / nsplit). */
 int gptst_stgcn_tapgemm_tpw(int rows, int co, int Ktot, int act);
 int gptst_mtgnn_tapgemm_tpw(long rows, int co, int gated);
+int gptst_stsgcn_wingemm_tpw(int B, int W, int R, int ci, int co, int act);
 /* bytes of dynamic LDS of the launch gptst_astgcn_attmix makes for Np padded nodes and ks polynomials, answered by the function the launch sizes
  * with; GPTST_EARG / GPTST_ESHAPE for the (Np, ks) the launch refuses (tests/test_gpu_astgcn_hip.py) */
 int gptst_astgcn_attmix_lds(int Np, int ks);

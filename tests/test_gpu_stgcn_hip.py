@@ -115,7 +115,7 @@ def test_wgrad_three_chunks_per_split_and_a_short_last_split(parity):
 
 # ---- 2. graph convolution ----------------------------------------------------------------------------------------------------------------
 def _nodemix_lds(N):
-    """bytes of dynamic LDS of the node-mix launch: 36 floats for each of the 16 ceil(N / 16) padded nodes (SG_NM_P of csrc/stgcn.hip)"""
+    """bytes of dynamic LDS of the node-mix launch: 36 floats for each of the 16 ceil(N / 16) padded nodes (NODE_MIX_P of csrc/node_mix_dev.h)"""
     return 16 * ((N + 15) // 16) * 36 * 4
 
 

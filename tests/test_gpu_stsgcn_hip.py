@@ -103,11 +103,15 @@ def _glu(pre, co):
 WINGEMM = [(3, 3, 37, 32, 64),           # ci != co; 3N = 111 and N = 37 are no multiples of 16: tiles are counted inside a (b, w) group
            (2, 2, 20, 128, 128),         # the widest GLU; its mirrored form has 256 input columns: the 32-row weight block
            (128, 10, 20, 16, 64)]        # 512 row tiles per window over 51 workgroups of 8 waves: a wave's loop over its tiles runs twice
+# tiles per wave of each case's GLU launch on expanded rows, by hand: ceil(3 N / 16) B row tiles per window, ceil(co / 32) column blocks,
+# 1024 // (column blocks * W) row blocks of 8 waves.  The third: 512 tiles, 2 column blocks, 51 row blocks: ceil(512 / 408) = 2
+WINGEMM_TPW = {WINGEMM[0]: 1, WINGEMM[1]: 1, WINGEMM[2]: 2}
 
 
 @pytest.mark.parametrize("B,W,N,ci,co", WINGEMM)
 def test_wingemm_per_window_weights(B, W, N, ci, co, parity):
     """expanded and middle rows, GLU with the kept S and A, the ``sharing`` form, and the mirrored form without activation"""
+    assert _C.lib().value("gptst_stsgcn_wingemm_tpw", B, W, 3 * N, ci, co, ops.ACT_GLU) == WINGEMM_TPW[(B, W, N, ci, co)]
     g = torch.Generator().manual_seed(ci + co + N)
     Wt = torch.randn(W, 2 * co, ci, generator=g, dtype=torch.float64) / ci ** 0.5
     bs = 0.3 * torch.randn(W, 2 * co, generator=g, dtype=torch.float64)

@@ -18,7 +18,7 @@ import torch  # noqa: E402
 from gptst_amd import graph, ops  # noqa: E402
 from gptst_amd.config import predictor_args  # noqa: E402
 from gptst_amd.enhance import xavier_downstream_  # noqa: E402
-from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, TGCN  # noqa: E402
+from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, STSGCN, TGCN  # noqa: E402
 
 DEV = "cuda:0"
 T, C = 12, 64
@@ -49,6 +49,18 @@ def astgcn(N):
         for blk in m.BlockList:
             for p in (blk.TAt.U1, blk.TAt.U3, blk.SAt.W1, blk.SAt.W3):
                 p.copy_(0.25 * (p - 0.5))
+    return m
+
+
+def stsgcn(N):                                    # the conf's four layers of [64, 64, 64], GLU, a weight per window
+    ap = predictor_args("PEMS08", "STSGCN")
+    a = graph.synthetic_adjacency(N, 2)
+    ap.num_nodes, ap.A = N, a / a.sum(1, keepdims=True)       # rows normalised: a raw adjacency grows the activations layer by layer
+    m = STSGCN(ap, DEV, C, 1, backend="hip")
+    with torch.no_grad():                         # non-zero position embeddings, as after training: at zero they hide an omitted add
+        for k, p in m.named_parameters():
+            if k.endswith("_emb"):
+                p.normal_(0, 0.3)
     return m
 
 
@@ -85,7 +97,7 @@ def run(make, B, N):
 
 
 CONFIGS = {}
-for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn)):
+for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn)):
     CONFIGS[_name + "_b2_n37"] = lambda make=_make: run(make, 2, 37)            # a padded node tile, several row tiles
     CONFIGS[_name + "_b1_n170"] = lambda make=_make: run(make, 1, 170)
 
