@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -46,7 +46,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -113,16 +113,38 @@ def main_shard(args, dev):
         dist.destroy_process_group()
 
 
+def fusion_matrix(args, data_root, A, loaders, scaler):
+    """STFGNN's (4N, 4N) spatial-temporal fusion graph (reference model/STFGNN/args.py:192-210): ``<data_root>/STFGNN/<ds>/<ds>_adj_mx.npy`` when
+    that file exists; otherwise built from the adjacency and the DTW graph of the loaded series (graph.dtw_graph, on the series' device), and
+    cached there as the reference does.  The series at hand is the training split, z-scored: the head of the data, longer than the 60 % of
+    its days the DTW graph reads; it is put back to real values first, though the DTW normalises every day's row anyway."""
+    from gptst_amd import graph
+    path = os.path.join(data_root, "STFGNN", args.dataset, args.dataset + "_adj_mx.npy")
+    if os.path.exists(path):
+        return torch.tensor(np.load(path), dtype=torch.float32)
+    series = loaders[0].series[:, :, 0] * float(scaler.std) + float(scaler.mean)
+    whole = sum(ld.series.shape[0] for ld in loaders if ld is not None)
+    print("gpt-st_amd: %s not found -> DTW graph of the %s training series %s" % (path, args.dataset, tuple(series.shape)), flush=True)
+    dtw = graph.dtw_graph(series, args.dataset, total_steps=whole)
+    adj = graph.stfgnn_fusion_graph(A, dtw)
+    try:
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        np.save(path, adj.double().numpy())
+    except OSError as e:
+        print("gpt-st_amd: the fusion matrix is not cached (%s)" % e)
+    return adj
+
+
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39 and model/STSGCN/args.py:6-51 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51 and model/STFGNN/args.py:154-211 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, STSGCN, TGCN
-    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN"):
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN and -model STSGCN (SURVEY.md §8f rank 4)")
+    from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STSGCN, TGCN
+    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN"):
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN and -model STFGNN (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -149,6 +171,9 @@ def main_eval(args, dev):
     elif str(args.model) == "STSGCN":                                            # model/Model.py:58-60, STSGCN/args.py:41-50: the raw adjacency
         ap = SimpleNamespace(**vars(pargs), A=np.asarray(A, dtype=np.float32))
         predictor = STSGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stsgcn_backend))
+    elif str(args.model) == "STFGNN":                                            # model/Model.py, STFGNN/args.py:192-210: the fusion matrix
+        ap = SimpleNamespace(**vars(pargs), adj=fusion_matrix(args, data_root, A, (train, val, test), scaler))
+        predictor = STFGNN(ap, dev, args.hidden_dim, backend=str(args.stfgnn_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

@@ -3,6 +3,8 @@
 //   frames     (b, t, n)       (B T N rows)      the layer's input, and the gradient that leaves it
 //   expanded   (b, w, k, n)    (B W 3 N rows)    block (w, k), k = 0..2, stands for frame w + k of window w
 //   middle     (b, w, n)       (B W N rows)      the last operation's output and the running max: already the next layer's frames
+// The STFGNN predictor (stfgnn.hip) has windows of four frames: its expanded rows are groups of R = 4N, which wingemm, gate_bwd and winwgrad
+// take as they take 3N — the middle block is rows N .. 2N of a group either way.
 //
 //   mix        the localized adjacency of a window without its (3N, 3N) matrix: with A^ = the adjacency with a unit diagonal,
 //                  mix(S)_k = A^ S_k + [k >= 1] S_{k-1} + [k <= 1] S_{k+1}
@@ -307,7 +309,7 @@ extern "C" int gptst_stsgcn_wingemm_tpw(int B, int W, int R, int ci, int co, int
 
 extern "C" int gptst_stsgcn_wingemm(const float* X, int ci, const float* Wt, const float* bias, int shared, float* Y, int co, float* S, float* A,
                                     int act, float* best, int* which, int opj, int B, int W, int R, int N, void* stream) {
-    if (!X || !Wt || !Y || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N) || (S != nullptr) != (A != nullptr)
+    if (!X || !Wt || !Y || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N && R != 4 * N) || (S != nullptr) != (A != nullptr)
         || (act != SS_ACT_NONE && act != SS_ACT_GLU) || ((S != nullptr || best != nullptr) && act != SS_ACT_GLU) || (which != nullptr && !best)
         || opj < 0)
         return GPTST_EARG;
@@ -325,7 +327,7 @@ extern "C" int gptst_stsgcn_wingemm(const float* X, int ci, const float* Wt, con
 
 extern "C" int gptst_stsgcn_gate_bwd(const float* up, const float* dBest, const int* which, int opj, const float* S, const float* A, float* dPre,
                                      int B, int W, int R, int N, int co, void* stream) {
-    if (!dBest || !which || !S || !A || !dPre || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N) || opj < 0) return GPTST_EARG;
+    if (!dBest || !which || !S || !A || !dPre || B <= 0 || W <= 0 || N <= 0 || (R != N && R != 3 * N && R != 4 * N) || opj < 0) return GPTST_EARG;
     if (co < 4 || co % 4) return GPTST_ESHAPE;
     const long n4 = (long)B * W * R * co / 4;
     long blocks = (n4 + 255) / 256; if (blocks > 4096) blocks = 4096;

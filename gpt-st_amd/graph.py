@@ -93,3 +93,132 @@ def normalized_adjacency(A):
 def tgcn_graph(A):
     """The dense fp32 (N, N) graph of ``predictors.TGCN`` (the reference builds it inside the cell and casts it with ``.float()``, TGCN.py:37,116)."""
     return torch.tensor(normalized_adjacency(A), dtype=torch.float32)
+
+
+# ---- STFGNN: the spatial-temporal fusion graph (reference model/STFGNN/args.py:10-151) ---------------------------------------------------
+def stfgnn_fusion_graph(A, A_dtw, steps=4):
+    """The (steps N, steps N) fp32 fusion matrix of ``construct_adj_fusion`` (args.py:101-151), from the spatial adjacency A and the temporal
+    (DTW) graph A_dtw.  With "1" the identity block and X^ = X with a unit diagonal (every diagonal entry is forced to 1 last):
+
+        [ D^ 1  1  D ]
+        [ 1  S^ 1  1 ]
+        [ 1  1  S^ 1 ]
+        [ D  1  1  D^]
+
+    The reference writes the blocks by index 3N..4N whatever ``steps`` is; every conf has 4, and nothing else is built here."""
+    if steps != 4:
+        raise ValueError("the STFGNN fusion graph is defined for 4 steps (reference args.py:139-145 index block 3), got %r" % (steps,))
+    A, D = np.asarray(A, dtype=np.float64), np.asarray(A_dtw, dtype=np.float64)
+    n = len(A)
+    adj = np.zeros((n * steps, n * steps))
+    eye = np.identity(n)
+    blk = lambda i, j: (slice(i * n, (i + 1) * n), slice(j * n, (j + 1) * n))      # noqa: E731
+    for i in range(steps):
+        adj[blk(i, i)] = A if i in (1, 2) else D
+    for k in range(steps - 1):                                                       # adjacent steps: the node's own row, both ways
+        np.fill_diagonal(adj[blk(k, k + 1)], 1.0)
+        np.fill_diagonal(adj[blk(k + 1, k)], 1.0)
+    adj[blk(3, 0)] = D
+    adj[blk(0, 3)] = D
+    for i, j in ((2, 0), (0, 2), (1, 3), (3, 1)):
+        adj[blk(i, j)] = adj[blk(0, 1)]
+    assert np.array_equal(adj[blk(0, 1)], eye)
+    np.fill_diagonal(adj, 1.0)
+    return torch.tensor(adj, dtype=torch.float32)
+
+
+def stfgnn_blocks(adj):
+    """(S^, D) — both (N, N) fp32 — when ``adj`` (4N, 4N) has exactly the form ``stfgnn_fusion_graph`` gives for a D with a unit diagonal
+    (``dtw_graph`` always gives one): the ten identity blocks exact, block(0,0) = block(3,3) = block(0,3) = block(3,0) = D, block(1,1) =
+    block(2,2) = S^.  None for any other matrix: the HIP backend of ``predictors.STFGNN`` multiplies by the two blocks alone and serves no other."""
+    adj = torch.as_tensor(adj)
+    if adj.dim() != 2 or adj.shape[0] != adj.shape[1] or adj.shape[0] % 4 or adj.shape[0] == 0:
+        return None
+    n = adj.shape[0] // 4
+    b = adj.reshape(4, n, 4, n).permute(0, 2, 1, 3)                                  # b[i, j] = block (i, j)
+    eye = torch.eye(n, dtype=adj.dtype, device=adj.device)
+    for i, j in ((0, 1), (0, 2), (1, 0), (1, 2), (1, 3), (2, 0), (2, 1), (2, 3), (3, 1), (3, 2)):
+        if not torch.equal(b[i, j], eye):
+            return None
+    D, S = b[0, 3], b[1, 1]
+    if not (torch.equal(b[3, 0], D) and torch.equal(b[0, 0], D) and torch.equal(b[3, 3], D) and torch.equal(b[2, 2], S)):
+        return None
+    return S.float().contiguous(), D.float().contiguous()
+
+
+def _dtw_series(series, dataset, slots, day_slots, train_share, total_steps=None):
+    """(days, slots, N) float64: the first channel, the first ``train_share`` of the days (construct_dtw + gen_data, args.py:10-24,59-67).
+    ``total_steps``: the length of the whole series where ``series`` is only its head (the training split): the day count comes from it, and a
+    last part-day of the head is dropped"""
+    data = torch.as_tensor(series)
+    if data.dim() == 3:
+        data = data[:, :, 0]
+    data = data.double()
+    if day_slots is None:
+        day_slots = 96 if dataset == "SZ_TAXI" else 288                              # the reference counts days of 288 slots for the NYC sets too
+    if slots is None:
+        slots = 96 if dataset == "SZ_TAXI" else 48 if dataset in ("NYC_TAXI", "NYC_BIKE") else 288
+    tr_day = int((data.shape[0] if total_steps is None else total_steps) / day_slots * train_share)
+    n = data.shape[1]
+    full = data.shape[0] // slots * slots
+    if full != data.shape[0] and total_steps is None:
+        raise ValueError("the series has %d steps, no whole number of days of %d slots" % (data.shape[0], slots))
+    if full < tr_day * slots:
+        raise ValueError("the series has %d whole days, the DTW graph reads %d" % (full // slots, tr_day))
+    return data[:full].reshape(-1, slots, n)[:tr_day]
+
+
+def dtw_distances(x, band=12, chunk=2048):
+    """x (days, slots, N) -> (N, N) float64, upper triangle: the banded DTW distance of ``compute_dtw`` (args.py:26-57, order 1) between the
+    series of nodes i < j.  Every day's row is normalised on its own; the local cost of slots (p of j, q of i) is the sum over the days of
+    |a[day, q] - b[day, p]|; the recurrence runs over the band |p - q| <= band, whose edges drop the neighbour outside it.  Vectorised over the
+    node pairs (the reference loops over them in Python), ``chunk`` pairs at a time on x's device; the band's cells of one row depend on their
+    left neighbour, so the recurrence itself is a loop of slots * (2 band + 1) steps."""
+    x = x.double()
+    days, T0, n = x.shape
+    z = (x - x.mean(1, keepdim=True)) / x.std(1, unbiased=False, keepdim=True)
+    z = z.permute(2, 0, 1).contiguous()                                              # (N, days, slots)
+    iu, ju = torch.triu_indices(n, n, 1, device=x.device)
+    out = torch.zeros(n, n, dtype=torch.float64, device=x.device)
+    inf = float("inf")
+    for c0 in range(0, iu.numel(), chunk):
+        a, b = z[iu[c0:c0 + chunk]], z[ju[c0:c0 + chunk]]                            # a: node i (columns q), b: node j (rows p)
+        P = a.shape[0]
+        prev = None
+        for p in range(T0):
+            lo, hi = max(0, p - band), min(T0, p + band + 1)
+            cost = (a[:, :, lo:hi] - b[:, :, p:p + 1]).abs().sum(1)                  # (P, hi - lo)
+            row = torch.full((P, T0), inf, dtype=torch.float64, device=x.device)     # cells outside the band are never the minimum
+            for q in range(lo, hi):
+                if p == 0 and q == 0:
+                    best = torch.zeros(P, dtype=torch.float64, device=x.device)
+                elif p == 0:
+                    best = row[:, q - 1]
+                elif q == 0:
+                    best = prev[:, 0]
+                else:
+                    best = torch.minimum(torch.minimum(prev[:, q - 1], prev[:, q]), row[:, q - 1])
+                row[:, q] = cost[:, q - lo] + best
+            prev = row
+        out[iu[c0:c0 + chunk], ju[c0:c0 + chunk]] = prev[:, T0 - 1]
+    return out
+
+
+def dtw_graph(series, dataset="PEMS08", band=12, adj_percent=0.01, train_share=0.6, slots=None, day_slots=None, chunk=2048,
+              return_distances=False, total_steps=None):
+    """The 0/1 temporal graph of ``construct_dtw`` (args.py:59-99) as (N, N) float64 numpy: the banded DTW distance between every two nodes'
+    training series (``dtw_distances``), for each node its ``int(N * adj_percent)`` nearest (itself, at distance 0, among them), made
+    symmetric by taking an edge that either side has, and a unit diagonal.  ``series`` (L, N[, F]): the first channel is used, on the
+    series' device.  Quirks kept: the day count is L / 288 for every dataset but SZ_TAXI, also where a day has 48 slots (so the NYC sets use a
+    tenth of their days); ``slots`` / ``day_slots`` override the two for series of another shape.  ``total_steps``: see ``_dtw_series``."""
+    x = _dtw_series(series, dataset, slots, day_slots, train_share, total_steps)
+    d = dtw_distances(x, band, chunk)
+    dtw = (d + d.t()).cpu().numpy()
+    n = dtw.shape[0]
+    w = np.zeros((n, n))
+    top = int(n * adj_percent)
+    for i in range(n):
+        w[i, dtw[i].argsort()[:top]] = 1
+    w = np.maximum(w, w.T)
+    np.fill_diagonal(w, 1.0)
+    return (w, d.cpu().numpy()) if return_distances else w

@@ -1379,13 +1379,14 @@ def stsgcn_mix(Lp, In, mode, B, T, N):
 
 def stsgcn_wingemm(X, Wt, bias, act, B, W, R, N, keep=False, best=None, which=None, opj=0):
     """Y (B W R, co) = act(X Wt[w]^T + bias[w]) for the rows of window w; Wt (W, cw, ci) — or (1, cw, ci): one weight for all windows — and bias
-    (W | 1, cw) or None; act ACT_GLU (cw = 2 co) or ACT_NONE.  keep (GLU): -> (Y, S, A).  best (B W N, co) / which (int32): the running max on
+    (W | 1, cw) or None; act ACT_GLU (cw = 2 co) or ACT_NONE.  R = N (middle rows), 3 N (STSGCN's expanded rows) or 4 N (STFGNN's); the middle
+    block is rows N .. 2N of a group.  keep (GLU): -> (Y, S, A).  best (B W N, co) / which (int32): the running max on
     the middle block and the operation that holds it, updated in place (opj = 0 writes, later operations replace where strictly greater)."""
     _chk(X, Wt, bias, best)
     ci = X.shape[1]
     cw = Wt.shape[1]
     co = cw // 2 if act == ACT_GLU else cw
-    assert X.shape[0] == B * W * R and Wt.shape[2] == ci and Wt.shape[0] in (1, W) and (bias is None or bias.shape == Wt.shape[:2])
+    assert X.shape[0] == B * W * R and R in (N, 3 * N, 4 * N) and Wt.shape[2] == ci and Wt.shape[0] in (1, W) and (bias is None or bias.shape == Wt.shape[:2])
     assert which is None or (which.dtype == torch.int32 and which.is_contiguous() and which.shape == best.shape)
     assert best is None or best.shape == (B * W * N, co)
     Y = torch.empty(B * W * R, co, device=X.device, dtype=torch.float32)
@@ -1399,7 +1400,7 @@ def stsgcn_gate_bwd(up, dBest, which, opj, S, A, B, W, R, N):
     """dPre (B W R, 2 co) of operation opj: g = up (or 0) + dBest [which == opj] on the middle block, through the GLU derivative"""
     _chk(up, dBest, S, A)
     co = S.shape[1]
-    assert S.shape[0] == B * W * R and dBest.shape == (B * W * N, co) and which.dtype == torch.int32 and which.shape == dBest.shape
+    assert S.shape[0] == B * W * R and R in (N, 3 * N, 4 * N) and dBest.shape == (B * W * N, co) and which.dtype == torch.int32 and which.shape == dBest.shape
     dPre = torch.empty(B * W * R, 2 * co, device=S.device, dtype=torch.float32)
     _call("gptst_stsgcn_gate_bwd", _p(up), _p(dBest), _p(which), opj, _p(S), _p(A), _p(dPre), B, W, R, N, co, tag="co%d R%d W%d" % (co, R // N, W),
           nbytes=_nb(up, dBest, S, A, dPre))
@@ -1416,3 +1417,21 @@ def stsgcn_winwgrad(D, X, B, W, R):
     bpart = torch.empty(W, ns, cw, device=D.device, dtype=torch.float32)
     _call("gptst_stsgcn_winwgrad", _p(D), cw, _p(X), ci, _p(part), _p(bpart), ns, B, W, R, tag="cw%d ci%d R%d W%d" % (cw, ci, R, W), nbytes=_nb(D, X, part))
     return part.sum(1), bpart.sum(1)
+
+
+# ---- the downstream STFGNN predictor (csrc/stfgnn.hip) ----------------------------------------------------------------------------------
+# row layouts of a layer over T frames, W = T - 3 windows: frames (B T N), expanded (B W 4 N): block (w, k) stands for frame w + k, middle (B W N).
+# The modes are stsgcn_mix's (MIX_F2E ... MIX_E2F); the grouped GEMM, its gate backward and weight gradient are stsgcn_wingemm / stsgcn_gate_bwd /
+# stsgcn_winwgrad with R = 4 N.
+def stfgnn_mix(Sp, Dp, In, mode, B, T, N):
+    """the product with the (4N, 4N) fusion graph as blocks: mix(X)_0 = mix(X)_3 = D (X_0 + X_3) + X_1 + X_2, mix(X)_k = S X_k + the other three
+    for k = 1, 2.  Sp, Dp (Np, Np) = S^ and D zero-padded (their transposes for the adjoints).  mode: MIX_F2E frames -> expanded, MIX_E2E,
+    MIX_E2M (block 1 only), MIX_M2E (adjoint of E2M), MIX_E2F (adjoint of F2E)."""
+    _chk(Sp, Dp, In)
+    W, c = T - 3, In.shape[1]
+    rows = {"f": B * T * N, "e": B * W * 4 * N, "m": B * W * N}
+    src, dst = _MIX_ROWS[mode]
+    assert In.shape[0] == rows[src] and Sp.dim() == 2 and Sp.shape == Dp.shape, (In.shape, mode, B, T, N)
+    Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
+    _call("gptst_stfgnn_mix", _p(Sp), _p(Dp), Sp.shape[0], _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
+    return Out

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 22  /* 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 23  /* 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -534,9 +534,10 @@ int gptst_astgcn_rowln_bwd_param(const float* dY, const float* X, const float* m
  * mix: mix(S)_k = L S_k + [k >= 1] S_{k-1} + [k <= 1] S_{k+1}, the (3N, 3N) localized adjacency never formed.  mode 0 frames -> expanded
  *   (block (w, k) reads frame w + k), 1 expanded -> expanded, 2 expanded -> middle (k = 1 only), 3 middle -> expanded (the adjoint of 2: block 1 =
  *   L In, blocks 0 and 2 = In), 4 expanded -> frames (the adjoint of 0: frame t gathers the blocks with w + k = t, k ascending).  In != Out.
- * wingemm: Y[(b, w, r)] = act(X[(b, w, r)] Wt[w]^T + bias[w]) over B W groups of R rows, R = 3N (expanded) or N (middle); Wt (W, cw, ci), bias
+ * wingemm: Y[(b, w, r)] = act(X[(b, w, r)] Wt[w]^T + bias[w]) over B W groups of R rows, R = 3N (expanded; 4N: the four-frame windows of STFGNN,
+ *   below) or N (middle); Wt (W, cw, ci), bias
  *   (W, cw), cw = 2 co (act 3, GLU) or co (act 0); shared != 0: ONE weight (cw, ci) for all windows.  GLU: S = sigma(Q) and A = P + bias when not
- *   NULL.  best (B W N, co) not NULL (GLU): the running max on the middle block (rows N .. 2N of a group of 3N; all of a group of N) —
+ *   NULL.  best (B W N, co) not NULL (GLU): the running max on the middle block (rows N .. 2N of a group of 3N or 4N; all of a group of N) —
  *   operation opj = 0 writes, a later one replaces where strictly greater — and which (int32, same shape; may be NULL) the operation that holds it.
  * gate_bwd: dPre (rows, 2 co) = [g S | g A S (1 - S)] with g = up (rows, co; NULL: 0) + dBest [which == opj] on the middle block.
  * winwgrad: part (W, nsplit, cw, ci) = row-split partials of D[window]^T X[window], bpart (W, nsplit, cw) (or NULL) of D's column sums, in a
@@ -549,6 +550,17 @@ int gptst_stsgcn_gate_bwd(const float* up, const float* dBest, const int* which,
 int gptst_stsgcn_winwgrad_nsplit(int wrows, int cw, int ci, int W);
 int gptst_stsgcn_winwgrad(const float* D, int cw, const float* X, int ci, float* part, float* bpart, int nsplit, int B, int W, int R,
                           void* stream);
+/* ---- the downstream STFGNN predictor (stfgnn.hip; reference model/STFGNN/STFGNN.py, gpt-st_amd/predictors/stfgnn_hip.py) --------------------
+ * A layer over T frames has W = T - 3 windows of four frames.  Row layouts: frames (b, t, n); expanded (b, w, k, n), k = 0..3, block (w, k)
+ * standing for frame w + k; middle (b, w, n).  S, D (Np, Np): S^ (the spatial adjacency with a unit diagonal) and the temporal graph D (which
+ * has one) — or their transposes for the adjoints — zero-padded to Np = 16 ceil(N / 16) <= 448 (GPTST_ESHAPE beyond, nothing written).
+ * mix: the product with the (4N, 4N) fusion graph, never formed: mix(X)_0 = mix(X)_3 = D (X_0 + X_3) + X_1 + X_2, mix(X)_k = S X_k + the
+ *   other three blocks for k = 1, 2.  mode 0 frames -> expanded, 1 expanded -> expanded (its own adjoint with the transposed graphs),
+ *   2 expanded -> middle (k = 1 only; D unused), 3 middle -> expanded (the adjoint of 2: block 1 = S In, blocks 0, 2, 3 = In), 4 expanded ->
+ *   frames (the adjoint of 0: the two products of a frame in one workgroup, the gather order fixed: csrc/stfgnn.hip).  In != Out.
+ * The GEMM grouped by window, its gate backward and weight gradient are gptst_stsgcn_wingemm / _gate_bwd / _winwgrad with R = 4N; the gated
+ * temporal branch is gptst_mtgnn_tapgemm (gated, offsets 0 and 3) with gptst_mtgnn_gate_bwd / gptst_mtgnn_wgrad. */
+int gptst_stfgnn_mix(const float* S, const float* D, int Np, const float* In, float* Out, int c, int mode, int B, int T, int N, void* stream);
 
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column

@@ -18,7 +18,7 @@ import torch  # noqa: E402
 from gptst_amd import graph, ops  # noqa: E402
 from gptst_amd.config import predictor_args  # noqa: E402
 from gptst_amd.enhance import xavier_downstream_  # noqa: E402
-from gptst_amd.predictors import ASTGCN, MTGNN, STGCN, STSGCN, TGCN  # noqa: E402
+from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STSGCN, TGCN  # noqa: E402
 
 DEV = "cuda:0"
 T, C = 12, 64
@@ -64,6 +64,21 @@ def stsgcn(N):                                    # the conf's four layers of [6
     return m
 
 
+def stfgnn(N):                                    # the conf's three layers of [64, 64, 64], GLU, a weight per window
+    ap = predictor_args("PEMS08", "STFGNN")
+    s, d = graph.synthetic_adjacency(N, 2), graph.synthetic_adjacency(N, 5)
+    d = ((d + d.T) > 0).astype("float32")
+    s, d = s / s.sum(1, keepdims=True), d / d.sum(1, keepdims=True)       # rows normalised, as for STSGCN; the temporal graph symmetric
+    d[range(N), range(N)] = 1.0                                           # with a unit diagonal, as graph.dtw_graph gives it
+    ap.num_nodes, ap.adj = N, graph.stfgnn_fusion_graph(s, d)
+    m = STFGNN(ap, DEV, C, backend="hip")
+    with torch.no_grad():                         # position embeddings of the size they have after training
+        for k, p in m.named_parameters():
+            if k.endswith("_embedding"):
+                p.normal_(0, 0.3)
+    return m
+
+
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
@@ -97,7 +112,7 @@ def run(make, B, N):
 
 
 CONFIGS = {}
-for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn)):
+for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn), ("stfgnn", stfgnn)):
     CONFIGS[_name + "_b2_n37"] = lambda make=_make: run(make, 2, 37)            # a padded node tile, several row tiles
     CONFIGS[_name + "_b1_n170"] = lambda make=_make: run(make, 1, 170)
 
