@@ -14,6 +14,7 @@
 // become one 16.7 MB write; hypertem_bwd_wgrad + rowouter_part (30 + 11 us, ~130 MB) become one pass over dPre.
 // Serves base = 1, C = 64 or 128, T = 12 (GPTST_ESHAPE otherwise: lin_in + the generic layer).
 #include "common.h"
+#include "poolgen_dev.h"
 
 #define EI_T 12
 GPTST_STAMP_TABLES(encin)
@@ -92,19 +93,20 @@ __global__ __launch_bounds__(256) void encin_fwd_kernel(const float* __restrict_
     GPTST_STAMP(3); GPTST_WG_END();
 }
 
+// the backward of one (b,t) = `bt` on 256 threads; smem: encin_bwd_smem(C, N) bytes.  A __device__ body so that the launch which carries
+// reduction jobs next to it (encin_bwd_jobs_kernel below) runs the SAME code as the stand-alone kernel.
 template <int C>
-__global__ __launch_bounds__(256) void encin_bwd_kernel(const float* __restrict__ dPre, const float* __restrict__ src, int lda,
-                                                        const float* __restrict__ mask, float fill, const float* __restrict__ w,
-                                                        const float* __restrict__ bi, const float* __restrict__ Wbt, const float* __restrict__ ab,
-                                                        const float* __restrict__ wv, float* __restrict__ dWb, float* __restrict__ dG,
-                                                        float* __restrict__ dinp, int N, int B) {
+__device__ __forceinline__ void encin_bwd_body(const float* __restrict__ dPre, const float* __restrict__ src, int lda,
+                                               const float* __restrict__ mask, float fill, const float* __restrict__ w,
+                                               const float* __restrict__ bi, const float* __restrict__ Wbt, const float* __restrict__ ab,
+                                               const float* __restrict__ wv, float* __restrict__ dWb, float* __restrict__ dG,
+                                               float* __restrict__ dinp, int N, int bt, float* __restrict__ smem) {
     constexpr int LPR = C / 4, RPP = 256 / LPR, U = 4;
-    extern __shared__ __attribute__((aligned(16))) float smem[];
     float* red = smem;                     // [RPP][4][C]  per-slot partials of A, Bv, Cv, Mv
     float* vec = red + RPP * 4 * C;        // [6][C]       A | Bv | Cv | Mv | w W_bt | bi W_bt
     float* as_ = vec + 6 * C;              // [N] dPre . (w W_bt),  [N] dPre . (bi W_bt)
     float* cs_ = as_ + N;
-    const int bt = blockIdx.x, b = bt / EI_T, t = bt % EI_T, tid = threadIdx.x;
+    const int b = bt / EI_T, t = bt % EI_T, tid = threadIdx.x;
     GPTST_WG_BEGIN(); GPTST_STAMP(0);
     if (tid < 2 * C) vec[4 * C + tid] = wv[(size_t)bt * 2 * C + tid];
     __syncthreads();
@@ -186,6 +188,35 @@ __global__ __launch_bounds__(256) void encin_bwd_kernel(const float* __restrict_
     GPTST_STAMP(4); GPTST_WG_END();
 }
 
+static size_t encin_bwd_smem(int C, int N) { return ((size_t)(256 / (C / 4)) * 4 * C + 6 * C + 2 * (size_t)N) * sizeof(float); }
+
+struct EncinBwdArgs {
+    const float *dPre, *src, *mask, *w, *bi, *Wbt, *ab, *wv;
+    float *dWb, *dG, *dinp;
+    int lda, N;
+    float fill;
+};
+
+template <int C>
+__global__ __launch_bounds__(256) void encin_bwd_kernel(EncinBwdArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    encin_bwd_body<C>(a.dPre, a.src, a.lda, a.mask, a.fill, a.w, a.bi, a.Wbt, a.ab, a.wv, a.dWb, a.dG, a.dinp, a.N, blockIdx.x, smem);
+}
+
+// TAIL ROLES, level 1 of the end of the backward: the grid is [B*T backward workgroups | job blocks].  Nothing is on the data-gradient chain behind this launch,
+// and its 384 workgroups of four waves leave most of the chip's bandwidth idle (29 MB in 19 us), so the weight-gradient reductions whose inputs exist already
+// (gptst_pool_jobs kinds 1 / 2: written by EARLIER launches) run here as further workgroups instead of in a launch of their own behind it.  The backward
+// workgroups come first in block order: the latency-bound role is on the chip at once.  No workgroup waits for another.  The job role keeps the job
+// kernel's occupancy (PJ_OCC); dynamic LDS = max(encin_bwd_smem, the jobs' fold).
+template <int C>
+__global__ __launch_bounds__(256, PJ_OCC) void encin_bwd_jobs_kernel(EncinBwdArgs a, int nhost, PJCarry jc) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    if ((int)blockIdx.x < nhost)
+        encin_bwd_body<C>(a.dPre, a.src, a.lda, a.mask, a.fill, a.w, a.bi, a.Wbt, a.ab, a.wv, a.dWb, a.dG, a.dinp, a.N, blockIdx.x, smem);
+    else
+        pj_reduce_block(jc, (int)blockIdx.x - nhost, reinterpret_cast<float (*)[PG_MAXK][65]>(smem), threadIdx.x);
+}
+
 // out (B,T,N,C) = LReLU(hyperTem1(Linear(base = 1 -> C)(masked flow)));  ab (B*T*N, 2): (alpha, beta) per row;  wv (B*T, 2C): (w W_bt | bi W_bt)
 // — both kept for the backward.  src: (B*T*N, lda) rows whose column 0 is the flow;  mask (B*T*N) fp32 1 = visible, or NULL;  w = dim_in_flow.weight
 // (C,1), bi = its bias;  G (N,T,T), Wbt (B*T,C,C), bbt (B*T,C).
@@ -204,15 +235,52 @@ extern "C" int gptst_encin_ht1_fwd(const float* src, int lda, const float* mask,
 // backward of the above given dPre = dOut * lrelu'(out) (chain form):  dWb (B*T, C*C + C) rows [dW_bt | db_bt] (as gptst_hypertem_bwd_wgrad, one split),
 // dG (B, N, T, T) per-sample partials of the temporal-graph gradient, dinp (B*T, 2C) partials of [d dim_in_flow.weight | d dim_in_flow.bias]
 // (the caller sums the rows).  No input gradient exists (the input is data).
+static int encin_bwd_check(const float* dPre, const float* src, int lda, const float* w, const float* bi, const float* Wbt, const float* ab,
+                           const float* wv, float* dWb, float* dG, float* dinp, int B, int T, int N, int C) {
+    if (!dPre || !src || !w || !bi || !Wbt || !ab || !wv || !dWb || !dG || !dinp || B <= 0 || N <= 0 || lda <= 0) return GPTST_EARG;
+    if (T != EI_T || (C != 64 && C != 128)) return GPTST_ESHAPE;
+    if (encin_bwd_smem(C, N) > 64 * 1024) return GPTST_ESHAPE;
+    return GPTST_OK;
+}
+
 extern "C" int gptst_encin_ht1_bwd(const float* dPre, const float* src, int lda, const float* mask, float fill, const float* w, const float* bi,
                                    const float* Wbt, const float* ab, const float* wv, float* dWb, float* dG, float* dinp, int B, int T, int N,
                                    int C, void* stream) {
-    if (!dPre || !src || !w || !bi || !Wbt || !ab || !wv || !dWb || !dG || !dinp || B <= 0 || N <= 0 || lda <= 0) return GPTST_EARG;
-    if (T != EI_T || (C != 64 && C != 128)) return GPTST_ESHAPE;
-    const size_t smem = ((size_t)(256 / (C / 4)) * 4 * C + 6 * C + 2 * (size_t)N) * sizeof(float);
-    if (smem > 64 * 1024) return GPTST_ESHAPE;
-    if (C == 64) hipLaunchKernelGGL((encin_bwd_kernel<64>), dim3(B * T), dim3(256), smem, (hipStream_t)stream, dPre, src, lda, mask, fill, w, bi, Wbt, ab, wv, dWb, dG, dinp, N, B);
-    else hipLaunchKernelGGL((encin_bwd_kernel<128>), dim3(B * T), dim3(256), smem, (hipStream_t)stream, dPre, src, lda, mask, fill, w, bi, Wbt, ab, wv, dWb, dG, dinp, N, B);
+    const int rc = encin_bwd_check(dPre, src, lda, w, bi, Wbt, ab, wv, dWb, dG, dinp, B, T, N, C);
+    if (rc) return rc;
+    const EncinBwdArgs a{dPre, src, mask, w, bi, Wbt, ab, wv, dWb, dG, dinp, lda, N, fill};
+    const size_t smem = encin_bwd_smem(C, N);
+    if (C == 64) hipLaunchKernelGGL((encin_bwd_kernel<64>), dim3(B * T), dim3(256), smem, (hipStream_t)stream, a);
+    else hipLaunchKernelGGL((encin_bwd_kernel<128>), dim3(B * T), dim3(256), smem, (hipStream_t)stream, a);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
+}
+
+// gptst_encin_ht1_bwd followed by gptst_pool_jobs(njobs, ...) with gradient-reduction jobs (kinds 1 / 2) whose inputs EARLIER launches wrote and whose outputs
+// nothing in this launch reads: at C = 64 the heaviest PJ_MAX jobs ride in the backward's launch (encin_bwd_jobs_kernel), what is left of a longer table follows
+// through gptst_pool_jobs; in deterministic mode, at C = 128 or with another kind in the table: exactly the two calls.  No job is left out.
+extern "C" int gptst_encin_ht1_bwd_jobs(const float* dPre, const float* src, int lda, const float* mask, float fill, const float* w, const float* bi,
+                                        const float* Wbt, const float* ab, const float* wv, float* dWb, float* dG, float* dinp, int B, int T, int N,
+                                        int C, int njobs, const int* jkind, const void* const* jemb, const void* const* jx, const void* const* jpool,
+                                        const void* const* jout, const int* jR, const int* jK, const int* jcols, const int* jnsplit, const int* jldx,
+                                        void* stream) {
+    int rc = encin_bwd_check(dPre, src, lda, w, bi, Wbt, ab, wv, dWb, dG, dinp, B, T, N, C);
+    if (rc) return rc;
+    const PJCols cols{njobs, jkind, jemb, jx, jpool, jout, jR, jK, jcols, jnsplit, jldx};
+    PJCarry jc;
+    int taken = 0;
+    if (C == 64) {
+        taken = gptst_pj_carry_take(&jc, &cols);
+        if (taken < 0) return taken;
+    } else if (njobs < 0) return GPTST_EARG;
+    if (taken == 0) {
+        rc = gptst_encin_ht1_bwd(dPre, src, lda, mask, fill, w, bi, Wbt, ab, wv, dWb, dG, dinp, B, T, N, C, stream);
+    } else {
+        const EncinBwdArgs a{dPre, src, mask, w, bi, Wbt, ab, wv, dWb, dG, dinp, lda, N, fill};
+        const size_t fold = (size_t)4 * PG_MAXK * 65 * sizeof(float), own = encin_bwd_smem(C, N);
+        hipLaunchKernelGGL((encin_bwd_jobs_kernel<64>), dim3(B * T + jc.npb + jc.neb), dim3(256), own > fold ? own : fold, (hipStream_t)stream, a, B * T, jc);
+        GPTST_CHECK_LAUNCH();
+    }
+    if (rc) return rc;
+    return gptst_pj_carry_rest(&cols, taken, stream);
 }

@@ -26,9 +26,9 @@
 // Occupancy of the job kernel (r05): one kernel holds every job kind, so its register count is the maximum over the kinds — 152 VGPRs with
 // UC = 8 column steps per batch in the embedding-gradient jobs, i.e. 3 waves per SIMD, and the reductions stream at 3.8-4.0 TB/s with 48 KB in
 // flight per CU (tools/mb_pooljobs.py).  PJ_OCC = minimum waves per SIMD the compiler must leave room for, PJ_UC / PJ_NU = loads per batch.
-#ifndef PJ_OCC
-#define PJ_OCC 6       // r05: 76 VGPRs with PJ_UC = 4 (was 152 / 3 waves per SIMD): the forward table 32.8 -> 28.0 us, the reduction table unchanged at the
-#endif                 // ~4 TB/s a streaming read reaches on this chip (torch.sum: 3.7-4.9 TB/s), profiles/r05_pooljobs_occupancy.txt
+// PJ_OCC = 6 (poolgen_dev.h: the launches that host the reductions as a role keep it too), r05: 76 VGPRs with PJ_UC = 4 (was 152 / 3 waves per SIMD): the
+// forward table 32.8 -> 28.0 us, the reduction table unchanged at the ~4 TB/s a streaming read reaches on this chip (torch.sum: 3.7-4.9 TB/s),
+// profiles/r05_pooljobs_occupancy.txt
 // (PJ_MAX, PJob, PJobs, pj_fwd_mfma: poolgen_dev.h — the cooperative mask launch of masksel.hip carries forward jobs too, r05)
 
 // out[r, :] = sum_k emb[r,k] pool[k, :].   blocks: (ceil(cols/V/256), ceil(R/rows)), rows <= PG_MAXROWS
@@ -239,6 +239,69 @@ GPTST_INTERNAL int gptst_pj_reduce_table(PJobs* t, int njobs, const int* kind, c
     return GPTST_OK;
 }
 
+// Workgroups are dispatched in table order: the jobs whose workgroups stream the most bytes go first, so that the launch does not end
+// with a few long workgroups on an otherwise idle chip (the jobs of a call are independent: any order gives the same result).
+static std::vector<int> pj_order(int njobs, const int* kind, const int* R, const int* cols, const int* nsplit) {
+    std::vector<int> ord(njobs);
+    std::vector<long> cost(njobs);
+    for (int p = 0; p < njobs; ++p) {
+        ord[p] = p;
+        const long rr = (long)R[p] * nsplit[p], cc = cols[p];
+        cost[p] = kind[p] == PJ_BWD_POOL ? rr * (cc < 64 ? cc : 64) : kind[p] == PJ_BWD_EMB ? 16L * nsplit[p] * (cc < 1024 ? cc : 1024)
+                : kind[p] == PJ_FWD ? 64L * (cc < 256 ? cc : 256) : 1L;
+    }
+    if (g_pg_sort) std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cost[a] > cost[b]; });
+    return ord;
+}
+
+// the columns of a call's job table in another row order (rows ord[first .. njobs))
+struct PJGathered {
+    std::vector<int> kind, R, K, cols, nsplit, ldx;
+    std::vector<const void*> emb, x, pool, out;
+    PJGathered(const PJCols& j, const std::vector<int>& ord, int first, int last) {
+        for (int o = first; o < last; ++o) {
+            const int p = ord[o];
+            kind.push_back(j.kind[p]); R.push_back(j.R[p]); K.push_back(j.K[p]); cols.push_back(j.cols[p]); nsplit.push_back(j.nsplit[p]);
+            ldx.push_back(j.ldx ? j.ldx[p] : 0);
+            emb.push_back(j.emb[p]); x.push_back(j.x[p]); pool.push_back(j.pool[p]); out.push_back(j.out[p]);
+        }
+    }
+};
+
+static bool pj_cols_ok(const PJCols* j) {
+    return j && j->njobs >= 0 && (j->njobs == 0 || (j->kind && j->emb && j->x && j->pool && j->out && j->R && j->K && j->cols && j->nsplit));
+}
+
+GPTST_INTERNAL int gptst_pj_carry_take(PJCarry* c, const PJCols* j) {
+    if (!c || !pj_cols_ok(j)) return GPTST_EARG;
+    c->t.n = c->npool = c->npb = c->neb = 0;
+    if (j->njobs == 0 || g_deterministic) return 0;
+    for (int p = 0; p < j->njobs; ++p) {
+        if (j->kind[p] < PJ_FWD || j->kind[p] > PJ_GRAM) return GPTST_EARG;
+        if (j->kind[p] != PJ_BWD_POOL && j->kind[p] != PJ_BWD_EMB) return 0;
+    }
+    const std::vector<int> ord = pj_order(j->njobs, j->kind, j->R, j->cols, j->nsplit);
+    const int take = j->njobs < PJ_MAX ? j->njobs : PJ_MAX;
+    const PJGathered g(*j, ord, 0, take);
+    const int rc = gptst_pj_reduce_table(&c->t, take, g.kind.data(), g.emb.data(), g.x.data(), g.pool.data(), g.out.data(), g.R.data(), g.K.data(),
+                                         g.cols.data(), g.nsplit.data(), g.ldx.data(), &c->npool, &c->npb, &c->neb);
+    if (rc == GPTST_ESHAPE) { c->t.n = c->npool = c->npb = c->neb = 0; return 0; }
+    return rc ? rc : take;
+}
+
+extern "C" int gptst_pool_jobs(int njobs, const int* kind, const void* const* emb, const void* const* x, const void* const* pool,
+                               const void* const* out, const int* R, const int* K, const int* cols, const int* nsplit, const int* ldx,
+                               void* stream);
+GPTST_INTERNAL int gptst_pj_carry_rest(const PJCols* j, int taken, void* stream) {
+    if (!pj_cols_ok(j) || taken < 0 || taken > j->njobs) return GPTST_EARG;
+    if (taken == j->njobs) return GPTST_OK;
+    if (taken == 0) return gptst_pool_jobs(j->njobs, j->kind, j->emb, j->x, j->pool, j->out, j->R, j->K, j->cols, j->nsplit, j->ldx, stream);
+    const std::vector<int> ord = pj_order(j->njobs, j->kind, j->R, j->cols, j->nsplit);
+    const PJGathered g(*j, ord, taken, j->njobs);
+    return gptst_pool_jobs(j->njobs - taken, g.kind.data(), g.emb.data(), g.x.data(), g.pool.data(), g.out.data(), g.R.data(), g.K.data(),
+                           g.cols.data(), g.nsplit.data(), g.ldx.data(), stream);
+}
+
 // Generic entry: njobs problems of any kind in as few launches as the 4 KB argument block allows (PJ_MAX jobs each).
 // A BWD_EMB job must not share a launch with a job that produces its input; callers order dependent work into separate calls.
 extern "C" int gptst_pool_jobs(int njobs, const int* kind, const void* const* emb, const void* const* x, const void* const* pool,
@@ -251,17 +314,7 @@ extern "C" int gptst_pool_jobs(int njobs, const int* kind, const void* const* em
                     0, kind[p], 0, ldx ? ldx[p] : 0};
     };
     const bool det = g_deterministic != 0;
-    // Workgroups are dispatched in table order: the jobs whose workgroups stream the most bytes go first, so that the launch does not end
-    // with a few long workgroups on an otherwise idle chip (the jobs of a call are independent: any order gives the same result).
-    std::vector<int> ord(njobs);
-    std::vector<long> cost(njobs);
-    for (int p = 0; p < njobs; ++p) {
-        ord[p] = p;
-        const long rr = (long)R[p] * nsplit[p], cc = cols[p];
-        cost[p] = kind[p] == PJ_BWD_POOL ? rr * (cc < 64 ? cc : 64) : kind[p] == PJ_BWD_EMB ? 16L * nsplit[p] * (cc < 1024 ? cc : 1024)
-                : kind[p] == PJ_FWD ? 64L * (cc < 256 ? cc : 256) : 1L;
-    }
-    if (g_pg_sort) std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return cost[a] > cost[b]; });
+    const std::vector<int> ord = pj_order(njobs, kind, R, cols, nsplit);
     PJobs t; t.n = 0;
     for (int o = 0; o < njobs; ++o) {                            // table launches (in deterministic mode: everything but the kind-2 jobs)
         const int p = ord[o];

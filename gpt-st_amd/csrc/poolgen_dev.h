@@ -92,6 +92,9 @@ __device__ __forceinline__ void pj_gram(const PJob& a, int bx, float* __restrict
 
 // ---- the two gradient reductions (kinds 1 and 2), 256 threads `tid` each: also run as role workgroups of a backward launch that leaves CUs and HBM
 // bandwidth idle (cap_mfma.hip, r05) ----
+#ifndef PJ_OCC
+#define PJ_OCC 6       // minimum waves per SIMD of every kernel that runs these job bodies (poolgen.hip)
+#endif
 #ifndef PJ_UC
 #define PJ_UC 4
 #endif
@@ -236,3 +239,30 @@ __device__ __forceinline__ void pj_bwd_emb(const PJob& a, int bx, int by, int ti
         if (orow < a.R && i < a.K && (by * 4 + wave) * 256 < a.cols) atomicAdd(a.out + (size_t)orow * a.K + i, acc[r]);
     }
 }
+
+// ---- a reduce table (gptst_pj_reduce_table) as the job role of a launch whose first workgroups are another kernel's ("host": encin.hip, tmix.hip,
+// timefeat.hip — the end of the backward) ----
+// jobs [0, npool) are kind 1 and own the 256-thread blocks [0, npb), the rest are kind 2 and own [npb, npb + neb)
+struct PJCarry { PJobs t; int npool, npb, neb; };
+__device__ __forceinline__ void pj_reduce_block(const PJCarry& c, int vb, float (*fold)[PG_MAXK][65], int tid) {
+    if (vb < c.npb) {
+        int p = 0;
+        for (int q = 1; q < c.npool; ++q) if (vb >= c.t.j[q].blk0) p = q;           // uniform scan of the (scalar) table
+        const PJob& a = c.t.j[p];
+        if (((a.cols | a.ldx) & 3) == 0) pj_bwd_pool<4>(a, vb - a.blk0, fold, tid); else pj_bwd_pool<1>(a, vb - a.blk0, fold, tid);
+    } else if (vb < c.npb + c.neb) {
+        vb -= c.npb;
+        int p = c.npool;
+        for (int q = c.npool + 1; q < c.t.n; ++q) if (vb >= c.t.j[q].blk0) p = q;
+        const PJob& a = c.t.j[p];
+        const int rel = vb - a.blk0;
+        if (((a.cols | a.ldx) & 3) == 0) pj_bwd_emb<4>(a, rel % a.nbx, rel / a.nbx, tid); else pj_bwd_emb<1>(a, rel % a.nbx, rel / a.nbx, tid);
+    }
+}
+// host side (poolgen.hip).  gptst_pj_carry_take: the jobs of a call, heaviest first, as the table a hosting launch carries -> how many it holds
+// (the first of that order; 0: none — an empty call, the deterministic mode, a kind that is not a reduction) or a negative GPTST_E* code.
+// gptst_pj_carry_rest: every job behind the first `taken` of the same order through gptst_pool_jobs, so that no job of the call is left out.
+struct PJCols { int njobs; const int* kind; const void* const* emb; const void* const* x; const void* const* pool; const void* const* out;
+                const int *R, *K, *cols, *nsplit, *ldx; };
+GPTST_INTERNAL int gptst_pj_carry_take(PJCarry* c, const PJCols* j);
+GPTST_INTERNAL int gptst_pj_carry_rest(const PJCols* j, int taken, void* stream);

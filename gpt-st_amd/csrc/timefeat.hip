@@ -6,6 +6,7 @@
 // reduced per workgroup from the LDS lines (+= with one atomic per output and workgroup).
 // Feature k of row r is tidx[(r*K + k)*2 + {0: day, 1: week}].
 #include "common.h"
+#include "poolgen_dev.h"
 
 struct TfParams {      // nn.Linear tensors: weight (out,in) row-major, bias (out)
     const float *wd, *bd, *ww, *bw, *w1, *b1, *w2, *b2, *w3, *b3;
@@ -157,7 +158,29 @@ __global__ __launch_bounds__(BWD == 2 ? TF_DET_T : 256) void timefeat_jobs_kerne
 #undef TF_CASE
 }
 
-static int tf_launch(TfJobs& t, int bwd, hipStream_t st) {
+// TAIL ROLES, level 3 of the end of the backward: the grid is [time-feature row blocks | job blocks].  The jobs are the reductions over dA (the node embeddings'
+// and the adj pools' gradients), which the launch before wrote; the time-feature MLPs read the time embeddings' gradients, which earlier launches completed.
+// The time-feature role wants 96 weight registers per lane at E = 16: under the job kernel's PJ_OCC it would spill, and this launch carries a few MB of
+// jobs only, so the HOST role sets this kernel's bound (4 waves per SIMD).
+__global__ __launch_bounds__(256, 4) void timefeat_bwd_jobs_kernel(TfJobs t, int nhost, PJCarry jc) {
+    constexpr int FOLD = 4 * PG_MAXK * 65;
+    __shared__ __attribute__((aligned(16))) float sh[FOLD > TF_SH_FLOATS ? FOLD : TF_SH_FLOATS];
+    if ((int)blockIdx.x >= nhost) { pj_reduce_block(jc, (int)blockIdx.x - nhost, reinterpret_cast<float (*)[PG_MAXK][65]>(sh), threadIdx.x); return; }
+    int q = 0;
+    for (int i = 1; i < t.n; ++i) if ((int)blockIdx.x >= t.j[i].blk0) q = i;
+    const TfJob& a = t.j[q];
+    const int blk = blockIdx.x - a.blk0;
+    switch (a.E) {
+    case 2: tf_bwd_body<2, false, 256>(a.p, a.g, a.tidx, a.dout, a.rows, a.K, blk, sh); break;
+    case 4: tf_bwd_body<4, false, 256>(a.p, a.g, a.tidx, a.dout, a.rows, a.K, blk, sh); break;
+    case 8: tf_bwd_body<8, false, 256>(a.p, a.g, a.tidx, a.dout, a.rows, a.K, blk, sh); break;
+    case 16: tf_bwd_body<16, false, 256>(a.p, a.g, a.tidx, a.dout, a.rows, a.K, blk, sh); break;
+    default: break;
+    }
+}
+
+// jc: a table of reduction jobs the backward launch carries (not in deterministic mode, whose launch is one workgroup per instance)
+static int tf_launch(TfJobs& t, int bwd, hipStream_t st, const PJCarry* jc = nullptr) {
     int nb = 0;
     for (int q = 0; q < t.n; ++q) {
         TfJob& a = t.j[q];
@@ -167,7 +190,9 @@ static int tf_launch(TfJobs& t, int bwd, hipStream_t st) {
         a.blk0 = nb;
         nb += (a.rows + rows_per - 1) / rows_per;
     }
-    if (bwd && g_deterministic) hipLaunchKernelGGL(timefeat_jobs_kernel<2>, dim3(t.n), dim3(TF_DET_T), 0, st, t);
+    if (jc && (!bwd || g_deterministic)) return GPTST_EARG;
+    if (jc) hipLaunchKernelGGL(timefeat_bwd_jobs_kernel, dim3(nb + jc->npb + jc->neb), dim3(256), 0, st, t, nb, *jc);
+    else if (bwd && g_deterministic) hipLaunchKernelGGL(timefeat_jobs_kernel<2>, dim3(t.n), dim3(TF_DET_T), 0, st, t);
     else if (bwd) hipLaunchKernelGGL(timefeat_jobs_kernel<1>, dim3(nb), dim3(256), 0, st, t);
     else hipLaunchKernelGGL(timefeat_jobs_kernel<0>, dim3(nb), dim3(256), 0, st, t);
     GPTST_CHECK_LAUNCH();
@@ -196,8 +221,8 @@ extern "C" int gptst_timefeat_bwd(const float* wd, const float* bd, const float*
 
 // njobs instances in ONE launch.  params: njobs x 10 pointers (module order, as above); grads: njobs x 10 pointers (bwd only, +=);
 // io: njobs outputs (fwd) or output gradients (bwd); rows / K / E per job; all jobs read the same tidx (B,T,2).
-extern "C" int gptst_timefeat_jobs(int njobs, int bwd, const void* const* params, const void* const* grads, const float* tidx,
-                                   const void* const* io, const int* rows, const int* K, const int* E, void* stream) {
+static int tf_jobs(int njobs, int bwd, const void* const* params, const void* const* grads, const float* tidx,
+                   const void* const* io, const int* rows, const int* K, const int* E, void* stream, const PJCarry* jc) {
     if (njobs <= 0 || njobs > TF_MAXJ || !params || !io || !rows || !K || !E || (bwd && !grads)) return GPTST_EARG;
     TfJobs t; t.n = njobs;
     for (int q = 0; q < njobs; ++q) {
@@ -207,5 +232,26 @@ extern "C" int gptst_timefeat_jobs(int njobs, int bwd, const void* const* params
         t.j[q] = TfJob{TfParams{pp[0], pp[1], pp[2], pp[3], pp[4], pp[5], pp[6], pp[7], pp[8], pp[9]}, g, tidx,
                        bwd ? nullptr : (float*)io[q], bwd ? (const float*)io[q] : nullptr, rows[q], K[q], E[q], 0};
     }
-    return tf_launch(t, bwd, (hipStream_t)stream);
+    return tf_launch(t, bwd, (hipStream_t)stream, jc);
+}
+
+extern "C" int gptst_timefeat_jobs(int njobs, int bwd, const void* const* params, const void* const* grads, const float* tidx,
+                                   const void* const* io, const int* rows, const int* K, const int* E, void* stream) {
+    return tf_jobs(njobs, bwd, params, grads, tidx, io, rows, K, E, stream, nullptr);
+}
+
+// gptst_timefeat_jobs(njobs, bwd = 1, ...) followed by gptst_pool_jobs(npj, ...) with gradient-reduction jobs (kinds 1 / 2) whose inputs EARLIER launches wrote
+// and which neither read nor write what the time-feature backward touches: the heaviest PJ_MAX jobs ride in the same launch (timefeat_bwd_jobs_kernel), what
+// is left of a longer table follows through gptst_pool_jobs; in deterministic mode or with another kind in the table: exactly the two calls.  No job is left out.
+extern "C" int gptst_timefeat_jobs_bwd_jobs(int njobs, const void* const* params, const void* const* grads, const float* tidx, const void* const* io,
+                                            const int* rows, const int* K, const int* E, int npj, const int* jkind, const void* const* jemb,
+                                            const void* const* jx, const void* const* jpool, const void* const* jout, const int* jR, const int* jK,
+                                            const int* jcols, const int* jnsplit, const int* jldx, void* stream) {
+    const PJCols cols{npj, jkind, jemb, jx, jpool, jout, jR, jK, jcols, jnsplit, jldx};
+    PJCarry jc;
+    const int taken = gptst_pj_carry_take(&jc, &cols);
+    if (taken < 0) return taken;
+    const int rc = tf_jobs(njobs, 1, params, grads, tidx, io, rows, K, E, stream, taken ? &jc : nullptr);
+    if (rc) return rc;
+    return gptst_pj_carry_rest(&cols, taken, stream);
 }

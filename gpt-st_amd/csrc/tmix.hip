@@ -6,6 +6,7 @@
 //           tmix_dgraph (dG_n = sum_b dR[b,:,n,:] X[b,:,n,:]^T on fp32 MFMA 16x16x4),  gram_bwd (dG -> dA).
 // T is fixed at 12 by the reference (GPTST.py:97,208-209).
 #include "common.h"
+#include "poolgen_dev.h"
 
 #define TT 12
 #define TT2 144
@@ -23,10 +24,11 @@ __global__ __launch_bounds__(256) void gram_fwd_kernel(const float* __restrict__
 
 // ---- dA[n,h,t] = sum_u A[n,h,u] (dG[n,t,u] + dG[n,u,t]) -----------------------------------------------------
 // one workgroup per (layer, node): the nsplit partial graphs dG[l][s][n] are summed in a fixed order into LDS first
-__global__ __launch_bounds__(256) void gram_bwd_kernel(const float* __restrict__ A, const float* __restrict__ dG,
-                                                       float* __restrict__ dA, int N, int Hm, int nsplit) {
-    __shared__ float gs[TT2];
-    const int gn = blockIdx.x, l = gn / N, n = gn % N;
+// (a __device__ body on 256 threads: block `gn` = (layer, node), gs = TT2 floats of LDS — the stand-alone kernel and the launch that carries
+// reduction jobs next to it run the same code)
+__device__ __forceinline__ void gram_bwd_body(const float* __restrict__ A, const float* __restrict__ dG, float* __restrict__ dA, int N, int Hm,
+                                              int nsplit, int gn, float* __restrict__ gs) {
+    const int l = gn / N, n = gn % N;
     if (threadIdx.x < TT2) {
         const float* g = dG + ((size_t)l * nsplit * N + n) * TT2 + threadIdx.x;
         // 8 independent loads in flight, summed in a FIXED order (partial k holds splits k, k+8, ...): a plain loop is a chain of
@@ -51,6 +53,21 @@ __global__ __launch_bounds__(256) void gram_bwd_kernel(const float* __restrict__
 #pragma unroll
     for (int u = 0; u < TT; ++u) s = fmaf(a[u], gs[t * TT + u] + gs[u * TT + t], s);
     dA[((size_t)gn * Hm + h) * TT + t] = s;
+}
+
+__global__ __launch_bounds__(256) void gram_bwd_kernel(const float* __restrict__ A, const float* __restrict__ dG,
+                                                       float* __restrict__ dA, int N, int Hm, int nsplit) {
+    __shared__ float gs[TT2];
+    gram_bwd_body(A, dG, dA, N, Hm, nsplit, blockIdx.x, gs);
+}
+
+// TAIL ROLES, level 2 of the end of the backward: the grid is [L*N graph workgroups | job blocks].  The jobs are the reductions over what the launch before
+// wrote (the encoder's first layer: gptst_encin_ht1_bwd's dWb / dinp); they do not read dA and this role does not read their outputs.
+__global__ __launch_bounds__(256, PJ_OCC) void gram_bwd_jobs_kernel(const float* __restrict__ A, const float* __restrict__ dG,
+                                                                    float* __restrict__ dA, int N, int Hm, int nsplit, int nhost, PJCarry jc) {
+    __shared__ __attribute__((aligned(16))) float fold[4][PG_MAXK][65];
+    if ((int)blockIdx.x < nhost) gram_bwd_body(A, dG, dA, N, Hm, nsplit, blockIdx.x, &fold[0][0][0]);
+    else pj_reduce_block(jc, (int)blockIdx.x - nhost, fold, threadIdx.x);
 }
 
 // ---- out[b,t,n,:] = sum_u G[n,t,u] X[b,u,n,:]  (+ dOut * lrelu'(Y) when ADD_DPRE: the residual branch of backward) --
@@ -262,6 +279,27 @@ extern "C" int gptst_gram_bwd(const float* A, const float* dG, float* dA, int L,
     hipLaunchKernelGGL(gram_bwd_kernel, dim3(L * N), dim3(256), 0, (hipStream_t)stream, A, dG, dA, N, Hm, nsplit);
     GPTST_CHECK_LAUNCH();
     return GPTST_OK;
+}
+
+// gptst_gram_bwd followed by gptst_pool_jobs(njobs, ...) with gradient-reduction jobs (kinds 1 / 2) that neither read dA nor write what this call reads:
+// the heaviest PJ_MAX jobs ride in the same launch (gram_bwd_jobs_kernel), what is left of a longer table follows through gptst_pool_jobs; in
+// deterministic mode or with another kind in the table: exactly the two calls.  No job is left out.
+extern "C" int gptst_gram_bwd_jobs(const float* A, const float* dG, float* dA, int L, int N, int Hm, int nsplit, int njobs, const int* jkind,
+                                   const void* const* jemb, const void* const* jx, const void* const* jpool, const void* const* jout, const int* jR,
+                                   const int* jK, const int* jcols, const int* jnsplit, const int* jldx, void* stream) {
+    if (!A || !dG || !dA || L <= 0 || N <= 0 || nsplit <= 0 || Hm * TT > 256) return GPTST_EARG;
+    const PJCols cols{njobs, jkind, jemb, jx, jpool, jout, jR, jK, jcols, jnsplit, jldx};
+    PJCarry jc;
+    const int taken = gptst_pj_carry_take(&jc, &cols);
+    if (taken < 0) return taken;
+    if (taken == 0) {
+        const int rc = gptst_gram_bwd(A, dG, dA, L, N, Hm, nsplit, stream);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(gram_bwd_jobs_kernel, dim3(L * N + jc.npb + jc.neb), dim3(256), 0, (hipStream_t)stream, A, dG, dA, N, Hm, nsplit, L * N, jc);
+        GPTST_CHECK_LAUNCH();
+    }
+    return gptst_pj_carry_rest(&cols, taken, stream);
 }
 
 // the dPre-chain form (r05): dX = (dPre + G (*) dR) [* lrelu'(X) when premul], dG as above; the layer's output is not read

@@ -76,7 +76,8 @@ class Reductions:
     generated weights' gradients into their pools and embeddings (GPTST.py:24-25,29-30,104,129,137-138,156,160-161 backward), the
     temporal-graph factor gradients and the seven time-feature MLPs — is collected here while the data-gradient chain runs and
     executed at the end of the backward as THREE launches (gram_bwd, one job table, one time-feature job table) instead of ~20
-    small launches per STHCN.  Nothing on the critical chain waits for these results; only the optimiser does."""
+    small launches per STHCN.  Nothing on the critical chain waits for these results; only the optimiser does.  In the tail-role form
+    (tail_roles_ok) the job table has no launch of its own: the encoder's first-layer backward, gram_bwd and the time-feature backward carry it."""
 
     def __init__(self):
         self.jobs = ops.PoolJobs()   # reductions whose inputs are complete when they are queued (their producer has been launched)
@@ -91,6 +92,8 @@ class Reductions:
         self.fork_side = None
         self.forked = False          # a fork is open: flush() joins it
         self._dG = self._dA = None   # graph / factor gradient buffers shared by the step's STHCNs (_grad_buffers)
+        self.want_tail = False       # the caller's step may end its backward in the tail-role form (the fused steppers: step.py)
+        self.tail = False            # ... and this step does (tail_roles_ok, decided by step_bwd): the last three launches carry the reductions
 
     def take_carry(self, mb):
         """Up to `mb` MB of the queued reductions for a backward launch that carries them as role workgroups (ops.cap_cross_route_lin_bwd jobs=): the
@@ -110,6 +113,12 @@ class Reductions:
         self.jobs.jobs = rest
         c = ops.PoolJobs()
         c.jobs = take
+        return c
+
+    def take_all(self):
+        """every queued reduction, for the launch that carries them at the end of the backward (tail roles: ops.encin_ht1_bwd jobs=)"""
+        c = ops.PoolJobs()
+        c.jobs, self.jobs.jobs = self.jobs.jobs, []
         return c
 
     def untake(self, carry):
@@ -152,11 +161,18 @@ class Reductions:
                 A = torch.as_strided(A, (A.shape[0] + A2.shape[0],) + tuple(A.shape[1:]), A.stride())
                 dG = torch.as_strided(dG, (dG.shape[0] + dG2.shape[0],) + tuple(dG.shape[1:]), dG.stride())
                 dA = torch.as_strided(dA, (dA.shape[0] + dA2.shape[0],) + tuple(dA.shape[1:]), dA.stride())
-            ops.gram_bwd(A, dG, out=dA, layers=A.shape[0] // N, nsplit=nsG)
-        self.jobs.jobs, self.late.jobs = self.jobs.jobs + self.late.jobs, []
-        self.jobs.launch()
+            # tail roles, level 2: what was queued behind the encoder's first layer (its own reductions; the guide's, where the forward did not
+            # carry the KL path) rides with the graph-factor gradients — every producer has been enqueued, and none of these jobs reads dA
+            ops.gram_bwd(A, dG, out=dA, layers=A.shape[0] // N, nsplit=nsG, jobs=self.jobs if self.tail else None)
         tf, self.tf = self.tf, []
-        ops.timefeat_jobs_bwd(tf, tidx)
+        if self.tail:                               # level 3: the reductions over dA ride with the time-feature MLPs' backward
+            self.jobs.launch()                      # (nothing left, unless the step had no temporal graph)
+            ops.timefeat_jobs_bwd(tf, tidx, jobs=self.late)
+        else:
+            self.jobs.jobs, self.late.jobs = self.jobs.jobs + self.late.jobs, []
+            self.jobs.launch()
+            ops.timefeat_jobs_bwd(tf, tidx)
+        self.tail = False
         self.keep = []
 
 
@@ -300,6 +316,7 @@ def hypertem_core_bwd(saved, dout, dG_out, dims, chain=False, premul=False):
 CARRY_RED = os.environ.get("GPTST_CARRY_RED", "1") == "1"        # queued weight-gradient reductions as role workgroups of the routing backward (r05, late)
 CARRY_MB = float(os.environ.get("GPTST_CARRY_MB", "25"))        # at most this much of them per launch
 CARRY_KL = os.environ.get("GPTST_CARRY_KL", "1") == "1"        # the KL path's backward as guests of the forward's chain launches (KlCarry; 0: after model_bwd)
+TAIL_ROLES = os.environ.get("GPTST_TAIL_ROLES", "1") == "1"        # the end of the backward in three launches that carry the reductions (tail_roles_ok; 0: four launches)
 PAIR_UNDER_DP = os.environ.get("GPTST_PAIR_UNDER_DP", "1") == "1"    # the decoder-hyperTem1 / encoder-hyperTem4 pair also when the decoder's gradient bucket leaves early (r05)
 PAIR_BWD = os.environ.get("GPTST_PAIR_BWD", "1") == "1"        # two adjacent hyperTem layers' backward in one launch (r04)
 
@@ -326,6 +343,22 @@ def pair_bwd_on():
 
 def cross_role():
     return 0 if CTX.NO_HANDOFFS else CROSS_ROLE
+
+
+TAIL_MAX_WG = 512      # most workgroups of a level's own grid (B*T + 4B, the routing role form's bound) for the tail-role form
+
+
+def tail_roles_ok(red, dims, sv_e):
+    """The end of the backward — the encoder's low-rank first layer, gram_bwd, the reduction launch, the time-feature MLPs: none of them on the
+    data-gradient chain — runs as THREE launches, each carrying the reductions whose inputs exist by then as further workgroups (ops.encin_ht1_bwd /
+    gram_bwd / timefeat_jobs_bwd jobs=).  Taken where the step is of the kind that carries reductions in its routing backward (cap_core_bwd): not in
+    deterministic or safe mode, not under the data-parallel bucket overlap or node shards, C = 64, the low-rank EncIn first layer, and a batch whose
+    B*T (b,t) workgroups leave the chip room (the grid bound of gptst_cap_route_roles_ok; its LDS bound is the routing kernel's own and does not
+    matter here: N = 207 and N = 24 take this form); a caller asks for it with red.want_tail."""
+    B, T, N, C = dims
+    return bool(TAIL_ROLES and red.want_tail and CARRY_RED and not red.no_carry and red.on_bucket is None and CTX.NODE_REDUCE is None
+                and cross_role() and FUSE_CROSS and CAP_LIN and C == 64 and T == 12 and sv_e is not None and isinstance(sv_e.h1, EncIn)
+                and B * T + 4 * B <= TAIL_MAX_WG)
 
 
 def _ht_pair_shape_ok(dims):
@@ -750,8 +783,11 @@ def sthcn_bwd(p, g, pfx, tidx, sv, dout, dims, red, chain=False, premul_in=False
         assert chain
         e = sv.h1
         w, bi = p["encoder.dim_in_flow.weight"], p["encoder.dim_in_flow.bias"]
+        # tail roles, level 1: nothing is on the data-gradient chain behind this launch, and every reduction queued so far reads what earlier
+        # launches wrote — they ride here instead of waiting for the reduction launch (what is queued from here on: level 2, Reductions._run)
+        carry = red.take_all() if red.tail else None
         if nsG == B:
-            dWb, _, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv, dG=dG_all[0])
+            dWb, _, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv, dG=dG_all[0], jobs=carry)
         else:       # (C = 128: the other layers write ONE graph-gradient partial; this kernel writes one per sample)
             dWb, dGb, dinp = ops.encin_ht1_bwd(dd.view(B, T, N, C), e.source, e.mask, e.fill, w, bi, e.Wbt, e.ab, e.wv)
             torch.sum(dGb, 0, out=dG_all[0][0])
@@ -1089,8 +1125,14 @@ def step_bwd(p, g, source, mask, tidx, fw, prob, sv_g, dims, base, scaler_zeros,
         chain = chain_ok(dims)                                                 # dPre chain: no backward kernel re-reads its layer's output
         done = kl.out if kl is not None else KlOut()                           # outputs of the stages the chain launches carried
         _, dd = loss_tail(p, g, fw.dec, source, mask, base, sigma, mu, thresh, sws, red, chain=chain)
+        red.tail = chain and tail_roles_ok(red, dims, fw.sv_e)
+        # tail roles: the inputs of a carried KL path's reductions have existed since the forward — queued first, they ride at level 1
+        kl_first = red.tail and with_kl and None not in (done.head, done.tem, done.inp)
+        if kl_first:
+            dh2 = kl_head(p, g, sv_g, prob, fw.c1, N, 0.1, sws, red, chain=chain, carried=done.head)
+            guide_bwd(p, g, source, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=done)
         model_bwd(p, g, source, mask, tidx, fw.sv_e, fw.sv_d, fw.dec, None, None, dims, base, scaler_zeros, red, dd=dd, chain=chain)
-        if with_kl:
+        if with_kl and not kl_first:
             dh2 = kl_head(p, g, sv_g, prob, fw.c1, N, 0.1, sws, red, chain=chain, carried=done.head)
             guide_bwd(p, g, source, tidx, sv_g, None, dims, base, red, dh2=dh2, chain=chain, carried=done)
     else:

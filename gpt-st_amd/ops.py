@@ -26,20 +26,24 @@ LAST_CALL = {}    # (name, tag) -> argument tuple of the most recent timed launc
 CALL_LOCK = None  # tests that emulate ranks with threads set a threading.Lock: one C-ABI call (= all launches of one op) at a time
 
 
-def _call(name, *args, tag="", nbytes=0):
+def _call(name, *args, tag="", nbytes=0, entry=None):
+    """entry: the C entry point to call when it is not `name` — a form of `name` that carries a job table (jobs= below).  The launch is
+    recorded under `name`, the table goes into the tag; LAST_CALL keeps no arguments for it (they are another entry point's)."""
+    fn = entry or name
     if CALL_LOCK is not None:
         with CALL_LOCK:
-            _C.lib().call(name, *args, _C.stream())
+            _C.lib().call(fn, *args, _C.stream())
         return
     if TIMER is None:
-        _C.lib().call(name, *args, _C.stream())
+        _C.lib().call(fn, *args, _C.stream())
         return
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    _C.lib().call(name, *args, _C.stream())
+    _C.lib().call(fn, *args, _C.stream())
     e1.record()
     TIMER.append((name, tag, e0, e1, nbytes))
-    LAST_CALL[(name, tag)] = args
+    if entry is None:
+        LAST_CALL[(name, tag)] = args
 
 
 def _nb(*ts):
@@ -200,6 +204,15 @@ class PoolJobs:
         return [len(js)] + [(_ptrs0 if f in ("emb", "dW", "pool", "out") else _ints)([getattr(j, f) for j in js])
                             for f in PoolJob._fields if f in fields]
 
+    def take_reductions(self):
+        """-> (the ctypes columns of this table, its tag, its bytes, the jobs) for a launch that carries it (jobs= of encin_ht1_bwd / gram_bwd /
+        timefeat_jobs_bwd: gradient reductions only), and empties the table.  The caller holds the returned jobs until its call has been enqueued:
+        they are the last reference to some operands (a routing backward's dWp / dbp), the columns are raw pointers, and memory freed before the
+        enqueue can be handed to another thread's launch that the stream runs first (ranks emulated by threads)."""
+        assert not self.post and all(j.kind in (self.BWD_POOL, self.BWD_EMB) for j in self.jobs)
+        js, self.jobs = self.jobs, []
+        return self.columns(js), "+jobs%d" % len(js), _nb(*[t for j in js for t in (j.emb, j.dW, j.pool, j.out)]), js
+
     def launch(self):
         js, self.jobs = self.jobs, []
         post, self.post = self.post, []
@@ -294,11 +307,18 @@ def gram_fwd(A):
     return G
 
 
-def gram_bwd(A, dG, out=None, layers=1, nsplit=1):
-    """A (L*N,Hm,T); dG (L, nsplit, N, T, T) partial graph gradients (summed in a fixed order) -> dA (L*N,Hm,T)."""
+def gram_bwd(A, dG, out=None, layers=1, nsplit=1, jobs=None):
+    """A (L*N,Hm,T); dG (L, nsplit, N, T, T) partial graph gradients (summed in a fixed order) -> dA (L*N,Hm,T).
+    jobs: a PoolJobs table of gradient reductions that neither read dA nor write A / dG — launched here, as further workgroups of this launch
+    (gptst_gram_bwd_jobs), and emptied."""
     LN, Hm, T = A.shape
     dA = out if out is not None else torch.empty_like(A)
-    _call("gptst_gram_bwd", _p(A), _p(dG), _p(dA), layers, LN // layers, Hm, nsplit)
+    if jobs is not None and jobs.jobs:
+        cols, tag, nb, held = jobs.take_reductions()
+        _call("gptst_gram_bwd", _p(A), _p(dG), _p(dA), layers, LN // layers, Hm, nsplit, *cols, tag=tag, nbytes=nb, entry="gptst_gram_bwd_jobs")
+        del held
+    else:
+        _call("gptst_gram_bwd", _p(A), _p(dG), _p(dA), layers, LN // layers, Hm, nsplit)
     return dA
 
 
@@ -361,8 +381,10 @@ def encin_ht1_fwd(source, base, mask, fill, w, bi, G, Wbt, bbt):
     return out, ab, wv
 
 
-def encin_ht1_bwd(dPre, source, mask, fill, w, bi, Wbt, ab, wv, dG=None):
-    """-> dWb (B*T, C*C + C) rows [dW_bt | db_bt], dG (B,N,T,T) per-sample partials, dinp (B*T, 2C) partials of d(dim_in_flow.weight | bias)."""
+def encin_ht1_bwd(dPre, source, mask, fill, w, bi, Wbt, ab, wv, dG=None, jobs=None):
+    """-> dWb (B*T, C*C + C) rows [dW_bt | db_bt], dG (B,N,T,T) per-sample partials, dinp (B*T, 2C) partials of d(dim_in_flow.weight | bias).
+    jobs: a PoolJobs table of gradient reductions whose inputs earlier launches wrote — launched here, as further workgroups of this launch
+    (gptst_encin_ht1_bwd_jobs), and emptied."""
     B, T, N, F = source.shape
     C = Wbt.shape[-1]
     _chk(dPre, source, mask, w, bi, Wbt, ab, wv, dG)
@@ -370,8 +392,13 @@ def encin_ht1_bwd(dPre, source, mask, fill, w, bi, Wbt, ab, wv, dG=None):
     dWb, dinp = torch.empty(B * T, C * C + C, **f), torch.empty(B * T, 2 * C, **f)
     if dG is None:
         dG = torch.empty(B, N, T, T, **f)
-    _call("gptst_encin_ht1_bwd", _p(dPre), _p(source), F, _p(mask), float(fill), _p(w), _p(bi), _p(Wbt), _p(ab), _p(wv), _p(dWb), _p(dG), _p(dinp),
-          B, T, N, C, nbytes=_nb(dPre, Wbt, dWb, dG))
+    host = (_p(dPre), _p(source), F, _p(mask), float(fill), _p(w), _p(bi), _p(Wbt), _p(ab), _p(wv), _p(dWb), _p(dG), _p(dinp), B, T, N, C)
+    if jobs is not None and jobs.jobs:
+        cols, tag, nb, held = jobs.take_reductions()
+        _call("gptst_encin_ht1_bwd", *host, *cols, tag=tag, nbytes=_nb(dPre, Wbt, dWb, dG) + nb, entry="gptst_encin_ht1_bwd_jobs")
+        del held
+    else:
+        _call("gptst_encin_ht1_bwd", *host, nbytes=_nb(dPre, Wbt, dWb, dG))
     return dWb, dG, dinp
 
 
@@ -930,12 +957,22 @@ def timefeat_jobs_fwd(jobs, tidx):
     return outs
 
 
-def timefeat_jobs_bwd(jobs, tidx):
-    """jobs: [TimefeatJob with grads and dout]; gradients are accumulated; ONE launch."""
-    if not jobs:
+def timefeat_jobs_bwd(tf, tidx, jobs=None):
+    """tf: [TimefeatJob with grads and dout]; gradients are accumulated; ONE launch.
+    jobs: a PoolJobs table of gradient reductions whose inputs earlier launches wrote and which do not touch the time features' tensors —
+    launched here, as further workgroups of this launch (gptst_timefeat_jobs_bwd_jobs), and emptied."""
+    if not tf:
+        if jobs is not None:
+            jobs.launch()
         return
-    _call("gptst_timefeat_jobs", len(jobs), 1, _ptrs([t for j in jobs for t in j.params]), _ptrs([t for j in jobs for t in j.grads]), _p(tidx),
-          _ptrs([j.dout for j in jobs]), _ints([j.rows for j in jobs]), _ints([j.K for j in jobs]), _ints([j.E for j in jobs]))
+    a = (_ptrs([t for j in tf for t in j.params]), _ptrs([t for j in tf for t in j.grads]), _p(tidx),
+         _ptrs([j.dout for j in tf]), _ints([j.rows for j in tf]), _ints([j.K for j in tf]), _ints([j.E for j in tf]))
+    if jobs is not None and jobs.jobs:
+        cols, tag, nb, held = jobs.take_reductions()
+        _call("gptst_timefeat_jobs", len(tf), *a, *cols, tag=tag, nbytes=nb, entry="gptst_timefeat_jobs_bwd_jobs")
+        del held
+    else:
+        _call("gptst_timefeat_jobs", len(tf), 1, *a)
 
 
 # ---- loss / optimiser -------------------------------------------------------------------------------------------

@@ -192,6 +192,7 @@ class PretrainStep:
         gen = engine.gen_all(p, tidx, dims, guide=need_guide, defer=DEFER_GEN)
         red = engine.Reductions()
         red.no_carry = self.deterministic
+        red.want_tail = True                                         # (engine.tail_roles_ok decides per step)
         self._dec_reduced = False
         if self.dp_overlap and self._dp_in_graph():
             red.on_bucket = self._bucket_ready

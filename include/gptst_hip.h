@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 23  /* 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 24  /* 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -138,6 +138,17 @@ int gptst_gram_fwd(const float* A, float* G, int N, int Hm, void* stream);
 /* gram_bwd: A (L*N,Hm,T) of L layers, dG (L, nsplit, N, T, T) PARTIAL graph gradients (e.g. one per sample from gptst_hypertem_bwd),
  * summed in a fixed order -> dA (L*N,Hm,T). */
 int gptst_gram_bwd(const float* A, const float* dG, float* dA, int L, int N, int Hm, int nsplit, void* stream);
+/* TAIL ROLES.  The end of a step's backward is off the data-gradient chain: gptst_encin_ht1_bwd, gptst_gram_bwd and the time-feature backward each run a
+ * small latency-bound grid, and the gradient-reduction launch (gptst_pool_jobs kinds 1 / 2) is bandwidth work that needs no particular CU.  The three
+ * *_jobs entries are the plain entry followed by gptst_pool_jobs(njobs, j...) in ONE launch: the grid is [the entry's workgroups | job blocks], the jobs
+ * heaviest first; no workgroup waits for another.  The caller guarantees that the jobs' inputs were written by EARLIER launches of the stream, and that
+ * the entry neither reads the jobs' outputs nor writes their inputs.  Every table is served: of more than 112 jobs the heaviest 112 ride and the
+ * rest follow through gptst_pool_jobs; an empty table, the deterministic mode and a table with another kind give exactly the two calls.  Same
+ * results as the two calls (kind-2 outputs are float atomics as in gptst_pool_jobs). */
+int gptst_gram_bwd_jobs(const float* A, const float* dG, float* dA, int L, int N, int Hm, int nsplit,
+                        int njobs, const int* jkind, const void* const* jemb, const void* const* jx, const void* const* jpool,
+                        const void* const* jout, const int* jR, const int* jK, const int* jcols, const int* jnsplit, const int* jldx,
+                        void* stream);
 /* out = G (*) X  [+ dOut*lrelu'(Y) when dOut != NULL: fuses the residual branch of hyperTem's backward]. */
 int gptst_tmix(const float* X, const float* G, const float* dOut, const float* Y, float* out, int B, int T, int N, int C,
                void* stream);
@@ -191,6 +202,12 @@ int gptst_encin_ht1_fwd(const float* src, int lda, const float* mask, float fill
 int gptst_encin_ht1_bwd(const float* dPre, const float* src, int lda, const float* mask, float fill, const float* w, const float* bi,
                         const float* Wbt, const float* ab, const float* wv, float* dWb, float* dG, float* dinp, int B, int T, int N, int C,
                         void* stream);
+/* ... carrying a table of gradient-reduction jobs (TAIL ROLES, at gptst_gram_bwd_jobs); C = 128: the two calls */
+int gptst_encin_ht1_bwd_jobs(const float* dPre, const float* src, int lda, const float* mask, float fill, const float* w, const float* bi,
+                             const float* Wbt, const float* ab, const float* wv, float* dWb, float* dG, float* dinp, int B, int T, int N, int C,
+                             int njobs, const int* jkind, const void* const* jemb, const void* const* jx, const void* const* jpool,
+                             const void* const* jout, const int* jR, const int* jK, const int* jcols, const int* jnsplit, const int* jldx,
+                             void* stream);
 
 /* Guide classifier MLP_RL, input projection + node-conditioned layer on the low-rank structure of the input (guidein.hip, r04): for base = 1
  * h1 = LReLU((s w1 + b1) W_n + b_n) = LReLU(s u_n + c_n) with u_n = w1 W_n, c_n = b1 W_n + b_n — an elementwise pass; the backward needs
@@ -603,6 +620,12 @@ int gptst_stats_fold(const float* sws, int rows, float* stats, void* stream);
  * above; grads likewise (bwd != 0 only, +=); io[q]: output (fwd) or output gradient (bwd) of job q; all jobs read one tidx. */
 int gptst_timefeat_jobs(int njobs, int bwd, const void* const* params, const void* const* grads, const float* tidx,
                         const void* const* io, const int* rows, const int* K, const int* E, void* stream);
+/* the backward (bwd = 1) carrying a table of npj gradient-reduction jobs (TAIL ROLES, at gptst_gram_bwd_jobs) */
+int gptst_timefeat_jobs_bwd_jobs(int njobs, const void* const* params, const void* const* grads, const float* tidx, const void* const* io,
+                                 const int* rows, const int* K, const int* E,
+                                 int npj, const int* jkind, const void* const* jemb, const void* const* jx, const void* const* jpool,
+                                 const void* const* jout, const int* jR, const int* jK, const int* jcols, const int* jnsplit, const int* jldx,
+                                 void* stream);
 
 /* start of a step in one launch (stepbegin.hip): zero z0[0..n0) (the [flat gradient | statistics] buffer: optimizer.zero_grad,
  * BasicTrainer.py:79) and z1[0..n1) (the step's zero-initialised scratch; may be NULL), and gather tidx (BT,2) = src[:, 0, base:base+2]
