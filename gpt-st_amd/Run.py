@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -46,7 +46,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -135,16 +135,46 @@ def fusion_matrix(args, data_root, A, loaders, scaler):
     return adj
 
 
+def stgode_graphs(args, pargs, data_root, A, csv_path, train):
+    """STGODE's spatial and semantic graphs (reference model/STGODE/args.py:44-131, 176-177) from ``<data_root>/STGODE/<ds>/<ds>_dtw_distance.npy``
+    and ``_spatial_distance.npy`` when those files exist; otherwise the distances are built and cached there as the reference does: the
+    spatial ones from the dataset's csv by the reference's per-dataset rules — where only an adjacency exists (the synthetic graph) by
+    (1 - adj) 1000 — and the DTW ones between the day-mean profiles of the loaded, z-scored series with the project's exact recurrence (the
+    reference approximates with fastdtw(radius=6)).  The series at hand is the training split where the reference averages the days of
+    the whole series."""
+    from gptst_amd import graph
+    root = os.path.join(data_root, "STGODE", args.dataset)
+    dist = {}
+    for kind in ("dtw", "spatial"):
+        path = os.path.join(root, "%s_%s_distance.npy" % (args.dataset, kind))
+        if os.path.exists(path):
+            dist[kind] = np.load(path)
+            continue
+        print("gpt-st_amd: %s not found -> built from the %s" % (path, "training series" if kind == "dtw" else "adjacency"), flush=True)
+        if kind == "dtw":
+            day = 288 if train.series.shape[0] >= 288 else int(train.series.shape[0])
+            dist[kind] = graph.stgode_dtw_distances(train.series, day_slots=day)
+        else:
+            dist[kind] = (graph.stgode_spatial_distance_csv(csv_path, args.dataset, args.num_nodes) if os.path.exists(csv_path)
+                          else graph.stgode_spatial_distance(A))
+        try:
+            os.makedirs(root, exist_ok=True)
+            np.save(path, dist[kind])
+        except OSError as e:
+            print("gpt-st_amd: the %s distances are not cached (%s)" % (kind, e))
+    return graph.stgode_graphs(dist["spatial"], dist["dtw"], pargs.sigma1, pargs.sigma2, pargs.thres1, pargs.thres2)
+
+
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51 and model/STFGNN/args.py:154-211 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211 and model/STGODE/args.py:10-178 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STSGCN, TGCN
-    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN"):
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN and -model STFGNN (SURVEY.md §8f rank 4)")
+    from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STGODE, STSGCN, TGCN
+    if str(args.model) not in ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE"):
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN and -model STGODE (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -174,6 +204,10 @@ def main_eval(args, dev):
     elif str(args.model) == "STFGNN":                                            # model/Model.py, STFGNN/args.py:192-210: the fusion matrix
         ap = SimpleNamespace(**vars(pargs), adj=fusion_matrix(args, data_root, A, (train, val, test), scaler))
         predictor = STFGNN(ap, dev, args.hidden_dim, backend=str(args.stfgnn_backend))
+    elif str(args.model) == "STGODE":                                            # model/Model.py, STGODE/args.py:176-177: the two normalised graphs
+        sp, se = stgode_graphs(args, pargs, data_root, A, csv_path, train)
+        ap = SimpleNamespace(**vars(pargs), A_sp_wave=sp, A_se_wave=se)
+        predictor = STGODE(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stgode_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

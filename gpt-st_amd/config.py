@@ -84,6 +84,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-stsgcn_backend", default=FINETUNE_DEFAULTS["stsgcn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the STFGNN predictor (predictors/stfgnn_hip.py)
     ap.add_argument("-stfgnn_backend", default=FINETUNE_DEFAULTS["stfgnn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the STGODE predictor (predictors/stgode_hip.py)
+    ap.add_argument("-stgode_backend", default=FINETUNE_DEFAULTS["stgode_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -96,7 +98,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
-                         astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch")
+                         astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch", stgode_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -153,15 +155,20 @@ _STFGNN_KEYS = [("data", "num_nodes", int), ("data", "window", int), ("data", "h
                 ("model", "strides", int), ("model", "temporal_emb", _EVAL), ("model", "spatial_emb", _EVAL), ("model", "use_mask", _EVAL),
                 ("model", "activation", str), ("model", "module_type", str),
                 ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+# reference model/STGODE/args.py:156-171.  `out_channels` is a literal (the widths of a temporal block; the last is a block's output width).
+_STGODE_KEYS = [("data", "num_nodes", int), ("data", "num_timesteps_input", int), ("data", "num_timesteps_output", int),
+                ("model", "sigma1", float), ("model", "sigma2", float), ("model", "thres1", float), ("model", "thres2", float),
+                ("model", "in_channels", int), ("model", "out_channels", _EVAL), ("model", "n_layers", int),
+                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
 _PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS, "STSGCN": _STSGCN_KEYS,
-              "STFGNN": _STFGNN_KEYS}
+              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN and STFGNN are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN and STGODE are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN and STFGNN predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN and STGODE predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)

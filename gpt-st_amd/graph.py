@@ -168,15 +168,16 @@ def _dtw_series(series, dataset, slots, day_slots, train_share, total_steps=None
     return data[:full].reshape(-1, slots, n)[:tr_day]
 
 
-def dtw_distances(x, band=12, chunk=2048):
+def dtw_distances(x, band=12, chunk=2048, normalise=True):
     """x (days, slots, N) -> (N, N) float64, upper triangle: the banded DTW distance of ``compute_dtw`` (args.py:26-57, order 1) between the
     series of nodes i < j.  Every day's row is normalised on its own; the local cost of slots (p of j, q of i) is the sum over the days of
     |a[day, q] - b[day, p]|; the recurrence runs over the band |p - q| <= band, whose edges drop the neighbour outside it.  Vectorised over the
     node pairs (the reference loops over them in Python), ``chunk`` pairs at a time on x's device; the band's cells of one row depend on their
-    left neighbour, so the recurrence itself is a loop of slots * (2 band + 1) steps."""
+    left neighbour, so the recurrence itself is a loop of slots * (2 band + 1) steps.  ``band >= slots - 1`` is the unconstrained, exact DTW;
+    ``normalise=False`` takes the series as they are (STGODE: ``stgode_dtw_distances``)."""
     x = x.double()
     days, T0, n = x.shape
-    z = (x - x.mean(1, keepdim=True)) / x.std(1, unbiased=False, keepdim=True)
+    z = (x - x.mean(1, keepdim=True)) / x.std(1, unbiased=False, keepdim=True) if normalise else x
     z = z.permute(2, 0, 1).contiguous()                                              # (N, days, slots)
     iu, ju = torch.triu_indices(n, n, 1, device=x.device)
     out = torch.zeros(n, n, dtype=torch.float64, device=x.device)
@@ -222,3 +223,77 @@ def dtw_graph(series, dataset="PEMS08", band=12, adj_percent=0.01, train_share=0
     w = np.maximum(w, w.T)
     np.fill_diagonal(w, 1.0)
     return (w, d.cpu().numpy()) if return_distances else w
+
+
+# ---- STGODE: the spatial and the semantic (DTW) graph (reference model/STGODE/args.py:10-144) ---------------------------------------------
+def stgode_normalized_adj(A):
+    """``get_normalized_adj`` (args.py:133-144): 0.4 (I + D^-1/2 A D^-1/2) with D the row sums, floored at 1e-4 -> (N, N) float32 tensor"""
+    A = np.asarray(A, dtype=np.float64)
+    deg = A.sum(1)
+    deg[deg <= 10e-5] = 10e-5
+    dinv = 1.0 / np.sqrt(deg)
+    return torch.from_numpy((0.8 / 2 * (np.eye(A.shape[0]) + dinv[:, None] * A * dinv[None, :])).astype(np.float32))
+
+
+def stgode_adjacencies(sp_dist, dtw_dist, sigma1, sigma2, thres1, thres2):
+    """the thresholding of ``read_data`` (args.py:57-65, 118-125) -> (sp_matrix, dtw_matrix), float64 numpy.  Semantic: the DTW distances
+    z-scored over all entries, exp(-z^2 / sigma1^2), 1 where above thres1 and 0 elsewhere.  Spatial: the distances z-scored over their
+    finite entries, exp(-z^2 / sigma2^2) (0 at an infinite distance), kept where at least thres2."""
+    d = np.asarray(dtw_dist, dtype=np.float64)
+    d = (d - d.mean()) / d.std()
+    dtw = (np.exp(-d ** 2 / sigma1 ** 2) > thres1).astype(np.float64)
+    s = np.asarray(sp_dist, dtype=np.float64)
+    fin = s[s != np.inf]
+    s = (s - fin.mean()) / fin.std()
+    sp = np.exp(-s ** 2 / sigma2 ** 2)
+    sp[sp < thres2] = 0
+    return sp, dtw
+
+
+def stgode_graphs(sp_dist, dtw_dist, sigma1, sigma2, thres1, thres2):
+    """(A_sp_wave, A_se_wave) of reference args.py:176-177: ``stgode_normalized_adj`` of the two thresholded matrices"""
+    sp, dtw = stgode_adjacencies(sp_dist, dtw_dist, sigma1, sigma2, thres1, thres2)
+    return stgode_normalized_adj(sp), stgode_normalized_adj(dtw)
+
+
+def stgode_spatial_distance(A):
+    """the spatial distances where only an adjacency exists — the reference's rule for the NYC sets (args.py:92-94), used for the synthetic
+    graph too: (1 - adj) 1000"""
+    return (1.0 - np.asarray(A, dtype=np.float32)) * 1000
+
+
+def stgode_spatial_distance_csv(path, dataset, num_nodes):
+    """the spatial distances from the dataset's csv by the reference's per-dataset rules (args.py:82-108): a matrix file read as it is
+    (METR_LA, PEMS07M), a 0/1 matrix turned into 1000 / 5 (SZ_TAXI) or (1 - adj) 1000 (the NYC sets), else rows ``from,to,distance`` under a
+    header, entered symmetrically into a matrix of infinities"""
+    if dataset in ("PEMS07M", "METR_LA", "SZ_TAXI", "NYC_TAXI", "NYC_BIKE"):
+        m = np.loadtxt(path, delimiter=",", dtype=np.float64, ndmin=2)
+        if dataset == "SZ_TAXI":
+            m = np.where(m == 0, 1000.0, np.where(m == 1, 5.0, m)).astype(np.float32)
+        elif dataset in ("NYC_TAXI", "NYC_BIKE"):
+            m = stgode_spatial_distance(m)
+        return m
+    d = np.full((num_nodes, num_nodes), np.inf)
+    with open(path) as f:
+        f.readline()
+        for row in csv.reader(f):
+            if len(row) >= 3:
+                i, j = int(row[0]), int(row[1])
+                d[i, j] = d[j, i] = float(row[2])
+    return d
+
+
+def stgode_dtw_distances(series, day_slots=288, chunk=16384):
+    """(N, N) float64 symmetric: the DTW distance (local cost |a - b|) between the day-mean profiles of every two nodes (args.py:45-54).
+    ``series`` (L, N[, F]) as the reference has it there, z-scored; the first channel, whole days of ``day_slots``.  The recurrence is the
+    project's own (``dtw_distances`` with the band opened to the whole day and no per-row normalisation): the exact distance, where the
+    reference's ``fastdtw(radius=6)`` approximates it."""
+    data = torch.as_tensor(series)
+    if data.dim() == 3:
+        data = data[:, :, 0]
+    days = data.shape[0] // day_slots
+    if days < 1:
+        raise ValueError("the series has %d steps: not one whole day of %d slots" % (data.shape[0], day_slots))
+    prof = data[:days * day_slots].double().reshape(days, day_slots, -1).mean(0)
+    d = dtw_distances(prof[None], band=day_slots, chunk=chunk, normalise=False)
+    return (d + d.t()).cpu().numpy()

@@ -1472,3 +1472,78 @@ def stfgnn_mix(Sp, Dp, In, mode, B, T, N):
     Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
     _call("gptst_stfgnn_mix", _p(Sp), _p(Dp), Sp.shape[0], _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
     return Out
+
+
+# ---- the downstream STGODE predictor (csrc/stgode.hip) ----------------------------------------------------------------------------------
+# rows (B T N, c), channels last.  A block is BN_nodes(relu(step(relu(X)))); the batch norm's channel is the node.
+def stgode_step(Lp, In, W, M, B, T, N, coef, oscale=None, sscale=None, mask=None, relu_in=False, relu_out=False, keep_at=False):
+    """Out[n] = cn oscale[n] (L (sscale . src))[n] + cw src[n] W + sum_k (ct M[tau][k] + [k = tau] cs) src[b, k, n], src = In or relu(In); coef =
+    (cn, cw, ct, cs); Lp (Np, Np) zero-padded; then relu (relu_out) and the mask [mask > 0].  keep_at: -> (Out, AT), AT the bare node product"""
+    _chk(Lp, In, W, M, oscale, sscale, mask)
+    c = In.shape[1]
+    assert In.shape[0] == B * T * N and tuple(W.shape) == (c, c) and tuple(M.shape) == (T, T) and Lp.dim() == 2, (In.shape, W.shape, M.shape, B, T, N)
+    Out = torch.empty_like(In)
+    AT = torch.empty_like(In) if keep_at else None
+    _call("gptst_stgode_step", _p(Lp), Lp.shape[0], _p(In), _p(Out), _p(AT), _p(W), _p(M), _p(oscale), _p(sscale), _p(mask),
+          *(ctypes.c_float(float(v)) for v in coef), int(relu_in), int(relu_out), c, B, T, N, tag="c%d T%d r%d" % (c, T, int(relu_in)),
+          nbytes=_nb(In, Out, AT, mask))
+    return (Out, AT) if keep_at else Out
+
+
+def stgode_wgrad(G, X):
+    """-> (c, c) = relu(X)^T G: row-split partials summed in a fixed order"""
+    _chk(G, X)
+    rows, c = G.shape
+    ns = _C.lib().value("gptst_stgode_wgrad_nsplit", rows, c)
+    part = torch.empty(ns, c, c, device=G.device, dtype=torch.float32)
+    _call("gptst_stgode_wgrad", _p(G), _p(X), c, _p(part), ns, rows, tag="c%d" % c, nbytes=_nb(G, X, part))
+    return part.sum(0).t()
+
+
+def stgode_reduce(G, X, AT, B, T, N):
+    """-> ((T, T) = sum_{b, n, c} relu(X)[b, k, n, c] G[b, m, n, c], (N) = sum_{b, tau, c} G AT): partials per (b, node chunk) summed in a fixed order"""
+    _chk(G, X, AT)
+    c = G.shape[1]
+    nparts = _C.lib().value("gptst_stgode_reduce_nparts", c, T, N)
+    part2 = torch.empty(B * nparts, T, T, device=G.device, dtype=torch.float32)
+    parta = torch.empty(B, N, device=G.device, dtype=torch.float32)
+    _call("gptst_stgode_reduce", _p(G), _p(X), _p(AT), _p(part2), _p(parta), c, B, T, N, tag="c%d T%d" % (c, T), nbytes=_nb(G, X, AT))
+    return part2.sum(0), parta.sum(0)
+
+
+def stgode_bn_stats(Z, B, T, N):
+    """-> part (N, nsplit, 2): (mean, sum of squared deviations from it) of each split of a node's B T rows"""
+    _chk(Z)
+    ns = _C.lib().value("gptst_stgode_bn_nsplit", B * T)
+    part = torch.empty(N, ns, 2, device=Z.device, dtype=torch.float32)
+    _call("gptst_stgode_bn_stats", _p(Z), _p(part), ns, Z.shape[1], B, T, N, tag="c%d" % Z.shape[1], nbytes=_nb(Z))
+    return part
+
+
+def stgode_bn_apply(Z, part, gamma, beta, rmean, rvar, training, momentum, eps, B, T, N, keep=False, best=None, which=None, idx=0, want_y=True):
+    """batch norm over the node channel from the split statistics (part None: from the running ones) -> (Y | None, mean | None, rstd | None).
+    training: rmean / rvar are updated in place.  best / which: the running max over the branches, branch ``idx``"""
+    _chk(Z, part, gamma, beta, rmean, rvar, best)
+    ns = _C.lib().value("gptst_stgode_bn_nsplit", B * T)
+    assert part is None or tuple(part.shape) == (N, ns, 2)
+    assert which is None or (which.dtype == torch.int32 and which.is_contiguous() and which.shape == Z.shape)
+    Y = torch.empty_like(Z) if want_y else None
+    mean, rstd = (torch.empty(N, device=Z.device, dtype=torch.float32) for _ in range(2)) if keep else (None, None)
+    _call("gptst_stgode_bn_apply", _p(Z), _p(part), ns, _p(gamma), _p(beta), _p(rmean), _p(rvar), int(training), ctypes.c_float(float(momentum)),
+          ctypes.c_float(float(eps)), _p(Y), _p(mean), _p(rstd), _p(best), _p(which), idx, Z.shape[1], B, T, N,
+          tag="c%d m%d" % (Z.shape[1], int(best is not None)), nbytes=_nb(Z, Y, best))
+    return Y, mean, rstd
+
+
+def stgode_bn_bwd(dY, Z, gamma, mean, rstd, B, T, N, dBest=None, which=None, idx=0):
+    """-> (G = [Z > 0] dZ of the batch norm over the node channel, dgamma (N), dbeta (N)); dY None: the upstream gradient is dBest where
+    which == idx.  Two launches: the per-node sums as split partials, then the apply"""
+    _chk(dY, Z, gamma, mean, rstd, dBest)
+    ns = _C.lib().value("gptst_stgode_bn_nsplit", B * T)
+    part = torch.empty(N, ns, 2, device=Z.device, dtype=torch.float32)
+    G = torch.empty_like(Z)
+    dg, db = (torch.empty(N, device=Z.device, dtype=torch.float32) for _ in range(2))
+    for stage in (0, 1):
+        _call("gptst_stgode_bn_bwd", _p(dY), _p(dBest), _p(which), idx, _p(Z), _p(gamma), _p(mean), _p(rstd), _p(part), ns, _p(G), _p(dg), _p(db),
+              Z.shape[1], B, T, N, stage, tag="c%d s%d" % (Z.shape[1], stage), nbytes=_nb(Z, dY, dBest) + (stage and _nb(G)))
+    return G, dg, db

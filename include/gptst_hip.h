@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 24  /* 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 25  /* 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -578,6 +578,40 @@ int gptst_stsgcn_winwgrad(const float* D, int cw, const float* X, int ci, float*
  * The GEMM grouped by window, its gate backward and weight gradient are gptst_stsgcn_wingemm / _gate_bwd / _winwgrad with R = 4N; the gated
  * temporal branch is gptst_mtgnn_tapgemm (gated, offsets 0 and 3) with gptst_mtgnn_gate_bwd / gptst_mtgnn_wgrad. */
 int gptst_stfgnn_mix(const float* S, const float* D, int Np, const float* In, float* Out, int c, int mode, int B, int T, int N, void* stream);
+
+/* ---- the downstream STGODE predictor (stgode.hip; reference model/STGODE/STGODE.py, odegcn.py, gpt-st_amd/predictors/stgode_hip.py) ----------
+ * Rows (b, t, n) x c, c a multiple of 16 up to 128, T <= 32, graphs zero-padded to Np = 16 ceil(N / 16) <= 448 (GPTST_ESHAPE beyond, nothing
+ * written).  A block is BN_nodes(relu(step(relu(X)))).
+ * step: with src = In (relu_in: relu(In)), per (b, tau) and node n
+ *     Out[n, :] = cn oscale[n] (L (sscale . src))[n, :] + cw src[n, :] W + sum_k (ct M[tau][k] + [k = tau] cs) src[b, k, n, :]
+ *   then relu (relu_out) and the mask [mask > 0] (mask NULL: none).  oscale, sscale (N) may be NULL (1); AT (rows, c; may be NULL) takes the
+ *   bare node product L (sscale . src).  W (c, c), M (T, T) row-major.  In != Out.  Forward: L = A, oscale = sigmoid(alpha), M = W2^T,
+ *   (cn, cw, ct, cs) = (3, 6, 6, -11); backward: L = A^T, sscale = sigmoid(alpha), W^T, M = W2, cs = -17, mask = the block's input.
+ * wgrad: part (nsplit, c, c) = row-split partials of G^T relu(X); nsplit = gptst_stgode_wgrad_nsplit(rows, c); the caller sums the splits.
+ * reduce: part2 (B * nparts, T, T) = partials of sum_{n, c} relu(X)[b, k, n, c] G[b, m, n, c], parta (B, N) = sum_{tau, c} G AT per (b, n);
+ *   nparts = gptst_stgode_reduce_nparts(c, T, N); the caller sums over the first axis.
+ * bn_stats: part (N, nsplit, 2) = (mean, sum of squared deviations from it) of each split of the B T rows of a node; nsplit =
+ *   gptst_stgode_bn_nsplit(B T).  bn_apply: folds the splits (Chan, in double, index order) — part NULL: the running statistics instead —
+ *   and writes Y = (Z - mean) rstd gamma + beta (Y may be NULL when best is given); training != 0 with part: rmean / rvar updated as torch
+ *   does (momentum, unbiased variance); save_mean / save_rstd (N; may be NULL) for the backward.  best (rows, c; may be NULL): the running
+ *   max over the branches — idx = 0 writes, a later idx replaces where strictly greater — and which (int32; may be NULL) the branch that holds it.
+ * bn_bwd: dy = dY, or (dY NULL) dBest where which == idx.  stage 0: part (N, nsplit, 2) = split sums of dy and dy xhat; stage 1: G = [Z > 0]
+ *   gamma rstd (dy - mean(dy) - xhat mean(dy xhat)) — the batch norm's backward and the mask of the step's relu — and dgamma, dbeta (N). */
+int gptst_stgode_step(const float* L, int Np, const float* In, float* Out, float* AT, const float* W, const float* M, const float* oscale,
+                      const float* sscale, const float* mask, float cn, float cw, float ct, float cs, int relu_in, int relu_out, int c, int B,
+                      int T, int N, void* stream);
+int gptst_stgode_wgrad_nsplit(int rows, int c);
+int gptst_stgode_wgrad(const float* G, const float* X, int c, float* part, int nsplit, int rows, void* stream);
+int gptst_stgode_reduce_nparts(int c, int T, int N);
+int gptst_stgode_reduce(const float* G, const float* X, const float* AT, float* part2, float* parta, int c, int B, int T, int N, void* stream);
+int gptst_stgode_bn_nsplit(int R);
+int gptst_stgode_bn_stats(const float* Z, float* part, int nsplit, int c, int B, int T, int N, void* stream);
+int gptst_stgode_bn_apply(const float* Z, const float* part, int nsplit, const float* gamma, const float* beta, float* rmean, float* rvar,
+                          int training, float momentum, float eps, float* Y, float* save_mean, float* save_rstd, float* best, int* which, int idx,
+                          int c, int B, int T, int N, void* stream);
+int gptst_stgode_bn_bwd(const float* dY, const float* dBest, const int* which, int idx, const float* Z, const float* gamma, const float* mean,
+                        const float* rstd, float* part, int nsplit, float* G, float* dgamma, float* dbeta, int c, int B, int T, int N, int stage,
+                        void* stream);
 
 int gptst_rowouter_ws_floats(int J, int C);   /* scratch (ws) size of gptst_rowouter */
 /* first stage of gptst_rowouter alone: part (gptst_rowouter_nparts(rows), J*C + C + J) = row-chunk partials [sum a'^T X (j,c) | column

@@ -1,0 +1,394 @@
+"""The STGODE predictor on HIP (csrc/stgode.hip, predictors/stgode_hip.py) against fp64 torch on the CPU.  The reference of every launch is its
+definition in tests/stgode_util.py, which tests/test_stgode_hip_cpu.py holds to autograd on the module at 1e-10.  The backward kernels are fed
+the REFERENCE's z, X and winner index cast to fp32, so a kernel-level gradient has no decision of its own to get wrong.  The error measure and
+its bound are the project's (downstream_util: largest absolute error over the reference's largest magnitude, below 1e-4).
+
+Shapes: N 20 (padding to a tile), 33 (one row in the last tile), 170 / 207 / 250 / 266 (the shipped tilings, at B 1, T 2), 448 (the bound; 449
+is refused); T 1, 5, 12; B 1, 3; C 16, 64.  No kernel caps its grid, but a batch-norm workgroup walks its split of a node's rows 256 float4
+at a time: at (B, T, C) = (3, 12, 64) a node has 36 rows in 2 splits of 18 rows = 288 float4, so that loop runs twice."""
+import copy
+import logging
+from types import SimpleNamespace
+
+import pytest
+import torch
+
+import stgode_util as gu
+from gptst_amd import _C, ops, synth
+from gptst_amd.config import make_args, predictor_args
+from gptst_amd.predictors import STGODE, stgode_hip as H
+from downstream_util import TOL, _check, _err
+from oracle import gptst_oracle as O
+
+pytestmark = pytest.mark.gpu
+DEV = torch.device("cuda")
+GAP = gu.GAP
+
+
+def _d(t):
+    return t.float().to(DEV).contiguous()
+
+
+def _pad(A):
+    n = A.shape[0]
+    p = torch.zeros(H.pad16(n), H.pad16(n), dtype=torch.float64)
+    p[:n, :n] = A
+    return _d(p), _d(p.t())
+
+
+def _step_case(B, T, N, C, seed=0):
+    g = torch.Generator().manual_seed(seed)
+    A = gu.graphs(N)[0].double()                                             # non-symmetric
+    X = torch.randn(B, T, N, C, dtype=torch.float64, generator=g)
+    alpha = torch.rand(N, dtype=torch.float64, generator=g) * 0.8 + 0.1     # differs per node
+    W = torch.randn(C, C, dtype=torch.float64, generator=g) * (0.5 / C ** 0.5)
+    W2 = torch.randn(T, T, dtype=torch.float64, generator=g) * 0.3
+    dz = torch.randn(B, T, N, C, dtype=torch.float64, generator=g)
+    return A, X, alpha, W, W2, dz
+
+
+# ---- 1. the launches against their definitions ---------------------------------------------------------------------------------------------
+STEP_CASES = [(3, 5, 20, 16), (1, 12, 33, 64), (3, 1, 20, 64), (1, 2, 170, 64), (1, 2, 207, 64), (1, 2, 250, 64), (1, 2, 266, 64), (1, 1, 448, 16)]
+
+
+@pytest.mark.parametrize("B,T,N,C", STEP_CASES)
+def test_step_forward_backward_and_reductions(B, T, N, C, parity):
+    A, X, alpha, W, W2, dz = _step_case(B, T, N, C)
+    z, At, _ = gu.step_fwd(X, A, alpha, W, W2)
+    g = dz * (z > 0)
+    want = {"z": z, "At": At, "dX": gu.step_bwd(g, X, A, alpha, W, W2)}
+    want["dalpha"], want["dW"], want["dW2"] = gu.step_param_grads(g, X, At)
+    assert 0.1 < float((z > 0).double().mean()) < 0.9 and (A - A.t()).abs().max() > 1e-2
+    Lp, Lpt = _pad(A)
+    Xd, gd, ad, Wd, W2d = _d(X.reshape(-1, C)), _d(g.reshape(-1, C)), _d(alpha), _d(W), _d(W2)
+
+    def run():
+        zz, at = ops.stgode_step(Lp, Xd, Wd, _d(W2.t()), B, T, N, H.FWD, oscale=ad, relu_in=True, relu_out=True, keep_at=True)
+        z0 = ops.stgode_step(Lp, Xd, Wd, _d(W2.t()), B, T, N, H.FWD, oscale=ad, relu_in=True, relu_out=True)
+        assert torch.equal(z0, zz)                                           # keeping A t does not change the step
+        d2, da = ops.stgode_reduce(gd, Xd, _d(At.reshape(-1, C)), B, T, N)
+        return {"z": zz, "At": at, "dX": ops.stgode_step(Lpt, gd, _d(W.t()), W2d, B, T, N, H.BWD, sscale=ad, mask=Xd), "dalpha": 3 * da,
+                "dW": 6 * ops.stgode_wgrad(gd, Xd), "dW2": 6 * d2}
+    got, again = run(), run()
+    for k in want:
+        assert torch.equal(got[k], again[k]), k                              # no float atomics: two runs are bit-equal
+    _check(parity, {k: _err(got[k].view(want[k].shape), want[k]) for k in want})
+    # a transposed graph or alpha on the output side in the backward must not pass: on the reference alone, the mixed-up form is off by more
+    # than ten times TOL (row-normalised graphs of more nodes average more and tell less: 2.6e-3 at 448), which no error within TOL can hide
+    wrong = 3 * alpha[:, None] * torch.einsum("ji,btjc->btic", A, g) + 6 * (g @ W.t()) + 6 * torch.einsum("km,bmnc->bknc", W2, g) - 17 * g
+    assert _err(wrong * (X > 0), want["dX"]) > 10 * TOL
+
+
+def test_step_refuses_more_nodes_than_its_slab_holds():
+    """449 nodes are 29 node tiles, one more than the 64 KB slab holds: the launch answers ESHAPE and writes nothing; the predictor does not
+    claim the shape"""
+    N, C, T = 449, 16, 1
+    Lp = torch.zeros(464, 464, device=DEV)
+    X, W, M = torch.randn(T * N, C, device=DEV), torch.eye(C, device=DEV), torch.eye(T, device=DEV)
+    out = torch.full_like(X, 7.0)
+    rc = _C.lib().value("gptst_stgode_step", Lp.data_ptr(), 464, X.data_ptr(), out.data_ptr(), None, W.data_ptr(), M.data_ptr(), None, None, None,
+                        3.0, 6.0, 6.0, -11.0, 1, 1, C, 1, T, N, _C.stream())
+    torch.cuda.synchronize()
+    assert rc == _C.ESHAPE and bool((out == 7.0).all())
+    with pytest.raises(_C.GptstError) as e:
+        ops.stgode_step(Lp, X, W, M, 1, T, N, H.FWD)
+    assert e.value.code == _C.ESHAPE
+    rc = _C.lib().value("gptst_stgode_step", Lp.data_ptr(), 464, X.data_ptr(), out.data_ptr(), None, W.data_ptr(), M.data_ptr(), None, None, None,
+                        3.0, 6.0, 6.0, -11.0, 1, 1, C, 1, 33, N, _C.stream())       # T past the row of M in LDS
+    assert rc == _C.ESHAPE
+
+
+BN_CASES = [(3, 12, 20, 64), (1, 5, 33, 16), (3, 1, 20, 16), (1, 2, 170, 64)]
+
+
+@pytest.mark.parametrize("B,T,N,C", BN_CASES)
+def test_batch_norm_kernels(B, T, N, C, parity):
+    g = torch.Generator().manual_seed(1)
+    z = torch.relu(torch.randn(B, T, N, C, dtype=torch.float64, generator=g) + 0.3)
+    gamma, beta = torch.rand(N, dtype=torch.float64, generator=g) + 0.5, torch.randn(N, dtype=torch.float64, generator=g)
+    rm0, rv0 = torch.randn(N, dtype=torch.float64, generator=g), torch.rand(N, dtype=torch.float64, generator=g) + 0.5
+    dy = torch.randn(B, T, N, C, dtype=torch.float64, generator=g)
+    y, mean, var, varu = gu.bn_fwd(z, gamma, beta)
+    dz, dgam, dbet = gu.bn_bwd(dy, z, gamma, mean, var)
+    want = {"y": y, "mean": mean, "rstd": 1 / torch.sqrt(var + 1e-5), "rmean": 0.9 * rm0 + 0.1 * mean, "rvar": 0.9 * rv0 + 0.1 * varu,
+            "y_eval": gu.bn_eval(z, gamma, beta, rm0, rv0), "g": dz * (z > 0), "dgamma": dgam, "dbeta": dbet}
+    zd, gd, bd, dyd = _d(z.reshape(-1, C)), _d(gamma), _d(beta), _d(dy.reshape(-1, C))
+
+    def run():
+        rm, rv = _d(rm0), _d(rv0)
+        ye, _, _ = ops.stgode_bn_apply(zd, None, gd, bd, rm, rv, False, 0.1, 1e-5, B, T, N)
+        assert torch.equal(rm, _d(rm0)) and torch.equal(rv, _d(rv0))        # eval mode leaves the buffers alone
+        yy, mm, rr = ops.stgode_bn_apply(zd, ops.stgode_bn_stats(zd, B, T, N), gd, bd, rm, rv, True, 0.1, 1e-5, B, T, N, keep=True)
+        G, dg, db = ops.stgode_bn_bwd(dyd, zd, gd, _d(mean), _d(want["rstd"]), B, T, N)
+        return {"y": yy, "mean": mm, "rstd": rr, "rmean": rm, "rvar": rv, "y_eval": ye, "g": G, "dgamma": dg, "dbeta": db}
+    got, again = run(), run()
+    for k in want:
+        assert torch.equal(got[k], again[k]), k
+    _check(parity, {k: _err(got[k].view(want[k].shape), want[k]) for k in want})
+
+
+def test_batch_norm_statistics_do_not_cancel(parity):
+    """z = 100 + randn: the fp32 sum of squares minus the squared mean loses the variance (1 against 1e4 at 24 bits: an error of 1e-3 and more);
+    the two-pass splits folded by Chan's update keep it to 1e-5 relative.  And a node that is all zero after the relu: variance 0, eps decides"""
+    B, T, N, C = 3, 12, 20, 64
+    g = torch.Generator().manual_seed(2)
+    z = (100 + torch.randn(B, T, N, C, generator=g)).double()             # fp32 values: the statistics of exactly what the kernel reads
+    z[:, :, 3] = 0
+    gamma, beta = torch.ones(N, dtype=torch.float64), torch.full((N,), 0.25, dtype=torch.float64)
+    y, mean, var, _ = gu.bn_fwd(z, gamma, beta)
+    zd = _d(z.reshape(-1, C))
+    rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
+    yy, mm, rr = ops.stgode_bn_apply(zd, ops.stgode_bn_stats(zd, B, T, N), _d(gamma), _d(beta), rm, rv, True, 0.1, 1e-5, B, T, N, keep=True)
+    var_got = 1 / rr.double().cpu() ** 2 - 1e-5
+    live = torch.arange(N) != 3
+    rel = float(((var_got - var).abs() / var.clamp_min(1e-30))[live].max())
+    naive = z.float().pow(2).mean((0, 1, 3)) - z.float().mean((0, 1, 3)).pow(2)
+    parity("var_rel", rel)
+    print("relative error of the variance: %.2e (fp32 E[x^2] - E[x]^2 here: %.2e)" % (rel, float(((naive.double() - var).abs() / var.clamp_min(1e-30))[live].max())))
+    assert rel < 1e-5
+    assert float(mm[3]) == 0.0 and abs(float(rr[3]) - 1e-5 ** -0.5) < 1e-2 and bool((yy.view(B, T, N, C)[:, :, 3] == 0.25).all())
+    assert abs(float(rv[3]) - 0.9) < 1e-6 and abs(float(rm[3])) == 0.0
+    _check(parity, {"y": _err(yy.view(y.shape), y)})
+
+
+def test_running_max_ties_and_routing(parity):
+    B, T, N, C = 3, 5, 20, 16
+    g = torch.Generator().manual_seed(3)
+    zs = [torch.relu(torch.randn(B, T, N, C, dtype=torch.float64, generator=g)) for _ in range(3)]
+    gamma, beta = torch.rand(N, dtype=torch.float64, generator=g) + 0.5, torch.randn(N, dtype=torch.float64, generator=g)
+    dB = torch.randn(B, T, N, C, dtype=torch.float64, generator=g)
+    gd, bd = _d(gamma), _d(beta)
+
+    def fold(zlist):
+        best, which = torch.empty(B * T * N, C, device=DEV), torch.empty(B * T * N, C, device=DEV, dtype=torch.int32)
+        stats = []
+        for i, z in enumerate(zlist):
+            zd = _d(z.reshape(-1, C))
+            rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
+            y, m, r = ops.stgode_bn_apply(zd, ops.stgode_bn_stats(zd, B, T, N), gd, bd, rm, rv, True, 0.1, 1e-5, B, T, N, keep=True, best=best, which=which,
+                                          idx=i, want_y=False)
+            assert y is None
+            stats.append((zd, m, r))
+        return best, which, stats
+    # bit-identical branches: index 0 holds every element, and the backward goes there alone
+    best, which, stats = fold([zs[0]] * 3)
+    assert int(which.abs().max()) == 0
+    for i, (zd, m, r) in enumerate(stats):
+        G, dg, db = ops.stgode_bn_bwd(None, zd, gd, m, r, B, T, N, dBest=_d(dB.reshape(-1, C)), which=which, idx=i)
+        assert bool(G.any()) == (i == 0) and bool(dg.any()) == (i == 0) and bool(db.any()) == (i == 0)
+    # distinct branches: the reference's index, its max, and the routed backward of each branch
+    ys = [gu.bn_fwd(z, gamma, beta) for z in zs]
+    wbest, wwhich = gu.running_max([y[0] for y in ys])
+    best, which, stats = fold(zs)
+    best2, which2, _ = fold(zs)
+    assert torch.equal(best, best2) and torch.equal(which, which2)
+    assert torch.equal(which.cpu().view(wwhich.shape), wwhich) and set(wwhich.unique().tolist()) == {0, 1, 2}
+    errs = {"best": _err(best.view(wbest.shape), wbest)}
+    wd = wwhich.to(DEV).view(-1, C).contiguous()
+    for i, (zd, _, _) in enumerate(stats):
+        dz, dgam, dbet = gu.bn_bwd(dB * (wwhich == i), zs[i], gamma, ys[i][1], ys[i][2])
+        G, dg, db = ops.stgode_bn_bwd(None, zd, gd, _d(ys[i][1]), _d(1 / torch.sqrt(ys[i][2] + 1e-5)), B, T, N, dBest=_d(dB.reshape(-1, C)), which=wd, idx=i)
+        errs.update({"g%d" % i: _err(G.view(dz.shape), dz * (zs[i] > 0)), "dgamma%d" % i: _err(dg, dgam), "dbeta%d" % i: _err(db, dbet)})
+    _check(parity, errs)
+
+
+# ---- 2. the whole model ----------------------------------------------------------------------------------------------------------------------
+def _ref(N, T, n_layers, dim_out=1, seed=0, B=1, ap=None, P=3):
+    """(fp64 torch module on the CPU under the xavier-style redraw, x, w)"""
+    torch.manual_seed(seed)
+    m64 = STGODE(gu.model_args(N, T=T, P=P, n_layers=n_layers) if ap is None else ap, "cpu", 64, dim_out)
+    gu.xavier_redraw_(m64)
+    m64 = m64.double().train()
+    x = torch.randn(B, T, N, 64, dtype=torch.float64)
+    return m64, x, torch.randn(B, m64.horizon, N, dim_out, dtype=torch.float64)
+
+
+def _pair(*a, **kw):
+    m64, x, w = _ref(*a, **kw)
+    mh = copy.deepcopy(m64).float().to(DEV)
+    mh.backend = "hip"
+    return m64, mh.train(), x, w
+
+
+def _run(m, x, w):
+    m.zero_grad(set_to_none=True)
+    xi = x.clone().requires_grad_(True)
+    y = m(xi)
+    (y * w).sum().backward()
+    out = {"y": y.detach(), "dx": xi.grad}
+    out.update({k: p.grad.clone() for k, p in m.named_parameters() if p.grad is not None})
+    return out
+
+
+# (dim_out, seed) for which the fp64 reference is unambiguous: no max gap <= g, no step pre-activation and no block input within g of zero, g =
+# 1e-5 of the largest magnitude.  Searched on the CPU over the seeds 0 .. 39 of this shape (n_layers 1, B 1, N 20, T 4:
+# 5120 elements per block, 4 blocks): `_ref(20, 4, 1, dim_out, seed)` then `gu.unambiguous(gu.model_manual(m64, x), x)`; one seed in five to ten
+# comes out clean here: (0, 0, 0) for dim_out 1 at the seeds 8, 15, 26, 34, for dim_out 2 at 3, 7, 19, 21, 24, 33, 36; the first are taken.  The
+# test asserts the condition on the reference alone, before anything runs on the GPU.
+SMALL = [(1, 8), (2, 3)]
+
+
+@pytest.mark.parametrize("dim_out,seed", SMALL)
+def test_small_model_against_fp64_torch(dim_out, seed, parity):
+    m64, mh, x, w = _pair(20, 4, 1, dim_out, seed)
+    res = gu.model_manual(m64, x)
+    assert gu.unambiguous(res, x) == (0, 0, 0)
+    for bn in (b.batch_norm for s, _ in m64.branches() for b in s):
+        assert int(bn.num_batches_tracked) == 0                              # (model_manual ran no module)
+    want = _run(m64, x, w)
+    got = _run(mh, _d(x), _d(w))
+    assert m64.backend_used == "torch" and mh.backend_used == "hip" and set(got) == set(want) and len(want) == 4 * 7 + 4 + 2      # 4 blocks x (5 ode + 2 bn), the heads, y and dx
+    assert all(float(v.abs().max()) > 0 for v in want.values())
+    dead = [k for k, p in mh.named_parameters() if gu.is_dead(k)]
+    assert len(dead) == 48 and all(p.grad is None for k, p in mh.named_parameters() if gu.is_dead(k))
+    # the forward candidate error: the HIP trunk's max against the reference's, over the largest candidate magnitude, has to stay below g / 4
+    with torch.no_grad():
+        best = H.trunk(copy.deepcopy(mh), _d(x), keep=False)                 # (a copy: a training-mode forward moves the buffers)
+    cand = float((best.double().cpu().view(res["best"].shape) - res["best"]).abs().max()) / float(torch.stack(res["outs"]).abs().max())
+    parity("candidate", cand)
+    print("forward candidate error %.2e (g / 4 = %.2e)" % (cand, GAP / 4))
+    assert cand < GAP / 4
+    sd64, sdh = m64.state_dict(), mh.state_dict()
+    errs = {k: _err(got[k], want[k]) for k in want}
+    errs.update({"buf." + k: _err(sdh[k], sd64[k]) for k in sd64 if "running_" in k})
+    assert all(int(sdh[k]) == int(sd64[k]) == 1 for k in sd64 if "num_batches" in k)
+    _check(parity, errs)
+
+
+@pytest.mark.parametrize("ds", ["PEMS08", "METR_LA", "NYC_BIKE", "NYC_TAXI"])
+def test_shipped_configuration_forward_against_fp64_torch(ds, parity):
+    """the predictor as ``-mode eval -model STGODE`` builds it from the dataset's argument set, one batch element: the forward within TOL of
+    fp64 (it is continuous: a near-tie moves a value by less than its gap), the no-grad forward bit-equal to the training one, and one
+    backward whose gradients are finite, of the parameters' shapes and non-zero, with none for the dead convolutions"""
+    pa = predictor_args(ds, "STGODE")
+    N, dim_out = pa.num_nodes, make_args(ds).output_dim
+    sp, se = gu.graphs(N)
+    m64, mh, x, w = _pair(N, 12, None, dim_out, seed=pa.seed, B=1, ap=SimpleNamespace(**vars(pa), A_sp_wave=sp, A_se_wave=se))
+    assert len(m64.state_dict()) == 316 and m64.horizon == 12
+    with torch.no_grad():
+        want = m64(x)
+    xd = _d(x).requires_grad_(True)
+    with torch.no_grad():
+        y0 = mh(xd)
+    assert mh.backend_used == "hip" and y0.grad_fn is None
+    for bn in (b.batch_norm for s, _ in mh.branches() for b in s):           # the same batch again: put the buffers back
+        bn.reset_running_stats()
+    y = mh(xd)
+    assert mh.backend_used == "hip" and y.shape == (1, 12, N, dim_out) and torch.equal(y0, y)
+    (y * _d(w)).sum().backward()
+    torch.cuda.synchronize()
+    for k, p in mh.named_parameters():
+        if gu.is_dead(k):
+            assert p.grad is None, k
+        else:
+            assert p.grad is not None and p.grad.shape == p.shape and bool(torch.isfinite(p.grad).all()) and bool(p.grad.any()), k
+    assert xd.grad.shape == xd.shape and bool(torch.isfinite(xd.grad).all()) and float(xd.grad.abs().max()) > 0
+    _check(parity, {"y": _err(y, want)})
+
+
+# ---- 3. launch count and fallbacks -------------------------------------------------------------------------------------------------------------
+def test_launches_per_block_do_not_grow_with_the_frames(monkeypatch):
+    """3 launches per block forward (step, statistics, apply) and 5 backward (ops.stgode_bn_bwd is two: the sums, the apply), at T = 4 as at 12"""
+    counts = {}
+    for name in [n for n in dir(ops) if n.startswith("stgode_")]:
+        def wrap(*a, _f=getattr(ops, name), _n=name, **kw):
+            counts[_n] = counts.get(_n, 0) + 1
+            return _f(*a, **kw)
+        monkeypatch.setattr(ops, name, wrap)
+    launches = []
+    monkeypatch.setattr(ops, "_call", lambda name, *a, _f=ops._call, **kw: (launches.append(name), _f(name, *a, **kw))[1])
+    seen = {}
+    for T in (4, 12):
+        _, mh, x, w = _pair(20, T, 2, seed=1, B=2)
+        nblk = 2 * 2 * 2
+        counts.clear()
+        launches.clear()
+        with torch.no_grad():
+            mh(_d(x))
+        assert mh.backend_used == "hip" and counts == {"stgode_step": nblk, "stgode_bn_stats": nblk, "stgode_bn_apply": nblk}, counts
+        assert len(launches) == 3 * nblk
+        mh.eval()
+        launches.clear()
+        mh(_d(x))
+        assert len(launches) == 2 * nblk and "gptst_stgode_bn_stats" not in launches
+        mh.train()
+        counts.clear()
+        launches.clear()
+        _run(mh, _d(x), _d(w))
+        assert counts == {"stgode_step": 2 * nblk, "stgode_bn_stats": nblk, "stgode_bn_apply": nblk, "stgode_bn_bwd": nblk, "stgode_wgrad": nblk,
+                          "stgode_reduce": nblk}, counts
+        seen[T] = len(launches)
+    assert seen[4] == seen[12] == 8 * 8
+
+
+def test_fallbacks_take_the_torch_modules():
+    torch.manual_seed(2)
+
+    def same_as_torch(ap, xin, dim_in=64, dev=DEV, dtype=torch.float32):
+        mh, mt = STGODE(ap, dev, dim_in, 1, backend="hip").to(dtype), STGODE(ap, dev, dim_in, 1).to(dtype)
+        mt.load_state_dict(mh.state_dict(), strict=True)
+        mh.eval(), mt.eval()                                                 # (a downsample's TCN has dropout)
+        assert not H.supported(mh, xin)
+        with torch.no_grad():
+            yh, yt = mh(xin), mt(xin)
+        assert mh.backend_used == "torch" and mt.backend_used == "torch" and torch.equal(yh, yt)
+        return mh
+    x = torch.randn(2, 5, 20, 64, device=DEV)
+    same_as_torch(gu.model_args(20, n_layers=1), torch.randn(2, 5, 20, 2, device=DEV), dim_in=2)      # -mode ori sizes: the convolutions run
+    same_as_torch(gu.model_args(449, n_layers=1), torch.randn(1, 5, 449, 64, device=DEV))             # more nodes than the slab holds
+    same_as_torch(gu.model_args(20, n_layers=1), x.double(), dtype=torch.float64)                     # fp64
+    same_as_torch(gu.model_args(20, n_layers=1), x.cpu(), dev="cpu")                                  # CPU input
+    mg = STGODE(gu.model_args(20, n_layers=1), DEV, 64, 1, backend="hip")
+    assert H.supported(mg, x) and not H.supported(mg, x[:, :4])
+    with torch.no_grad():
+        mg(x)
+    assert mg.backend_used == "hip"
+
+
+# ---- 4. the chain ----------------------------------------------------------------------------------------------------------------------------
+def _front_end(tmp_path, backend, sd, psd):
+    from gptst_amd.enhance import EnhanceFrontEnd
+    from gptst_amd.eval_trainer import EvalTrainer
+    N = 20
+    args = make_args("PEMS08", mode="eval", num_nodes=N, embed_dim=8, HS=5, HT=6, scaler_zeros=synth.scaler_zeros(), batch_size=8, epochs=3,
+                     early_stop=False, log_dir=str(tmp_path), debug=True, model="STGODE_test", stgode_backend=backend, loss_func="mask_huber")
+    sd = O.init_state_dict(args, 4) if sd is None else sd
+    torch.manual_seed(0)
+    pred = STGODE(gu.model_args(N, T=12, P=12, n_layers=1), DEV, args.hidden_dim, args.output_dim, backend=args.stgode_backend)
+    if psd is None:
+        gu.xavier_redraw_(pred)
+    else:
+        pred.load_state_dict(psd, strict=True)
+    model = EnhanceFrontEnd(args, predictor=pred, finetune_encoder=False).to(DEV)
+    model.load_pretrained_model(sd)
+    return args, sd, model, EvalTrainer
+
+
+def test_chain_two_huber_steps_agree_with_the_torch_backend(tmp_path, parity):
+    args, sd, mh, ET = _front_end(tmp_path, "hip", None, None)
+    _, _, mt, _ = _front_end(tmp_path, "torch", sd, mh.predictor.state_dict())
+    mt.load_state_dict(mh.state_dict(), strict=True)
+    src = synth.make_batch(2, 12, 20, 1, interval=args.interval, seed=21).to(DEV)
+    tgt = synth.make_batch(2, 12, 20, 1, interval=args.interval, seed=22, start_slot=12).to(DEV)
+    losses = {}
+    for name, model in (("hip", mh), ("torch", mt)):
+        tr = ET(model, args, None, None, None, synth.SCALER_MEAN, synth.SCALER_STD)
+        tr.logger.setLevel(logging.WARNING)
+        model.train()
+        losses[name] = []
+        for _ in range(2):
+            tr.opt.zero_grad()
+            loss = tr._loss(model(src, tgt)[0], tgt)
+            loss.backward()
+            tr.opt.step()
+            assert model.predictor.backend_used == name
+            losses[name].append(float(loss.detach()))
+    assert losses["torch"][0] != losses["torch"][1]
+    errs = {"loss%d" % i: abs(losses["hip"][i] - losses["torch"][i]) / abs(losses["torch"][i]) for i in range(2)}
+    sh, st = mh.predictor.state_dict(), mt.predictor.state_dict()
+    for k in st:
+        if "running_" in k:
+            errs[k] = _err(sh[k], st[k])
+        elif "num_batches" in k:
+            assert int(sh[k]) == int(st[k]) == 2
+    _check(parity, errs)

@@ -18,7 +18,7 @@ import torch  # noqa: E402
 from gptst_amd import graph, ops  # noqa: E402
 from gptst_amd.config import predictor_args  # noqa: E402
 from gptst_amd.enhance import xavier_downstream_  # noqa: E402
-from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STSGCN, TGCN  # noqa: E402
+from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STGODE, STSGCN, TGCN  # noqa: E402
 
 DEV = "cuda:0"
 T, C = 12, 64
@@ -79,6 +79,13 @@ def stfgnn(N):                                    # the conf's three layers of [
     return m
 
 
+def stgode(N):                                    # the conf's n_layers = 3 on two normalised graphs, under the xavier redraw the confs ask for
+    ap = predictor_args("PEMS08", "STGODE")
+    s, d = graph.synthetic_adjacency(N, 2), graph.synthetic_adjacency(N, 5)
+    ap.num_nodes, ap.A_sp_wave, ap.A_se_wave = N, graph.stgode_normalized_adj(s), graph.stgode_normalized_adj(((d + d.T) > 0).astype("float32"))
+    return xavier_downstream_(STGODE(ap, DEV, C, 1, backend="hip"))
+
+
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
@@ -112,7 +119,7 @@ def run(make, B, N):
 
 
 CONFIGS = {}
-for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn), ("stfgnn", stfgnn)):
+for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn), ("stfgnn", stfgnn), ("stgode", stgode)):
     CONFIGS[_name + "_b2_n37"] = lambda make=_make: run(make, 2, 37)            # a padded node tile, several row tiles
     CONFIGS[_name + "_b1_n170"] = lambda make=_make: run(make, 1, 170)
 
