@@ -149,6 +149,17 @@ __device__ __forceinline__ float lrelu_grad_from_out(float out) { return out > 0
 
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-x)); }
 
+// StandardScaler.inverse_transform (reference lib/normalization.py:23-27) as fp32 torch forms it: a rounded multiply, then a rounded add.
+// The loss and the metrics keep a cell by `y > thresh` on this value, so the rounding is part of the rule: a stored raw zero
+// fl32((0 - mu) / sigma) comes back as exactly 0.0 (or within an ulp of mu) here, and as a residual of either sign from one fused
+// multiply-add — which `x * sigma + mu` compiles to under hipcc's default contraction.  (__fmul_rn / __fadd_rn are plain `*` / `+` in this
+// toolchain's headers and would be fused after inlining all the same; the pragma takes the contract flag off the two operations.)
+__device__ __forceinline__ float inverse_transform(float x, float sigma, float mu) {
+#pragma clang fp contract(off)
+    const float scaled = x * sigma;
+    return scaled + mu;
+}
+
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 __device__ __forceinline__ void st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
 // store of a tensor whose consumer is far away (the saved mix R of hyperTem: read by the backward ~0.5 ms later).  -DHT_R_NT: nontemporal.

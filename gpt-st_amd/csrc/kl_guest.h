@@ -100,8 +100,8 @@ __device__ __forceinline__ void tail_mfma_body(const TailArgs& t, int blk, float
                     const float o = acc0[r] + acc1[r] + bj;
                     const size_t e = i * J + j;
                     const float M = 1.f - o0[r];
-                    const float p = (o * t.sigma + t.mu) * M;
-                    const float y = (o1[r] * t.sigma + t.mu) * M;
+                    const float p = inverse_transform(o, t.sigma, t.mu) * M;
+                    const float y = inverse_transform(o1[r], t.sigma, t.mu) * M;
                     if (y > t.thresh) {
                         const float d = p - y;
                         s0 += fabsf(d); s1 += 1.f;

@@ -1,6 +1,7 @@
 // Loss and optimiser tail of the pretraining step.
 //   mae   : scaler_mae_loss (reference Run.py:92-100) + MAE_torch (lib/metrics.py:11-18) + inverse_transform
 //           (lib/normalization.py:23-27):  p=(out*s+m)*M, y=(label*s+m)*M, keep = y > thresh, loss = mean_keep |y-p|
+//           (out*s+m is common.h's inverse_transform: a rounded multiply, then a rounded add, as fp32 torch — the keep rule)
 //   kl    : 0.1 * KLDivLoss(sum)(log prob, eb) (Run.py:132, BasicTrainer.py:85) fused with the softmax backward of MLP_RL
 //   adam  : clip_grad_norm_(5) + Adam (BasicTrainer.py:95-97, Run.py:134) as ONE pass over a flat parameter buffer
 // stats (device float[8]): [0] sum |y-p| over kept cells, [1] kept count, [2] sum eb*(log eb - log prob), [3] extra sum g^2 terms in,
@@ -17,8 +18,8 @@ __global__ __launch_bounds__(256) void mae_fwd_kernel(const float* __restrict__ 
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)rows * J; e += (size_t)gridDim.x * 256) {
         const size_t i = e / J; const int j = (int)(e % J);
         const float M = 1.f - mask[e];
-        const float p = (out[e] * sigma + mu) * M;
-        const float y = (src[i * lda + j] * sigma + mu) * M;
+        const float p = inverse_transform(out[e], sigma, mu) * M;
+        const float y = inverse_transform(src[i * lda + j], sigma, mu) * M;
         if (y > thresh) { ls += fabsf(y - p); cnt += 1.f; }
     }
     ls = group_sum<64>(ls); cnt = group_sum<64>(cnt);
@@ -39,8 +40,8 @@ __global__ __launch_bounds__(256) void mae_bwd_kernel(const float* __restrict__ 
     for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < (size_t)rows * J; e += (size_t)gridDim.x * 256) {
         const size_t i = e / J; const int j = (int)(e % J);
         const float M = 1.f - mask[e];
-        const float p = (out[e] * sigma + mu) * M;
-        const float y = (src[i * lda + j] * sigma + mu) * M;
+        const float p = inverse_transform(out[e], sigma, mu) * M;
+        const float y = inverse_transform(src[i * lda + j], sigma, mu) * M;
         float g = 0.f;
         if (y > thresh) {
             const float d = p - y;

@@ -3,7 +3,8 @@
 //   per horizon t:        [n1, sum|e|, sum e^2, n2, sum|e/y|]        n1: cells with y > mae_thresh (all if none), n2: y > mape_thresh
 //   per (t, node n):      [K, sum p, sum y, sum p^2, sum y^2, sum p y]  over (batch, channel) — the moments CORR needs
 // p / y are formed on the fly as the reference does in pretrain mode (:229-235): y = inverse(label * m), p = inverse(out * m), where m
-// marks the masked cells.  Sums are doubles (atomicAdd f64).
+// marks the masked cells.  The mask product is rounded first; the inverse is common.h's inverse_transform (two rounded steps: the keep rule).
+// Sums are doubles (atomicAdd f64).
 #include "common.h"
 
 __global__ __launch_bounds__(256) void metrics_accum_kernel(const float* __restrict__ out, const float* __restrict__ src, int lda,
@@ -18,8 +19,8 @@ __global__ __launch_bounds__(256) void metrics_accum_kernel(const float* __restr
         for (int d = 0; d < D; ++d) {
             const size_t cell = ((size_t)bt * N + n) * D + d;
             const float msk = vis != nullptr ? 1.f - vis[cell] : 1.f;
-            const float p = (out[cell] * msk) * sigma + mu;
-            const float y = (src[((size_t)bt * N + n) * lda + d] * msk) * sigma + mu;
+            const float p = inverse_transform(out[cell] * msk, sigma, mu);
+            const float y = inverse_transform(src[((size_t)bt * N + n) * lda + d] * msk, sigma, mu);
             const float e = y - p;
             if (!has_mae_thresh || y > mae_thresh) { a[0] += 1.0; a[1] += fabsf(e); a[2] += (double)e * e; }
             if (y > mape_thresh) { a[3] += 1.0; a[4] += fabsf(e / y); }

@@ -67,8 +67,8 @@ __global__ __launch_bounds__(256) void tail_kernel(TailArgs t) {
                 o += t.b ? t.b[c4] : 0.f;
                 const size_t e = i * J + c4;
                 const float M = 1.f - t.mask[e];
-                const float p = (o * t.sigma + t.mu) * M;
-                const float y = (t.src[i * t.lda + c4] * t.sigma + t.mu) * M;
+                const float p = inverse_transform(o, t.sigma, t.mu) * M;
+                const float y = inverse_transform(t.src[i * t.lda + c4], t.sigma, t.mu) * M;
                 if (y > t.thresh) {
                     const float d = p - y;
                     s0 += fabsf(d); s1 += 1.f;
