@@ -86,6 +86,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-stfgnn_backend", default=FINETUNE_DEFAULTS["stfgnn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the STGODE predictor (predictors/stgode_hip.py)
     ap.add_argument("-stgode_backend", default=FINETUNE_DEFAULTS["stgode_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the MSDR predictor (predictors/msdr_hip.py)
+    ap.add_argument("-msdr_backend", default=FINETUNE_DEFAULTS["msdr_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -98,7 +100,8 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
-                         astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch", stgode_backend="torch")
+                         astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch", stgode_backend="torch",
+                         msdr_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -160,15 +163,24 @@ _STGODE_KEYS = [("data", "num_nodes", int), ("data", "num_timesteps_input", int)
                 ("model", "sigma1", float), ("model", "sigma2", float), ("model", "thres1", float), ("model", "thres2", float),
                 ("model", "in_channels", int), ("model", "out_channels", _EVAL), ("model", "n_layers", int),
                 ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+# reference model/MSDR/args.py:90-109.  ``filter_type`` takes its default from the conf's ``cl_decay_steps`` as the reference does (args.py:90): the
+# string "2000", which no branch of the cell names, so the confs' own ``dual_random_walk`` is never read and the cell runs on one scaled Laplacian
+# (graph.msdr_supports); ``--filter_type dual_random_walk`` on the command line selects the others.  `cl_decay_steps`, `use_curriculum_learning`,
+# `construct_type` and `l2lambda` are parsed and, as in the reference, read by nothing; `input_dim` is not read at all (Model.py:81 sets dim_in).
+_MSDR_KEYS = [("model", "cl_decay_steps", str, "filter_type"), ("model", "cl_decay_steps", int), ("model", "num_nodes", int),
+              ("model", "horizon", int), ("model", "seq_len", int), ("model", "max_diffusion_step", int), ("model", "num_rnn_layers", int),
+              ("model", "output_dim", int), ("model", "rnn_units", int), ("model", "pre_k", int), ("model", "pre_v", int),
+              ("model", "use_curriculum_learning", _EVAL), ("model", "construct_type", str), ("model", "l2lambda", int),
+              ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
 _PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS, "STSGCN": _STSGCN_KEYS,
-              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS}
+              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS, "MSDR": _MSDR_KEYS}
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN and STGODE are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE and MSDR are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN and STGODE predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE and MSDR predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)
@@ -181,8 +193,8 @@ def predictor_args(dataset, model="STGCN", argv=None):
     cm = configparser.ConfigParser()
     cm.optionxform = str
     cm.read(path)
-    for sec, key, typ in _PRED_KEYS[model]:
-        ap.add_argument("--" + key, default=typ(cm[sec][key]), type=typ)
+    for sec, key, typ, *flag in _PRED_KEYS[model]:                               # (a fourth entry: the flag that takes this conf key's value as its default)
+        ap.add_argument("--" + (flag[0] if flag else key), default=typ(cm[sec][key]), type=typ)
     pargs, _ = ap.parse_known_args([] if argv is None else argv)
     return pargs
 

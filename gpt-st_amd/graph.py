@@ -95,6 +95,49 @@ def tgcn_graph(A):
     return torch.tensor(normalized_adjacency(A), dtype=torch.float32)
 
 
+# ---- MSDR: the fixed supports of a GMSDR cell (reference model/MSDR/args.py:9-50, gmsdr_cell.py:80-91) ----------------------------------------
+def msdr_supports(A, filter_type):
+    """The (S, N, N) fp32 fixed supports ``predictors.MSDR`` multiplies by, dense where the reference keeps them sparse, from the raw
+    adjacency in fp32 as the reference holds it:
+
+        "dual_random_walk"   S = 2: (D^-1 A)^T and (D_T^-1 A^T)^T, D and D_T the row sums of A and A^T
+        "random_walk"        S = 1: (D^-1 A)^T
+        "laplacian"          S = 1: 2 L / lambda_max - I, L the normalised Laplacian of max(A, A^T); lambda_max from the dense eigenvalues
+                             (the reference asks ARPACK for the largest one)
+        anything else        S = 1: the same with lambda_max = 2, i.e. L - I.  The reference's default lands here: its ``--filter_type``
+                             takes its default from the conf's ``cl_decay_steps`` ("2000"), so the confs' own value is never read."""
+    a = np.asarray(A, dtype=np.float32)
+    n = len(a)
+
+    def random_walk(m):
+        d = m.sum(axis=1)
+        with np.errstate(divide="ignore"):
+            inv = np.power(d, -1)
+        inv[np.isinf(inv)] = 0.0
+        return inv[:, None] * m
+
+    def scaled_laplacian(lambda_max):
+        m = np.maximum(a, a.T)
+        d = m.sum(axis=1)
+        with np.errstate(divide="ignore"):
+            dis = np.power(d, -0.5)
+        dis[np.isinf(dis)] = 0.0
+        lap = np.identity(n) - (m * dis[None, :]).T * dis[None, :]             # the reference's operand order: (A D^-1/2)^T D^-1/2
+        if lambda_max is None:
+            lambda_max = float(np.abs(np.linalg.eigvalsh(lap)).max())          # ARPACK's 'LM': the largest magnitude
+        return (2.0 / lambda_max) * lap - np.identity(n)
+
+    if filter_type == "laplacian":
+        sup = [scaled_laplacian(None)]
+    elif filter_type == "random_walk":
+        sup = [random_walk(a).T]
+    elif filter_type == "dual_random_walk":
+        sup = [random_walk(a).T, random_walk(a.T).T]
+    else:
+        sup = [scaled_laplacian(2.0)]
+    return torch.tensor(np.stack([np.asarray(s, dtype=np.float32) for s in sup]), dtype=torch.float32)
+
+
 # ---- STFGNN: the spatial-temporal fusion graph (reference model/STFGNN/args.py:10-151) ---------------------------------------------------
 def stfgnn_fusion_graph(A, A_dtw, steps=4):
     """The (steps N, steps N) fp32 fusion matrix of ``construct_adj_fusion`` (args.py:101-151), from the spatial adjacency A and the temporal

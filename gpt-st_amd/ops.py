@@ -1547,3 +1547,46 @@ def stgode_bn_bwd(dY, Z, gamma, mean, rstd, B, T, N, dBest=None, which=None, idx
         _call("gptst_stgode_bn_bwd", _p(dY), _p(dBest), _p(which), idx, _p(Z), _p(gamma), _p(mean), _p(rstd), _p(part), ns, _p(G), _p(dg), _p(db),
               Z.shape[1], B, T, N, stage, tag="c%d s%d" % (Z.shape[1], stage), nbytes=_nb(Z, dY, dBest) + (stage and _nb(G)))
     return G, dg, db
+
+
+# ---- the downstream MSDR predictor's multi-state recurrence (csrc/msdr.hip) -----------------------------------------------------------------
+# TIME-major rows: a seq tensor is (T*B*N, width) with row (t B + b) N + n; the state ring Hs and its gradient dH are (T + K, B*N, Hp), slot
+# K + t the output of step t.  Outputs are the caller's buffers (the loop owns them).
+def msdr_groups(N, B, tiles=0):
+    """workgroups per sample of the step launches: the length of a row of their partials"""
+    return _C.lib().value("gptst_msdr_groups", N, B, tiles)
+
+
+def msdr_fwd_step(Lp, Wh, W2, bvec, R, w, wr, Gx, Hs, sig, t, B, T, N, w2=None, sig2=None, c=None, z=None, a=None, tiles=0):
+    """o = leaky_relu([h | L_k h]_k Wh^T + Gx[t]) W2^T + b + sum_k a_k (s_k + R_k) -> Hs[K + t], with s_k = Hs[t + k], h = s_{K-1} and
+    a = softmax_k(sum(sig[t + k]) + wr[k]);  sig[K + t] (and sig2 with w2) = per-workgroup partials of w . o;  kept when given: c, z, a"""
+    _chk(Lp, Wh, W2, bvec, R, w, w2, wr, Gx, Hs, sig, sig2, c, z, a)
+    K, Hp, ks = R.shape[0], Hs.shape[2], Lp.shape[0]
+    G = msdr_groups(N, B, tiles)
+    assert Wh.shape == (Hp, (ks + 1) * Hp) and W2.shape == (Hp, Hp) and bvec.shape == w.shape == (N, Hp) and R.shape == (K, N, Hp)
+    assert Hs.shape == (T + K, B * N, Hp) and sig.shape == (T + K, B, G) and Gx.shape == (T * B * N, Hp) and wr.shape == (K,)
+    assert (w2 is None) == (sig2 is None) and (sig2 is None or (sig2.shape == sig.shape and w2.shape == w.shape))
+    assert (c is None or c.shape == Gx.shape) and (z is None or z.shape == (T * B * N, (ks + 1) * Hp)) and (a is None or a.shape == (T, B, K))
+    _call("gptst_msdr_fwd_step", _p(Lp), Lp.shape[1], ks, _p(Wh), _p(W2), _p(bvec), _p(R), _p(w), _p(w2), _p(wr), _p(Gx), _p(Hs), _p(sig),
+          _p(sig2), _p(c), _p(z), (ks + 1) * Hp, _p(a), B, T, N, Hp, K, t, tiles, tag="Hp%d ks%d K%d" % (Hp, ks, K),
+          nbytes=_nb(Lp, Wh, W2, bvec, R, w) + (K + 2 + (c is not None) + (ks + 1) * (z is not None)) * B * N * Hp * 4)
+
+
+def msdr_bwd_pre(W, R, Hs, dH, c, dpre, pa, t, B, T, N, tiles=0):
+    """dpre[t] = (dH[K + t] W^T) leaky'(c[t]);  pa[b, g, k] = the workgroup's share of <dH[K + t], Hs[t + k] + R_k>"""
+    _chk(W, R, Hs, dH, c, dpre, pa)
+    K, Hp = R.shape[0], Hs.shape[2]
+    assert W.shape == (Hp, Hp) and Hs.shape == dH.shape == (T + K, B * N, Hp) and c.shape == dpre.shape == (T * B * N, Hp)
+    assert pa.shape == (B, msdr_groups(N, B, tiles), 8)
+    _call("gptst_msdr_bwd_pre", _p(W), _p(R), _p(Hs), _p(dH), _p(c), _p(dpre), _p(pa), B, T, N, Hp, K, t, tiles, tag="Hp%d K%d" % (Hp, K),
+          nbytes=_nb(W, R) + (K + 3) * B * N * Hp * 4)
+
+
+def msdr_bwd_state(LpT, WhT, w, a, pa, dpre, dH, de, t, B, T, N, tiles=0):
+    """de[t] = a (dA - sum a dA) with dA = the fold of pa;  dH[t + k] += a_k dH[K + t] + de_k w, and dH[t + K - 1] += [dpre | L_k^T dpre]_k WhT^T"""
+    _chk(LpT, WhT, w, a, pa, dpre, dH, de)
+    K, Hp, ks = a.shape[2], dH.shape[2], LpT.shape[0]
+    assert WhT.shape == (Hp, (ks + 1) * Hp) and w.shape == (N, Hp) and dH.shape == (T + K, B * N, Hp) and dpre.shape == (T * B * N, Hp)
+    assert a.shape == de.shape == (T, B, K) and pa.shape == (B, msdr_groups(N, B, tiles), 8)
+    _call("gptst_msdr_bwd_state", _p(LpT), LpT.shape[1], ks, _p(WhT), _p(w), _p(a), _p(pa), _p(dpre), _p(dH), _p(de), B, T, N, Hp, K, t, tiles,
+          tag="Hp%d ks%d K%d" % (Hp, ks, K), nbytes=_nb(LpT, WhT, w) + (2 * K + 2) * B * N * Hp * 4)

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 25  /* 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 26  /* 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -721,6 +721,32 @@ int gptst_mlprl_layer_bwd(const float* dlogits, const float* a, int lda, const f
                           const void* saved, long saved_bytes, float* d_time_eb, float* d_node_emb, float* d_ln1_w, float* d_ln1_b,
                           float* d_wpool_spa, float* d_bpool_spa, float* d_wpool_tem, float* d_bpool_tem, float* d_ln3_w, float* d_ln3_b,
                           void* scratch, long scratch_bytes, int B, int T, int N, int C, int d, int base, int HS, void* stream);
+
+/* ---- the downstream MSDR predictor's multi-state recurrence (msdr.hip; reference model/MSDR/gmsdr_cell.py:109-186, gpt-st_amd/predictors/msdr_hip.py) ---
+ * A cell keeps its last Kk outputs.  Per step t, with h the newest: pre = Gx_t + [h, L_1 h, .., A h] Th, c = leaky_relu(pre), a = softmax_k(w .
+ * vec(s_k + R_k) + bias), o = c W + b + sum_k a_k (s_k + R_k).  Gx and every weight / graph / input gradient are hoisted onto gptst_stgcn_nodemix /
+ * tapgemm / wgrad and gptst_mtgnn_graphgrad; these launches are the state chain.  All rows are TIME-major: row (t B + b) N + n of a "seq" tensor
+ * (T B N, width).  Hs (T + Kk, B N, Hp) is the state ring: slots [0, Kk) the initial states, oldest first, slot Kk + t the output of step t; dH
+ * is its gradient, same shape.  Hp = rnn_units zero-padded to a multiple of 16 (16 .. 128); 1 <= Kk <= 8; L (ks, Np, Np) zero-padded to Np = 16
+ * ceil(N / 16), ks = 2 or 3: the fixed supports, then A.  G = gptst_msdr_groups(N, B, tiles) workgroups serve a sample (tiles: 0 = the kernel's
+ * choice, 1 or 2 row tiles of 16 nodes per workgroup); partial rows have G entries and are folded in index order (no atomics).
+ * fwd_step: Wh (Hp, (ks + 1) Hp) = the state rows of Theta, column m Hp + i = (matrix m, input channel i), matrix 0 the identity;  W2 (Hp, Hp) =
+ *   W^T;  bvec, w, w2 (N, Hp);  R (Kk, N, Hp);  wr (Kk) = w . R_k + bias;  Gx (seq, Hp).  Reads slots t .. t + Kk - 1 of Hs and of sig (T + Kk,
+ *   B, G: the partials of w . s), writes slot t + Kk of both — and of sig2 with w2 (both or neither).  Kept when not NULL: c (seq, Hp), z (seq,
+ *   ldz = (ks + 1) Hp) = [h | L_k h]_k, a (T, B, Kk).
+ * bwd_pre: W (Hp, Hp);  dO = slot Kk + t of dH  ->  dpre (seq, Hp)[t] = (dO W^T) leaky'(c), pa (B, G, 8)[.., k] = partial of <dO, s_k + R_k>.
+ * bwd_state: LT (ks, Np, Np) the transposes;  WhT (Hp, (ks + 1) Hp), column m Hp + j = Theta_m[i][j];  de (T, B, Kk)[t] = a (dA - sum a dA);
+ *   slots t + k of dH += a_k dO + de_k w, slot t + Kk - 1 also += [dpre | L_k^T dpre]_k WhT^T.
+ * lds_bytes: the dynamic LDS of the widest of the three at this shape (above 160 KB they return GPTST_ESHAPE). */
+int gptst_msdr_lds_bytes(int N, int Hp, int B, int ks);
+int gptst_msdr_groups(int N, int B, int tiles);
+int gptst_msdr_fwd_step(const float* L, int Np, int ks, const float* Wh, const float* W2, const float* bvec, const float* R, const float* w,
+                        const float* w2, const float* wr, const float* Gx, float* Hs, float* sig, float* sig2, float* c, float* z, int ldz,
+                        float* a, int B, int T, int N, int Hp, int Kk, int t, int tiles, void* stream);
+int gptst_msdr_bwd_pre(const float* W, const float* R, const float* Hs, const float* dH, const float* c, float* dpre, float* pa, int B, int T,
+                       int N, int Hp, int Kk, int t, int tiles, void* stream);
+int gptst_msdr_bwd_state(const float* LT, int Np, int ks, const float* WhT, const float* w, const float* a, const float* pa, const float* dpre,
+                         float* dH, float* de, int B, int T, int N, int Hp, int Kk, int t, int tiles, void* stream);
 
 /* ---- communication (comm.hip): RCCL over xGMI with an explicit stream — a collective can sit inside a captured hipGraph -------------
  * The reference has no distributed code; these carry the data-parallel gradient exchange (one all-reduce of [flat gradient | statistics])
