@@ -5,8 +5,8 @@
 //     o   = c W + b + sum_k a_k (s_k + R_k)
 //
 // Everything on the input side (Gx = [U, L U, A U] Tx + beta over all steps, every weight / graph / input gradient) is hoisted out of the loop
-// onto the kernels of csrc/stgcn.hip and csrc/mtgnn.hip (predictors/msdr_hip.py).  What is left per step is this kernel family, the layout of
-// csrc/tgcn.hip's: a workgroup owns 16 NT nodes of one sample b;
+// onto the kernels of csrc/stgcn.hip and csrc/mtgnn.hip (predictors/msdr_hip.py).  What is left per step is this kernel family, in the layout of
+// csrc/recur_step_dev.h (whose two inner loops and launch it shares with csrc/tgcn.hip): a workgroup owns 16 NT nodes of one sample b;
 //
 //   fwd step    1 launch   slab = h_b (all nodes) in LDS;  M = [h | L_k h]_k for the tile;  pre = M Wh^T + Gx_t;  c -> LDS;  o = c W2^T + b +
 //                          the attention mix;  writes o into the state ring's next slot and, per workgroup, sigma = w . o over its tile
@@ -24,11 +24,8 @@
 // fp32 MFMA 16x16x4 (exact fp32).  Plain launches only: no workgroup waits on another.
 #include "common.h"
 #include "gptst_hip.h"
+#include "recur_step_dev.h"
 
-#define MS_THREADS 256
-#define MS_SP 68                 // pitch of the 64-column operand slab (csrc/tgcn.hip TG_SP): conflict-free ds_read_b32 down a column
-#define MS_MAX_DEVICES 64
-#define MS_LDS_MAX (160 * 1024)
 #define MS_MAXK 8                // kept states
 
 enum { MS_FWD = 0, MS_BWD_PRE = 1, MS_BWD_STATE = 2 };
@@ -58,13 +55,13 @@ __device__ __forceinline__ float ms_block_sum(float v, float* red, int tid) {
 }
 
 template <int MODE, int NT>
-__global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
+__global__ __launch_bounds__(RECUR_THREADS) void ms_step_kernel(MsStep p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     __shared__ float att[MS_MAXK], dev[MS_MAXK], red[4];
     const int MP = p.K + 4, CP = p.Hp + 4;
-    float* slab = smem;                                                  // [Np][MS_SP]: 64 columns of In_b (not in bwd pre)
-    float* Ml = smem + (MODE == MS_BWD_PRE ? 0 : (size_t)p.Np * MS_SP);  // [16 NT][K + 4]: the A operand of the GEMM
-    float* Cl = Ml + (size_t)16 * NT * MP;                               // fwd: [16 NT][Hp + 4]: c, the A operand of the second GEMM
+    float* slab = smem;                                                     // [Np][RECUR_SP]: 64 columns of In_b (not in bwd pre)
+    float* Ml = smem + (MODE == MS_BWD_PRE ? 0 : (size_t)p.Np * RECUR_SP);  // [16 NT][K + 4]: the A operand of the GEMM
+    float* Cl = Ml + (size_t)16 * NT * MP;                                  // fwd: [16 NT][Hp + 4]: c, the A operand of the second GEMM
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const int b = blockIdx.y, n0 = blockIdx.x * 16 * NT, Hp = p.Hp, Kk = p.Kk;
     const size_t slot = (size_t)p.B * p.N * Hp;                          // floats per ring slot
@@ -114,7 +111,7 @@ __global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
     if (MODE == MS_BWD_PRE) {
         // ---- the A operand is the tile's own rows of dO = dH[slot Kk + t] ----
         const float* dO = p.dH + (size_t)(Kk + p.t) * slot;
-        for (int f = tid; f < 16 * NT * (Hp / 4); f += MS_THREADS) {
+        for (int f = tid; f < 16 * NT * (Hp / 4); f += RECUR_THREADS) {
             const int row = f / (Hp / 4), c4 = f % (Hp / 4), n = n0 + row;
             st4(Ml + row * MP + 4 * c4, n < p.N ? ld4(dO + (srow + n) * Hp + 4 * c4) : f4zero());
         }
@@ -123,44 +120,22 @@ __global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
         const float* In = MODE == MS_FWD ? p.Hs + (size_t)(p.t + Kk - 1) * slot + srow * Hp : p.dpre + qrow * Hp;
         for (int cg = 0; 64 * cg < Hp; ++cg) {
             __syncthreads();                                             // the previous slab's reads are done (and the prologue's writes)
-            for (int f = tid; f < p.Np * 16; f += MS_THREADS) {
+            for (int f = tid; f < p.Np * 16; f += RECUR_THREADS) {
                 const int m = f >> 4, c4 = f & 15, col = 64 * cg + 4 * c4;
-                st4(slab + m * MS_SP + 4 * c4, (m < p.N && col < Hp) ? ld4(In + (size_t)m * Hp + col) : f4zero());
+                st4(slab + m * RECUR_SP + 4 * c4, (m < p.N && col < Hp) ? ld4(In + (size_t)m * Hp + col) : f4zero());
             }
             __syncthreads();
-            for (int f = tid; f < 16 * NT * 16; f += MS_THREADS) {       // the identity block: the tile's own rows
+            for (int f = tid; f < 16 * NT * 16; f += RECUR_THREADS) {    // the identity block: the tile's own rows
                 const int row = f >> 4, c4 = f & 15, col = 64 * cg + 4 * c4, n = n0 + row;
                 if (col >= Hp) continue;
-                const float4 v = n < p.Np ? ld4(slab + n * MS_SP + 4 * c4) : f4zero();
+                const float4 v = n < p.Np ? ld4(slab + n * RECUR_SP + 4 * c4) : f4zero();
                 st4(Ml + row * MP + col, v);
                 if (MODE == MS_FWD && p.z != nullptr && n < p.N) st4(p.z + (qrow + n) * p.ldz + col, v);
             }
             if (64 * cg + 16 * wave >= Hp) continue;                     // (wave-uniform)
             for (int k = 0; k < p.ks; ++k) {
-                const float* Lk = p.L + (size_t)k * p.Np * p.Np;
                 f32x4 acc[NT];
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-                float4 an[NT];                                           // the graph rows come from L2: fetched one step ahead of their use
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) an[nt] = tv[nt] ? ld4(Lk + (size_t)(n0 + 16 * nt + j) * p.Np + 4 * kk) : f4zero();
-                for (int m0 = 0; m0 < p.Np; m0 += 16) {
-                    float4 a[NT];
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        a[nt] = an[nt];
-                        if (tv[nt] && m0 + 16 < p.Np) an[nt] = ld4(Lk + (size_t)(n0 + 16 * nt + j) * p.Np + m0 + 16 + 4 * kk);
-                    }
-                    const float* sp = slab + (m0 + 4 * kk) * MS_SP + 16 * wave + j;
-                    const float bv[4] = {sp[0], sp[MS_SP], sp[2 * MS_SP], sp[3 * MS_SP]};
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].x, bv[0], acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].y, bv[1], acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].z, bv[2], acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].w, bv[3], acc[nt], 0, 0, 0);
-                    }
-                }
+                recur_mix_tiles<NT>(acc, p.L + (size_t)k * p.Np * p.Np, p.Np, n0, tv, slab, wave, j, kk);
                 const int col = (k + 1) * Hp + 64 * cg + 16 * wave + j;  // accumulator layout: reg r = (row 4 kk + r, column j)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
@@ -179,29 +154,9 @@ __global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
     float part[MS_MAXK];
 #pragma unroll
     for (int k = 0; k < MS_MAXK; ++k) part[k] = 0.f;
-    for (int ct = wave; 16 * ct < p.NO; ct += MS_THREADS / 64) {
+    for (int ct = wave; 16 * ct < p.NO; ct += RECUR_THREADS / 64) {
         f32x4 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* wp = p.Wt + (size_t)(16 * ct + j) * p.K + 4 * kk;
-        const float* mp = Ml + j * MP + 4 * kk;
-        for (int q0 = 0; q0 < p.K; q0 += 64) {                           // the weights come from L2: four k-blocks of loads in flight at a time
-            float4 w[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = q0 + 16 * i < p.K ? ld4(wp + q0 + 16 * i) : f4zero();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (q0 + 16 * i >= p.K) break;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float4 a = ld4(mp + 16 * nt * MP + q0 + 16 * i);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[i].x, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[i].y, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[i].z, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[i].w, acc[nt], 0, 0, 0);
-                }
-            }
-        }
+        recur_gemm_tiles<NT>(acc, Ml, MP, p.Wt, p.K, ct, j, kk);
         const int col = 16 * ct + j;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -249,29 +204,9 @@ __global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
         __syncthreads();
         float s1 = 0.f, s2 = 0.f;
         float* out = p.Hs + (size_t)(p.t + Kk) * slot;
-        for (int ct = wave; 16 * ct < Hp; ct += MS_THREADS / 64) {
+        for (int ct = wave; 16 * ct < Hp; ct += RECUR_THREADS / 64) {
             f32x4 acc[NT];
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-            const float* wp = p.W2 + (size_t)(16 * ct + j) * Hp + 4 * kk;
-            const float* mp = Cl + j * CP + 4 * kk;
-            for (int q0 = 0; q0 < Hp; q0 += 64) {
-                float4 w[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) w[i] = q0 + 16 * i < Hp ? ld4(wp + q0 + 16 * i) : f4zero();
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    if (q0 + 16 * i >= Hp) break;
-#pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) {
-                        const float4 a = ld4(mp + 16 * nt * CP + q0 + 16 * i);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[i].x, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[i].y, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[i].z, acc[nt], 0, 0, 0);
-                        acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[i].w, acc[nt], 0, 0, 0);
-                    }
-                }
-            }
+            recur_gemm_tiles<NT>(acc, Cl, CP, p.W2, Hp, ct, j, kk);
             const int col = 16 * ct + j;
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
@@ -299,56 +234,34 @@ __global__ __launch_bounds__(MS_THREADS) void ms_step_kernel(MsStep p) {
 
 // ---- launch ----
 static size_t ms_lds_bytes(int mode, int Np, int Hp, int ks, int nt) {
-    const size_t slab = mode == MS_BWD_PRE ? 0 : (size_t)Np * MS_SP;
+    const size_t slab = mode == MS_BWD_PRE ? 0 : (size_t)Np * RECUR_SP;
     const size_t K = mode == MS_BWD_PRE ? Hp : (size_t)(ks + 1) * Hp;
     return (slab + (size_t)16 * nt * (K + 4) + (mode == MS_FWD ? (size_t)16 * nt * (Hp + 4) : 0)) * sizeof(float);
 }
 
-// row tiles per workgroup, as csrc/tgcn.hip: 2 while that still leaves more workgroups than the chip has CUs, else 1
-static int ms_tiles(int B, int Np, int forced) {
-    if (forced == 1 || forced == 2) return forced;
-    const int tiles = Np / 16;
-    return (long)B * ((tiles + 1) / 2) > 256 ? 2 : 1;
-}
-
 static int ms_groups(int B, int Np, int forced) {
-    const int nt = ms_tiles(B, Np, forced);
+    const int nt = recur_tiles(B, Np, forced);
     return (Np / 16 + nt - 1) / nt;
-}
-
-template <int MODE, int NT>
-static int ms_launch_nt(const MsStep& p, hipStream_t stream) {
-    const size_t smem = ms_lds_bytes(MODE, p.Np, p.Hp, p.ks, NT);
-    if (smem > 64 * 1024) {                    // more than 64 KB of dynamic LDS needs the attribute, on every device this process launches on
-        static size_t have[MS_MAX_DEVICES] = {};
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0) return GPTST_EARG;
-        if (dev >= MS_MAX_DEVICES || have[dev] < smem) {
-            const hipError_t e = hipFuncSetAttribute((const void*)ms_step_kernel<MODE, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return (int)e;
-            if (dev < MS_MAX_DEVICES) have[dev] = smem;          // (a race sets it twice: harmless)
-        }
-    }
-    hipLaunchKernelGGL((ms_step_kernel<MODE, NT>), dim3(p.G, p.B), dim3(MS_THREADS), smem, stream, p);
-    GPTST_CHECK_LAUNCH();
-    return GPTST_OK;
 }
 
 template <int MODE>
 static int ms_launch(MsStep p, int tiles, void* stream) {
-    if (!p.Wt || p.B <= 0 || p.B > 65535 || p.T <= 0 || p.N <= 0 || p.t < 0 || p.t >= p.T || tiles < 0 || tiles > 2) return GPTST_EARG;
     if (MODE != MS_BWD_PRE && (!p.L || p.ks < 1 || p.ks > 3)) return GPTST_EARG;
-    if (p.Hp < 16 || p.Hp > 128 || p.Hp % 16 || p.Np != 16 * ((p.N + 15) / 16) || p.Kk < 1 || p.Kk > MS_MAXK) return GPTST_ESHAPE;
-    const int nt = ms_tiles(p.B, p.Np, tiles);
+    const int rc = recur_check(p.Wt, p.B, p.T, p.N, p.t, tiles, p.Hp, p.Np);
+    if (rc != GPTST_OK) return rc;
+    if (p.Kk < 1 || p.Kk > MS_MAXK) return GPTST_ESHAPE;
+    const int nt = recur_tiles(p.B, p.Np, tiles);
     p.G = ms_groups(p.B, p.Np, tiles);
-    if (ms_lds_bytes(MODE, p.Np, p.Hp, p.ks, nt) > MS_LDS_MAX) return GPTST_ESHAPE;
-    return nt == 2 ? ms_launch_nt<MODE, 2>(p, (hipStream_t)stream) : ms_launch_nt<MODE, 1>(p, (hipStream_t)stream);
+    const size_t smem = ms_lds_bytes(MODE, p.Np, p.Hp, p.ks, nt);
+    if (smem > RECUR_LDS_MAX) return GPTST_ESHAPE;
+    return nt == 2 ? recur_launch<ms_step_kernel<MODE, 2>>(p, dim3(p.G, p.B), smem, (hipStream_t)stream)
+                   : recur_launch<ms_step_kernel<MODE, 1>>(p, dim3(p.G, p.B), smem, (hipStream_t)stream);
 }
 
 extern "C" int gptst_msdr_lds_bytes(int N, int Hp, int B, int ks) {
     if (N <= 0 || Hp <= 0 || B <= 0 || ks < 1) return GPTST_EARG;
     const int Np = 16 * ((N + 15) / 16);
-    return (int)ms_lds_bytes(MS_FWD, Np, Hp, ks, ms_tiles(B, Np, 0));         // the widest of the three launches
+    return (int)ms_lds_bytes(MS_FWD, Np, Hp, ks, recur_tiles(B, Np, 0));      // the widest of the three launches
 }
 
 extern "C" int gptst_msdr_groups(int N, int B, int tiles) {

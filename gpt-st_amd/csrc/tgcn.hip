@@ -15,16 +15,13 @@
 // Rows: a "step" tensor is (B*N, Hp) with row b N + n; a "seq" tensor is (B*T*N, width) with row (b T + t) N + n (the layout of the hoisted
 // kernels: channels-last, nothing permuted).  Hp = rnn_units zero-padded to a multiple of 16: a padded channel stays exactly 0 (sigmoid(0) = 1/2,
 // tanh(0) = 0, h' = 0/2 + 0/2).  fp32 MFMA 16x16x4 (exact fp32).  Plain launches only: no workgroup waits on another, no float atomics.
+// The GEMM's inner loop, the constants and the launch are csrc/recur_step_dev.h's, shared with csrc/msdr.hip; the slab fill, the mix loop (the
+// header's recur_mix_tiles, kept written out here: measured) and the epilogues are here.
 #include "common.h"
 #include "gptst_hip.h"
-
-#define TG_THREADS 256
-#define TG_SP 68                 // pitch of the 64-column operand slab: 4 kk-rows apart = 272 floats = 16 banks apart, conflict-free ds_read_b32
-#define TG_MAX_DEVICES 64
-#define TG_LDS_MAX (160 * 1024)
+#include "recur_step_dev.h"
 
 enum { TG_FWD_GATES = 0, TG_FWD_STATE = 1, TG_BWD_CAND = 2, TG_BWD_STATE = 3 };
-
 
 struct TgStep {
     const float* L; int Np;                    // (Np, Np) zero-padded: L forward, L^T backward
@@ -36,11 +33,11 @@ struct TgStep {
 };
 
 template <int MODE, int NT>
-__global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
+__global__ __launch_bounds__(RECUR_THREADS) void tg_step_kernel(TgStep p) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* slab = smem;                              // [Np][TG_SP]: 64 columns of In_b
+    float* slab = smem;                              // [Np][RECUR_SP]: 64 columns of In_b
     const int MP = p.K + 4;
-    float* Ml = smem + (size_t)p.Np * TG_SP;         // [16 NT][K + 4]: M, the A operand of the GEMM
+    float* Ml = smem + (size_t)p.Np * RECUR_SP;      // [16 NT][K + 4]: M, the A operand of the GEMM
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
     const int b = blockIdx.y, n0 = blockIdx.x * 16 * NT, Hp = p.Hp;
     const size_t srow = (size_t)b * p.N;                         // first step row of b
@@ -52,7 +49,7 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
     // ---- mix: M = L[tile rows, :] In_b, 64 columns of In_b at a time; wave w owns column tile w of the 64 for all NT row tiles ----
     for (int cg = 0; 64 * cg < p.K; ++cg) {
         __syncthreads();                                         // the previous slab's reads are done
-        for (int f = tid; f < p.Np * 16; f += TG_THREADS) {
+        for (int f = tid; f < p.Np * 16; f += RECUR_THREADS) {
             const int m = f >> 4, c4 = f & 15, col = 64 * cg + 4 * c4;
             float4 v = f4zero();
             if (m < p.N && col < p.K) {
@@ -66,10 +63,11 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
                     if (m >= n0 && m < n0 + 16 * NT) st4(p.dp1_out + (qrow + m) * Hp + col, v);      // the tile's owner keeps dpre1
                 }
             }
-            st4(slab + m * TG_SP + 4 * c4, v);
+            st4(slab + m * RECUR_SP + 4 * c4, v);
         }
         __syncthreads();
         if (64 * cg + 16 * wave >= p.K) continue;                // (wave-uniform)
+        // recur_mix_tiles, written out: through the shared function these kernels came out 0.5 - 1.3 % slower (recur_step_dev.h)
         f32x4 acc[NT];
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
@@ -83,8 +81,8 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
                 a[nt] = an[nt];
                 if (tv[nt] && m0 + 16 < p.Np) an[nt] = ld4(p.L + (size_t)(n0 + 16 * nt + j) * p.Np + m0 + 16 + 4 * kk);
             }
-            const float* sp = slab + (m0 + 4 * kk) * TG_SP + 16 * wave + j;
-            const float bv[4] = {sp[0], sp[TG_SP], sp[2 * TG_SP], sp[3 * TG_SP]};
+            const float* sp = slab + (m0 + 4 * kk) * RECUR_SP + 16 * wave + j;
+            const float bv[4] = {sp[0], sp[RECUR_SP], sp[2 * RECUR_SP], sp[3 * RECUR_SP]};
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
                 acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[nt].x, bv[0], acc[nt], 0, 0, 0);
@@ -106,29 +104,9 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
     __syncthreads();
 
     // ---- GEMM + epilogue: wave w owns output column tiles w, w + 4, ... for all NT row tiles ----
-    for (int ct = wave; 16 * ct < p.NO; ct += TG_THREADS / 64) {
+    for (int ct = wave; 16 * ct < p.NO; ct += RECUR_THREADS / 64) {
         f32x4 acc[NT];
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) acc[nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        const float* wp = p.Wt + (size_t)(16 * ct + j) * p.K + 4 * kk;
-        const float* mp = Ml + j * MP + 4 * kk;
-        for (int q0 = 0; q0 < p.K; q0 += 64) {                     // the weights come from L2: four k-blocks of loads in flight at a time
-            float4 w[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) w[i] = q0 + 16 * i < p.K ? ld4(wp + q0 + 16 * i) : f4zero();
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                if (q0 + 16 * i >= p.K) break;
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) {
-                    const float4 a = ld4(mp + 16 * nt * MP + q0 + 16 * i);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.x, w[i].x, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.y, w[i].y, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.z, w[i].z, acc[nt], 0, 0, 0);
-                    acc[nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a.w, w[i].w, acc[nt], 0, 0, 0);
-                }
-            }
-        }
+        recur_gemm_tiles<NT>(acc, Ml, MP, p.Wt, p.K, ct, j, kk);
         const int col = 16 * ct + j;
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt)
@@ -167,47 +145,25 @@ __global__ __launch_bounds__(TG_THREADS) void tg_step_kernel(TgStep p) {
 }
 
 // ---- launch ----
-static size_t tg_lds_bytes(int Np, int K, int nt) { return ((size_t)Np * TG_SP + (size_t)16 * nt * (K + 4)) * sizeof(float); }
-
-// row tiles per workgroup: 2 while that still leaves more workgroups than the chip has CUs, else 1 (a small batch must not collapse the grid)
-static int tg_tiles(int B, int Np, int forced) {
-    if (forced == 1 || forced == 2) return forced;
-    const int tiles = Np / 16;
-    return (long)B * ((tiles + 1) / 2) > 256 ? 2 : 1;
-}
-
-template <int MODE, int NT>
-static int tg_launch_nt(const TgStep& p, hipStream_t stream) {
-    const size_t smem = tg_lds_bytes(p.Np, p.K, NT);
-    if (smem > 64 * 1024) {                    // more than 64 KB of dynamic LDS needs the attribute, on every device this process launches on
-        static size_t have[TG_MAX_DEVICES] = {};
-        int dev = -1;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0) return GPTST_EARG;
-        if (dev >= TG_MAX_DEVICES || have[dev] < smem) {
-            const hipError_t e = hipFuncSetAttribute((const void*)tg_step_kernel<MODE, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-            if (e != hipSuccess) return (int)e;
-            if (dev < TG_MAX_DEVICES) have[dev] = smem;          // (a race sets it twice: harmless)
-        }
-    }
-    const int tiles = p.Np / 16;
-    hipLaunchKernelGGL((tg_step_kernel<MODE, NT>), dim3((tiles + NT - 1) / NT, p.B), dim3(TG_THREADS), smem, stream, p);
-    GPTST_CHECK_LAUNCH();
-    return GPTST_OK;
-}
+static size_t tg_lds_bytes(int Np, int K, int nt) { return ((size_t)Np * RECUR_SP + (size_t)16 * nt * (K + 4)) * sizeof(float); }
 
 template <int MODE>
 static int tg_launch(TgStep p, int tiles, void* stream) {
-    if (!p.L || !p.Wt || p.B <= 0 || p.B > 65535 || p.T <= 0 || p.N <= 0 || p.t < 0 || p.t >= p.T || tiles < 0 || tiles > 2) return GPTST_EARG;
-    if (p.Hp < 16 || p.Hp > 128 || p.Hp % 16 || p.Np != 16 * ((p.N + 15) / 16)) return GPTST_ESHAPE;
-    const int nt = tg_tiles(p.B, p.Np, tiles);
-    if (tg_lds_bytes(p.Np, p.K, nt) > TG_LDS_MAX) return GPTST_ESHAPE;
-    return nt == 2 ? tg_launch_nt<MODE, 2>(p, (hipStream_t)stream) : tg_launch_nt<MODE, 1>(p, (hipStream_t)stream);
+    if (!p.L) return GPTST_EARG;
+    const int rc = recur_check(p.Wt, p.B, p.T, p.N, p.t, tiles, p.Hp, p.Np);
+    if (rc != GPTST_OK) return rc;
+    const int nt = recur_tiles(p.B, p.Np, tiles);
+    const size_t smem = tg_lds_bytes(p.Np, p.K, nt);
+    if (smem > RECUR_LDS_MAX) return GPTST_ESHAPE;
+    const dim3 grid((p.Np / 16 + nt - 1) / nt, p.B);
+    return nt == 2 ? recur_launch<tg_step_kernel<MODE, 2>>(p, grid, smem, (hipStream_t)stream)
+                   : recur_launch<tg_step_kernel<MODE, 1>>(p, grid, smem, (hipStream_t)stream);
 }
 
 extern "C" int gptst_tgcn_lds_bytes(int N, int Hp, int B) {
     if (N <= 0 || Hp <= 0 || B <= 0) return GPTST_EARG;
     const int Np = 16 * ((N + 15) / 16);
-    return (int)tg_lds_bytes(Np, 2 * Hp, tg_tiles(B, Np, 0));               // the widest K of the four launches (bwd state)
+    return (int)tg_lds_bytes(Np, 2 * Hp, recur_tiles(B, Np, 0));               // the widest K of the four launches (bwd state)
 }
 
 extern "C" int gptst_tgcn_fwd_gates(const float* L, int Np, const float* W0h, const float* h, const float* Gx0, float* u, float* r, float* q,

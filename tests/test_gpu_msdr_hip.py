@@ -36,8 +36,9 @@ def _g(t):
 
 # ---- 1. the three step launches, each alone, against their formulas ---------------------------------------------------------------------------
 # (1, 266, 64): 272 padded nodes, a slab of 73 984 bytes: the forward and the second backward launch ask for more than the 64 KB of dynamic LDS
-# a launch gets by default
-STEP_SHAPES = [(1, 16, 32), (3, 37, 64), (2, 170, 64), (1, 266, 64)]
+# a launch gets by default.  (2, 37, 112): Hp above 64, so a second 64-column slab pass whose last wave has no column tile, zero fill at
+# col >= Hp, and a partial k-block in the second GEMM
+STEP_SHAPES = [(1, 16, 32), (3, 37, 64), (2, 170, 64), (1, 266, 64), (2, 37, 112)]
 VARIANTS = [(1, 1, 1), (4, 2, 2), (4, 1, 0), (1, 2, 2)]          # (kept states K, fixed supports, row tiles per workgroup: 0 = the kernel's choice)
 T2, T1 = 2, 1                # two steps in the seq tensors, the launch works on the second: a wrong (t, b) row offset shows
 

@@ -18,7 +18,7 @@ import torch  # noqa: E402
 from gptst_amd import graph, ops  # noqa: E402
 from gptst_amd.config import predictor_args  # noqa: E402
 from gptst_amd.enhance import xavier_downstream_  # noqa: E402
-from gptst_amd.predictors import ASTGCN, MTGNN, STFGNN, STGCN, STGODE, STSGCN, TGCN  # noqa: E402
+from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STSGCN, TGCN  # noqa: E402
 
 DEV = "cuda:0"
 T, C = 12, 64
@@ -86,6 +86,19 @@ def stgode(N):                                    # the conf's n_layers = 3 on t
     return xavier_downstream_(STGODE(ap, DEV, C, 1, backend="hip"))
 
 
+def msdr(N):                                      # the conf's 2 + 2 layers of pre_k = 4 states; rnn_units 100: channels padded to 112
+    ap = predictor_args("PEMS08", "MSDR")
+    ap.num_nodes, ap.rnn_units = N, 100
+    ap.supports = graph.msdr_supports(graph.synthetic_adjacency(N, 2), ap.filter_type)
+    m = MSDR(ap, DEV, C, backend="hip")
+    with torch.no_grad():                         # W, b, R off their zero initialisation: at it every state is 0 and a wrong product hides
+        for c in m.cells():
+            c.W.normal_(0, 1 / 32)
+            c.b.normal_(0, 0.1)
+            c.R.normal_(0, 0.1)
+    return m
+
+
 def sha(t):
     return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
 
@@ -119,7 +132,8 @@ def run(make, B, N):
 
 
 CONFIGS = {}
-for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn), ("stfgnn", stfgnn), ("stgode", stgode)):
+for _name, _make in (("stgcn", stgcn), ("tgcn", tgcn), ("mtgnn", mtgnn), ("astgcn", astgcn), ("stsgcn", stsgcn), ("stfgnn", stfgnn), ("stgode", stgode),
+                     ("msdr", msdr)):
     CONFIGS[_name + "_b2_n37"] = lambda make=_make: run(make, 2, 37)            # a padded node tile, several row tiles
     CONFIGS[_name + "_b1_n170"] = lambda make=_make: run(make, 1, 170)
 
