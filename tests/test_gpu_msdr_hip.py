@@ -8,7 +8,12 @@ The gradient of ``attlinear.bias`` is identically zero (a constant added to ever
 so a relative error on it means nothing: those gradients (one per cell) are held to |g| <= 1e-6 max|gradient of that cell's attlinear.weight|
 instead (the fp32 reference stays below 6.1e-7 of it; the HIP backend returns exactly 0).
 
-Every comparison first moves W, b and R off their zero initialisation (msdr_util.perturb_): at the initialisation every hidden state is 0."""
+Every comparison first moves W, b and R off their zero initialisation (msdr_util.perturb_): at the initialisation every hidden state is 0.
+
+Step shapes: padded widths Hp 16 (one column tile: three waves skip the mix, K below one k-block), 32, 48, 64, 112 and 128 (two full slabs, K
+up to 512), each under every variant of kept states, supports and row tiles; the launch's own choice of row tiles (tiles = 0) is crossed at its
+boundary, 37 nodes at B = 128 (3 workgroups a sample) and 129 (2), where it must be bit-equal to the forced count it names.  Every launch
+is run twice and must repeat bit for bit."""
 import logging
 from types import SimpleNamespace
 
@@ -37,8 +42,10 @@ def _g(t):
 # ---- 1. the three step launches, each alone, against their formulas ---------------------------------------------------------------------------
 # (1, 266, 64): 272 padded nodes, a slab of 73 984 bytes: the forward and the second backward launch ask for more than the 64 KB of dynamic LDS
 # a launch gets by default.  (2, 37, 112): Hp above 64, so a second 64-column slab pass whose last wave has no column tile, zero fill at
-# col >= Hp, and a partial k-block in the second GEMM
-STEP_SHAPES = [(1, 16, 32), (3, 37, 64), (2, 170, 64), (1, 266, 64), (2, 37, 112)]
+# col >= Hp, and a partial k-block in the second GEMM.  (1, 16, 16): one column tile, so three of the four waves skip the mix, and the second
+# GEMM's K = 16 is less than one 64-wide k-block; (3, 37, 48): three column tiles, one wave idle, K = 96 .. 192; (2, 37, 128): two full
+# 64-column slabs, K up to 512 — with two fixed supports and two tiles forced, 96 000 bytes of LDS on a 48-node graph
+STEP_SHAPES = [(1, 16, 32), (3, 37, 64), (2, 170, 64), (1, 266, 64), (2, 37, 112), (1, 16, 16), (3, 37, 48), (2, 37, 128)]
 VARIANTS = [(1, 1, 1), (4, 2, 2), (4, 1, 0), (1, 2, 2)]          # (kept states K, fixed supports, row tiles per workgroup: 0 = the kernel's choice)
 T2, T1 = 2, 1                # two steps in the seq tensors, the launch works on the second: a wrong (t, b) row offset shows
 
@@ -50,6 +57,10 @@ def test_step_shapes_reach_beyond_64_kb_of_lds():
     assert all(v("gptst_msdr_lds_bytes", N, Hp, B, 3) <= 64 * 1024 for B, N, Hp in STEP_SHAPES[:2])
     assert v("gptst_msdr_lds_bytes", 170, 64, 2, 2) == 64768 <= 64 * 1024 < v("gptst_msdr_lds_bytes", 170, 64, 2, 3)      # two fixed supports: above, too
     assert v("gptst_msdr_groups", 266, 1, 0) == 17 and v("gptst_msdr_groups", 266, 1, 2) == 9 and v("gptst_msdr_groups", 16, 1, 2) == 1
+    # the widest rows at a small graph: served, below 64 KB as the launch plans it (B = 2: one tile a workgroup) with one, two and three supports
+    assert [v("gptst_msdr_lds_bytes", 37, 128, 2, ks) for ks in (1, 2, 3)] == [(48 * 68 + 16 * ((ks + 1) * 128 + 4) + 16 * 132) * 4 for ks in (1, 2, 3)]
+    assert 0 < v("gptst_msdr_lds_bytes", 37, 128, 2, 3) == 54528 <= 64 * 1024 < (48 * 68 + 32 * (4 * 128 + 4) + 32 * 132) * 4 == 96000 <= H.LDS_MAX
+    assert all(0 < v("gptst_msdr_lds_bytes", N, Hp, B, 3) <= 64 * 1024 for B, N, Hp in STEP_SHAPES[5:])
 
 
 def _step_inputs(B, N, Hp, K, S, tiles, seed):
@@ -65,9 +76,8 @@ def _step_inputs(B, N, Hp, K, S, tiles, seed):
                            mixes=lambda x, Ls: torch.cat([x] + [torch.matmul(Lk, x.view(B, N, -1)).reshape(B * N, -1) for Lk in Ls], dim=1))
 
 
-@pytest.mark.parametrize("K,S,tiles", VARIANTS)
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_fwd(B, N, Hp, K, S, tiles, parity):
+# each launch at one shape and variant -> (what it wrote, its errors against the fp64 formula); a repeated launch is bit-equal
+def _fwd(B, N, Hp, K, S, tiles):
     s = _step_inputs(B, N, Hp, K, S, tiles, N + Hp + K)
     Wh, W2 = s.rn(Hp, (s.ks + 1) * Hp) / (3 * Hp) ** 0.5, s.rn(Hp, Hp) / Hp ** 0.5
     bvec, R, w, w2, wr = s.rn(N, Hp), s.rn(K, N, Hp), s.rn(N, Hp) / (N * Hp) ** 0.5, s.rn(N, Hp), s.rn(K)
@@ -78,39 +88,45 @@ def test_step_fwd(B, N, Hp, K, S, tiles, parity):
     M = s.mixes(Hs[T1 + K - 1], s.L)
     c = F.leaky_relu(M @ Wh.t() + s.seq(Gx))
     o = (c @ W2.t()).view(B, N, Hp) + bvec + (a.t()[:, :, None, None] * xs).sum(0)
-    hs, sg, sg2 = _g(Hs), _g(sig), torch.full((T2 + K, B, s.G), SENT, device=DEV)
-    hs[T1 + K], sg[T1 + K] = SENT, SENT
-    cc, z, att = (torch.full(shape, SENT, device=DEV) for shape in ((s.rows, Hp), (s.rows, (s.ks + 1) * Hp), (T2, B, K)))
-    ops.msdr_fwd_step(s.Lp, _g(Wh), _g(W2), _g(bvec), _g(R), _g(w), _g(wr), _g(Gx), hs, sg, T1, B, T2, N, w2=_g(w2), sig2=sg2, c=cc, z=z,
-                      a=att, tiles=tiles)
-    torch.cuda.synchronize()
+
+    def run():
+        hs, sg, sg2 = _g(Hs), _g(sig), torch.full((T2 + K, B, s.G), SENT, device=DEV)
+        hs[T1 + K], sg[T1 + K] = SENT, SENT
+        cc, z, att = (torch.full(shape, SENT, device=DEV) for shape in ((s.rows, Hp), (s.rows, (s.ks + 1) * Hp), (T2, B, K)))
+        ops.msdr_fwd_step(s.Lp, _g(Wh), _g(W2), _g(bvec), _g(R), _g(w), _g(wr), _g(Gx), hs, sg, T1, B, T2, N, w2=_g(w2), sig2=sg2, c=cc, z=z,
+                          a=att, tiles=tiles)
+        torch.cuda.synchronize()
+        return hs, sg, sg2, cc, z, att
+    (hs, sg, sg2, cc, z, att), again = run(), run()
+    assert all(torch.equal(x, y) for x, y in zip((hs, sg, sg2, cc, z, att), again))
     errs = {"o": _err(hs[T1 + K], o.view(B * N, Hp)), "c": _err(s.seq(cc), c), "z": _err(s.seq(z), M), "a": _err(att[T1], a),
             "sigma": _err(sg[T1 + K].sum(-1), (o * w).sum((1, 2))), "sigma2": _err(sg2[T1 + K].sum(-1), (o * w2).sum((1, 2)))}
-    _check(parity, errs)
     keep = [i for i in range(T2 + K) if i != T1 + K]                              # nothing outside the step's own block is written
     assert torch.equal(hs[keep], _g(Hs)[keep]) and torch.equal(sg[keep], _g(sig)[keep]) and bool((sg2[keep] == SENT).all())
     assert all(bool((x.view(T2, -1)[0] == SENT).all()) for x in (cc, z, att))
+    return (hs, sg, sg2, cc, z, att), errs
 
 
-@pytest.mark.parametrize("K,S,tiles", VARIANTS)
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_bwd_pre(B, N, Hp, K, S, tiles, parity):
+def _bwd_pre(B, N, Hp, K, S, tiles):
     s = _step_inputs(B, N, Hp, K, S, tiles, N + Hp + K + 1)
     W, R, Hs, dH, c = s.rn(Hp, Hp) / Hp ** 0.5, s.rn(K, N, Hp), s.rn(T2 + K, B * N, Hp), s.rn(T2 + K, B * N, Hp), s.rn(s.rows, Hp)
     dO = dH[K + T1]
     dpre = (dO @ W.t()) * torch.where(s.seq(c) > 0, 1.0, 0.01)
     xs = Hs[T1:T1 + K].view(K, B, N, Hp) + R[:, None]
     dA = (dO.view(1, B, N, Hp) * xs).sum((2, 3)).t()                              # (B, K)
-    dp, pa = torch.full((s.rows, Hp), SENT, device=DEV), torch.full((B, s.G, 8), SENT, device=DEV)
-    ops.msdr_bwd_pre(_g(W), _g(R), _g(Hs), _g(dH), _g(c), dp, pa, T1, B, T2, N, tiles=tiles)
-    torch.cuda.synchronize()
-    _check(parity, {"dpre": _err(s.seq(dp), dpre), "dA": _err(pa[:, :, :K].sum(1), dA)})
+
+    def run():
+        dp, pa = torch.full((s.rows, Hp), SENT, device=DEV), torch.full((B, s.G, 8), SENT, device=DEV)
+        ops.msdr_bwd_pre(_g(W), _g(R), _g(Hs), _g(dH), _g(c), dp, pa, T1, B, T2, N, tiles=tiles)
+        torch.cuda.synchronize()
+        return dp, pa
+    (dp, pa), again = run(), run()
+    assert torch.equal(dp, again[0]) and torch.equal(pa, again[1])
     assert bool((dp.view(T2, -1)[0] == SENT).all()) and bool((pa[:, :, K:] == SENT).all())
+    return (dp, pa), {"dpre": _err(s.seq(dp), dpre), "dA": _err(pa[:, :, :K].sum(1), dA)}
 
 
-@pytest.mark.parametrize("K,S,tiles", VARIANTS)
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_bwd_state(B, N, Hp, K, S, tiles, parity):
+def _bwd_state(B, N, Hp, K, S, tiles):
     s = _step_inputs(B, N, Hp, K, S, tiles, N + Hp + K + 2)
     WhT, w = s.rn(Hp, (s.ks + 1) * Hp) / (3 * Hp) ** 0.5, s.rn(N, Hp)
     a, pa, dpre, dH = torch.softmax(s.rn(T2, B, K), dim=-1), s.rn(B, s.G, 8), s.rn(s.rows, Hp), s.rn(T2 + K, B * N, Hp)
@@ -122,12 +138,51 @@ def test_step_bwd_state(B, N, Hp, K, S, tiles, parity):
     for k in range(K):
         want[T1 + k] += (a[T1][:, k, None, None] * dO + de[:, k, None, None] * w).view(B * N, Hp)
     want[T1 + K - 1] += dh
-    got, dev = _g(dH), torch.full((T2, B, K), SENT, device=DEV)
-    ops.msdr_bwd_state(s.LpT, _g(WhT), _g(w), _g(a), _g(pa), _g(dpre), got, dev, T1, B, T2, N, tiles=tiles)
-    torch.cuda.synchronize()
-    _check(parity, {"dH": _err(got[T1:T1 + K], want[T1:T1 + K]), "de": _err(dev[T1], de)})
+
+    def run():
+        got, dev = _g(dH), torch.full((T2, B, K), SENT, device=DEV)
+        ops.msdr_bwd_state(s.LpT, _g(WhT), _g(w), _g(a), _g(pa), _g(dpre), got, dev, T1, B, T2, N, tiles=tiles)
+        torch.cuda.synchronize()
+        return got, dev
+    (got, dev), again = run(), run()
+    assert torch.equal(got, again[0]) and torch.equal(dev, again[1])
     rest = [i for i in range(T2 + K) if not T1 <= i < T1 + K]
     assert torch.equal(got[rest], _g(dH)[rest]) and bool((dev[0] == SENT).all())
+    return (got, dev), {"dH": _err(got[T1:T1 + K], want[T1:T1 + K]), "de": _err(dev[T1], de)}
+
+
+@pytest.mark.parametrize("K,S,tiles", VARIANTS)
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_fwd(B, N, Hp, K, S, tiles, parity):
+    _check(parity, _fwd(B, N, Hp, K, S, tiles)[1])
+
+
+@pytest.mark.parametrize("K,S,tiles", VARIANTS)
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_bwd_pre(B, N, Hp, K, S, tiles, parity):
+    _check(parity, _bwd_pre(B, N, Hp, K, S, tiles)[1])
+
+
+@pytest.mark.parametrize("K,S,tiles", VARIANTS)
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_bwd_state(B, N, Hp, K, S, tiles, parity):
+    _check(parity, _bwd_state(B, N, Hp, K, S, tiles)[1])
+
+
+@pytest.mark.parametrize("B,rule", [(128, 1), (129, 2)])
+def test_the_kernel_s_own_tile_count_at_its_boundary(B, rule, parity):
+    """tiles = 0 leaves the rows per workgroup to the launch: two 16-node tiles once B ceil(tiles / 2) exceeds 256.  37 nodes are 3 tiles, so
+    B = 128 gives 256 (one tile a workgroup: 3 workgroups a sample) and B = 129 gives 258 (two: 2 workgroups).  Every launch of a step, left to
+    the rule, writes bit for bit what it writes with that tile count forced — the partials have the rule's length — within TOL of fp64.  One
+    kept state, one support, one column tile"""
+    N, Hp, K, S = 37, 16, 1, 0
+    assert ops.msdr_groups(N, 128, 0) == 3 and ops.msdr_groups(N, 129, 0) == 2
+    assert ops.msdr_groups(N, B, 0) == ops.msdr_groups(N, B, rule) == 4 - rule != ops.msdr_groups(N, B, 3 - rule)
+    for launch in (_fwd, _bwd_pre, _bwd_state):
+        own, errs = launch(B, N, Hp, K, S, 0)
+        forced, _ = launch(B, N, Hp, K, S, rule)
+        assert all(x.shape == y.shape and torch.equal(x, y) for x, y in zip(own, forced)), launch.__name__
+        _check(parity, {launch.__name__[1:] + "." + k: v for k, v in errs.items()})
 
 
 # ---- 2. whole models against fp64 torch ----------------------------------------------------------------------------------------------------

@@ -6,7 +6,10 @@ element-wise one, 1e-4 of the reference tensor's largest magnitude, for every ou
 The max and near-ties are handled as in test_gpu_stsgcn_hip.py: an element is ambiguous if its top-two gap on the fp64 reference is below
 GAP = 1e-5 of the largest candidate magnitude; gradient comparisons of whole models use shapes and seeds for which the test asserts ZERO
 ambiguous elements (the seeds were chosen on the CPU); the full confs are compared on the forward only.  The candidate error measured here is
-recorded as ``cand``."""
+recorded as ``cand``.
+
+The mix runs at the widths 16, 32, 48, 64, 80, 112 and 128 (one column tile, full 32-channel groups, a half-filled last group behind one to
+three full ones, four groups), at 128 with 3 and with 20 node tiles, as test_gpu_stsgcn_hip.py holds the same slab product."""
 import copy
 import logging
 from types import SimpleNamespace
@@ -44,7 +47,10 @@ MIX = [(3, 3, 20, 64),            # a padded tile; frames fed by one to four blo
        (1, 9, 20, 32),            # the conf's window count
        (1, 1, 170, 64), (1, 1, 266, 64),          # shipped node counts: 11 and 17 node tiles (the last workgroup has waves without a tile)
        (1, 2, 305, 16),           # 20 node tiles, the last with ONE real node
-       (1, 1, 448, 16)]           # the largest node count served: 63 KB of LDS
+       (1, 1, 448, 16),           # the largest node count served: 63 KB of LDS
+       (3, 9, 37, 128),           # the widest rows (four channel groups) at the conf's window count, three samples
+       (2, 3, 37, 80), (2, 3, 37, 112),           # a half-filled last group behind two and three full ones
+       (1, 1, 320, 128)]          # 20 node tiles at the widest rows
 
 
 @pytest.mark.parametrize("B,W,N,c", MIX)
@@ -63,10 +69,14 @@ def test_mix_every_form(B, W, N, c, parity):
             "e2e_adj": fu.mix_expanded(S.t(), D.t(), E), "m2e": fu.mix_m2e(S.t(), M), "e2f": fu.mix_e2f(S.t(), D.t(), E)}
     sp, dp, spt, dpt = _pad(S), _pad(D), _pad(S.t()), _pad(D.t())
     Hd, Ed, Md = _dev(Hf, B * T * N, c), _dev(E, B * W * 4 * N, c), _dev(M, B * W * N, c)
-    got = {"f2e": ops.stfgnn_mix(sp, dp, Hd, ops.MIX_F2E, B, T, N), "e2e": ops.stfgnn_mix(sp, dp, Ed, ops.MIX_E2E, B, T, N),
-           "e2m": ops.stfgnn_mix(sp, dp, Ed, ops.MIX_E2M, B, T, N), "e2e_adj": ops.stfgnn_mix(spt, dpt, Ed, ops.MIX_E2E, B, T, N),
-           "m2e": ops.stfgnn_mix(spt, dpt, Md, ops.MIX_M2E, B, T, N), "e2f": ops.stfgnn_mix(spt, dpt, Ed, ops.MIX_E2F, B, T, N)}
+
+    def run():
+        return {"f2e": ops.stfgnn_mix(sp, dp, Hd, ops.MIX_F2E, B, T, N), "e2e": ops.stfgnn_mix(sp, dp, Ed, ops.MIX_E2E, B, T, N),
+                "e2m": ops.stfgnn_mix(sp, dp, Ed, ops.MIX_E2M, B, T, N), "e2e_adj": ops.stfgnn_mix(spt, dpt, Ed, ops.MIX_E2E, B, T, N),
+                "m2e": ops.stfgnn_mix(spt, dpt, Md, ops.MIX_M2E, B, T, N), "e2f": ops.stfgnn_mix(spt, dpt, Ed, ops.MIX_E2F, B, T, N)}
+    got, again = run(), run()
     torch.cuda.synchronize()
+    assert all(torch.equal(got[k], again[k]) for k in want)                                              # fixed summation order: bit-equal
     assert all(got[k].shape == (want[k].numel() // c, c) for k in want)
     f2e, e2e = got["f2e"].view(B, W, 4, N, c), got["e2e"].view(B, W, 4, N, c)
     assert torch.equal(f2e[:, :, 0], f2e[:, :, 3]) and torch.equal(e2e[:, :, 0], e2e[:, :, 3])          # one product, written to both blocks

@@ -3,9 +3,20 @@ definition in tests/stgode_util.py, which tests/test_stgode_hip_cpu.py holds to 
 the REFERENCE's z, X and winner index cast to fp32, so a kernel-level gradient has no decision of its own to get wrong.  The error measure and
 its bound are the project's (downstream_util: largest absolute error over the reference's largest magnitude, below 1e-4).
 
-Shapes: N 20 (padding to a tile), 33 (one row in the last tile), 170 / 207 / 250 / 266 (the shipped tilings, at B 1, T 2), 448 (the bound; 449
-is refused); T 1, 5, 12; B 1, 3; C 16, 64.  No kernel caps its grid, but a batch-norm workgroup walks its split of a node's rows 256 float4
-at a time: at (B, T, C) = (3, 12, 64) a node has 36 rows in 2 splits of 18 rows = 288 float4, so that loop runs twice."""
+Shapes: N 20 (padding to a tile), 33 (one row in the last tile), 37, 170 / 207 / 250 / 266 (the shipped tilings, at B 1, T 2), 448 (the bound;
+449 is refused, and 448 runs at C 16 and at C 128); T 1, 5, 12 and 32 (the bound: a full row of M in LDS; 33 is refused); B 1, 3.
+Widths: every multiple of 16 up to 128 — the step walks 32-channel groups, so 16 is one column tile, 32 and 64 full groups, 48 / 80 / 112 a
+half-filled last group behind one to three full ones, 96 and 128 three and four groups (all eight of the wave's register slots, a 64 KB W);
+the whole model runs at the block widths 32, 48, 64 and 128.
+Splits, each asserted through the entry that plans it, so a moved rule fails the test rather than leaving the path unreached:
+the reductions chunk the nodes by clamp(6144 / (T (C + 1)), 1, 8): 8 and 7 nodes at the small shapes, 3 at (T, C) = (12, 128) (7 chunks of
+20 nodes, the last with 2) and 1 at (32, 128) (17 chunks, the tile's tightest fit); the weight gradient gives a split one 64-row chunk until
+the chunks outnumber 1024 / tiles: 16453 rows at C 128 are 129 splits of 2 chunks (the last chunk 5 rows), 65605 rows at C 64 are 513, so
+the body's prefetch of the next chunk runs under the relu source; the batch norm splits a node's R = B T rows into min(ceil(R / 32), 32):
+1 and 2 at the small shapes, 2 unequal ones (17 and 16 rows) at R = 33, 24 at R = 768 (the shipped batch of 64 x 12) and the cap 32 at
+R = 1100 (35 rows a split, the last 15).  No kernel caps its grid, but a batch-norm workgroup walks its split of a node's rows 256 float4
+at a time: at (B, T, C) = (3, 12, 64) a node has 36 rows in 2 splits of 18 rows = 288 float4, so that loop runs twice; at (100, 11, 64) a
+split is 560 float4 and it runs three times."""
 import copy
 import logging
 from types import SimpleNamespace
@@ -48,11 +59,21 @@ def _step_case(B, T, N, C, seed=0):
 
 
 # ---- 1. the launches against their definitions ---------------------------------------------------------------------------------------------
-STEP_CASES = [(3, 5, 20, 16), (1, 12, 33, 64), (3, 1, 20, 64), (1, 2, 170, 64), (1, 2, 207, 64), (1, 2, 250, 64), (1, 2, 266, 64), (1, 1, 448, 16)]
+STEP_CASES = [(3, 5, 20, 16), (1, 12, 33, 64), (3, 1, 20, 64), (1, 2, 170, 64), (1, 2, 207, 64), (1, 2, 250, 64), (1, 2, 266, 64), (1, 1, 448, 16),
+              # the other widths: one full group, a half-filled last group behind 1, 2, 3 full ones, three and four groups
+              (2, 3, 20, 32), (2, 3, 37, 48), (1, 3, 20, 80), (1, 2, 37, 96), (2, 3, 37, 112), (1, 3, 20, 128),
+              (1, 2, 170, 128),            # a shipped node count: 11 node tiles, a last workgroup with idle waves
+              (1, 1, 448, 128),            # the largest slab with four channel groups
+              (1, 32, 20, 16),             # T at its bound
+              (1, 32, 17, 128),            # one node per reduce chunk, 17 chunks
+              (1, 12, 20, 128)]            # three nodes per reduce chunk, the last chunk holds 2
+REDUCE_PARTS = {(1, 32, 17, 128): 17, (1, 12, 20, 128): 7, (3, 5, 20, 16): 3, (1, 12, 33, 64): 5}      # 1, 3, 8 and 7 nodes per chunk
 
 
 @pytest.mark.parametrize("B,T,N,C", STEP_CASES)
 def test_step_forward_backward_and_reductions(B, T, N, C, parity):
+    if (B, T, N, C) in REDUCE_PARTS:
+        assert _C.lib().value("gptst_stgode_reduce_nparts", C, T, N) == REDUCE_PARTS[(B, T, N, C)]
     A, X, alpha, W, W2, dz = _step_case(B, T, N, C)
     z, At, _ = gu.step_fwd(X, A, alpha, W, W2)
     g = dz * (z > 0)
@@ -98,11 +119,35 @@ def test_step_refuses_more_nodes_than_its_slab_holds():
     assert rc == _C.ESHAPE
 
 
-BN_CASES = [(3, 12, 20, 64), (1, 5, 33, 16), (3, 1, 20, 16), (1, 2, 170, 64)]
+@pytest.mark.parametrize("rows,C,nsplit", [(16453, 128, 129), (65605, 64, 513)])
+def test_weight_gradient_with_two_chunks_per_split(rows, C, nsplit, parity):
+    """the step cases have at most 9 chunks of 64 rows, one per split; the shipped batch has 2040.  16453 rows at C 128: 258 chunks over 4 output
+    tiles are 129 splits of 2 chunks, the last chunk with 5 rows; 65605 rows at C 64: 1026 chunks over one tile are 513 splits of 2 — so every
+    workgroup fetches its second chunk while the first is in LDS.  X is a pre-activation of mixed sign: the relu is the kernel's"""
+    assert _C.lib().value("gptst_stgode_wgrad_nsplit", rows, C) == nsplit and (rows + 63) // 64 == 2 * nsplit and rows % 64 == 5
+    g = torch.Generator().manual_seed(rows)
+    X, G = (torch.randn(rows, C, dtype=torch.float64, generator=g) for _ in range(2))
+    assert 0.4 < float((X > 0).double().mean()) < 0.6
+    want = torch.relu(X).t() @ G
+    Xd, Gd = _d(X), _d(G)
+    got, again = ops.stgode_wgrad(Gd, Xd), ops.stgode_wgrad(Gd, Xd)
+    assert torch.equal(got, again)
+    _check(parity, {"dW": _err(got, want)})
+    assert _err(X.t() @ G, want) > 10 * TOL and _err(want.t(), want) > 10 * TOL            # (a missing relu or a transposed result must not pass)
+
+
+BN_CASES = [(3, 12, 20, 64), (1, 5, 33, 16), (3, 1, 20, 16), (1, 2, 170, 64),
+            (2, 3, 20, 32), (3, 5, 33, 48), (2, 12, 20, 128),        # the other widths
+            (64, 12, 20, 16),              # R = 768 rows a node: 24 splits, the shipped batch's fold
+            (100, 11, 20, 64),             # R = 1100: the cap of 32 splits, 35 rows each and 15 in the last; 560 float4 a split: three passes of the row loop
+            (3, 11, 20, 16)]               # R = 33: splits of 17 and 16 rows
+BN_SPLITS = {3: 1, 5: 1, 36: 2, 33: 2, 768: 24, 1100: 32}                  # R = B T -> splits
 
 
 @pytest.mark.parametrize("B,T,N,C", BN_CASES)
 def test_batch_norm_kernels(B, T, N, C, parity):
+    if B * T in BN_SPLITS:
+        assert _C.lib().value("gptst_stgode_bn_nsplit", B * T) == BN_SPLITS[B * T]
     g = torch.Generator().manual_seed(1)
     z = torch.relu(torch.randn(B, T, N, C, dtype=torch.float64, generator=g) + 0.3)
     gamma, beta = torch.rand(N, dtype=torch.float64, generator=g) + 0.5, torch.randn(N, dtype=torch.float64, generator=g)
@@ -129,30 +174,33 @@ def test_batch_norm_kernels(B, T, N, C, parity):
 
 def test_batch_norm_statistics_do_not_cancel(parity):
     """z = 100 + randn: the fp32 sum of squares minus the squared mean loses the variance (1 against 1e4 at 24 bits: an error of 1e-3 and more);
-    the two-pass splits folded by Chan's update keep it to 1e-5 relative.  And a node that is all zero after the relu: variance 0, eps decides"""
-    B, T, N, C = 3, 12, 20, 64
-    g = torch.Generator().manual_seed(2)
-    z = (100 + torch.randn(B, T, N, C, generator=g)).double()             # fp32 values: the statistics of exactly what the kernel reads
-    z[:, :, 3] = 0
-    gamma, beta = torch.ones(N, dtype=torch.float64), torch.full((N,), 0.25, dtype=torch.float64)
-    y, mean, var, _ = gu.bn_fwd(z, gamma, beta)
-    zd = _d(z.reshape(-1, C))
-    rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
-    yy, mm, rr = ops.stgode_bn_apply(zd, ops.stgode_bn_stats(zd, B, T, N), _d(gamma), _d(beta), rm, rv, True, 0.1, 1e-5, B, T, N, keep=True)
-    var_got = 1 / rr.double().cpu() ** 2 - 1e-5
-    live = torch.arange(N) != 3
-    rel = float(((var_got - var).abs() / var.clamp_min(1e-30))[live].max())
-    naive = z.float().pow(2).mean((0, 1, 3)) - z.float().mean((0, 1, 3)).pow(2)
-    parity("var_rel", rel)
-    print("relative error of the variance: %.2e (fp32 E[x^2] - E[x]^2 here: %.2e)" % (rel, float(((naive.double() - var).abs() / var.clamp_min(1e-30))[live].max())))
-    assert rel < 1e-5
-    assert float(mm[3]) == 0.0 and abs(float(rr[3]) - 1e-5 ** -0.5) < 1e-2 and bool((yy.view(B, T, N, C)[:, :, 3] == 0.25).all())
-    assert abs(float(rv[3]) - 0.9) < 1e-6 and abs(float(rm[3])) == 0.0
-    _check(parity, {"y": _err(yy.view(y.shape), y)})
+    the two-pass splits folded by Chan's update keep it to 1e-5 relative.  And a node that is all zero after the relu: variance 0, eps decides.
+    At 2 splits of 18 rows and at the cap, 32 splits of 35 rows with 15 in the last: the bound comes from the two passes of a split and the
+    fold in double, not from the number of splits"""
+    for (B, T, N, C), tag in (((3, 12, 20, 64), ""), ((100, 11, 20, 64), "_r1100")):
+        assert _C.lib().value("gptst_stgode_bn_nsplit", B * T) == BN_SPLITS[B * T]
+        g = torch.Generator().manual_seed(2)
+        z = (100 + torch.randn(B, T, N, C, generator=g)).double()         # fp32 values: the statistics of exactly what the kernel reads
+        z[:, :, 3] = 0
+        gamma, beta = torch.ones(N, dtype=torch.float64), torch.full((N,), 0.25, dtype=torch.float64)
+        y, mean, var, _ = gu.bn_fwd(z, gamma, beta)
+        zd = _d(z.reshape(-1, C))
+        rm, rv = torch.zeros(N, device=DEV), torch.ones(N, device=DEV)
+        yy, mm, rr = ops.stgode_bn_apply(zd, ops.stgode_bn_stats(zd, B, T, N), _d(gamma), _d(beta), rm, rv, True, 0.1, 1e-5, B, T, N, keep=True)
+        var_got = 1 / rr.double().cpu() ** 2 - 1e-5
+        live = torch.arange(N) != 3
+        rel = float(((var_got - var).abs() / var.clamp_min(1e-30))[live].max())
+        naive = z.float().pow(2).mean((0, 1, 3)) - z.float().mean((0, 1, 3)).pow(2)
+        parity("var_rel" + tag, rel)
+        print("R = %d: relative error of the variance: %.2e (fp32 E[x^2] - E[x]^2 here: %.2e)"
+              % (B * T, rel, float(((naive.double() - var).abs() / var.clamp_min(1e-30))[live].max())))
+        assert rel < 1e-5
+        assert float(mm[3]) == 0.0 and abs(float(rr[3]) - 1e-5 ** -0.5) < 1e-2 and bool((yy.view(B, T, N, C)[:, :, 3] == 0.25).all())
+        assert abs(float(rv[3]) - 0.9) < 1e-6 and abs(float(rm[3])) == 0.0
+        _check(parity, {"y" + tag: _err(yy.view(y.shape), y)})
 
 
-def test_running_max_ties_and_routing(parity):
-    B, T, N, C = 3, 5, 20, 16
+def _running_max_case(B, T, N, C, parity, tag):
     g = torch.Generator().manual_seed(3)
     zs = [torch.relu(torch.randn(B, T, N, C, dtype=torch.float64, generator=g)) for _ in range(3)]
     gamma, beta = torch.rand(N, dtype=torch.float64, generator=g) + 0.5, torch.randn(N, dtype=torch.float64, generator=g)
@@ -183,23 +231,33 @@ def test_running_max_ties_and_routing(parity):
     best2, which2, _ = fold(zs)
     assert torch.equal(best, best2) and torch.equal(which, which2)
     assert torch.equal(which.cpu().view(wwhich.shape), wwhich) and set(wwhich.unique().tolist()) == {0, 1, 2}
-    errs = {"best": _err(best.view(wbest.shape), wbest)}
+    errs = {"best" + tag: _err(best.view(wbest.shape), wbest)}
     wd = wwhich.to(DEV).view(-1, C).contiguous()
     for i, (zd, _, _) in enumerate(stats):
         dz, dgam, dbet = gu.bn_bwd(dB * (wwhich == i), zs[i], gamma, ys[i][1], ys[i][2])
         G, dg, db = ops.stgode_bn_bwd(None, zd, gd, _d(ys[i][1]), _d(1 / torch.sqrt(ys[i][2] + 1e-5)), B, T, N, dBest=_d(dB.reshape(-1, C)), which=wd, idx=i)
-        errs.update({"g%d" % i: _err(G.view(dz.shape), dz * (zs[i] > 0)), "dgamma%d" % i: _err(dg, dgam), "dbeta%d" % i: _err(db, dbet)})
+        errs.update({"g%d%s" % (i, tag): _err(G.view(dz.shape), dz * (zs[i] > 0)), "dgamma%d%s" % (i, tag): _err(dg, dgam),
+                     "dbeta%d%s" % (i, tag): _err(db, dbet)})
     _check(parity, errs)
 
 
+def test_running_max_ties_and_routing(parity):
+    """at one column tile and at the widest rows (128 channels: 32 float4 a row)"""
+    _running_max_case(3, 5, 20, 16, parity, "")
+    _running_max_case(2, 3, 20, 128, parity, "_c128")
+
+
 # ---- 2. the whole model ----------------------------------------------------------------------------------------------------------------------
-def _ref(N, T, n_layers, dim_out=1, seed=0, B=1, ap=None, P=3):
-    """(fp64 torch module on the CPU under the xavier-style redraw, x, w)"""
+def _ref(N, T, n_layers, dim_out=1, seed=0, B=1, ap=None, P=3, width=64):
+    """(fp64 torch module on the CPU under the xavier-style redraw, x, w); ``width``: the blocks' width = the input's (the temporal nets stay in
+    their identity form), with the middle level at half of it as in the confs"""
     torch.manual_seed(seed)
-    m64 = STGODE(gu.model_args(N, T=T, P=P, n_layers=n_layers) if ap is None else ap, "cpu", 64, dim_out)
+    if ap is None:
+        ap = gu.model_args(N, T=T, P=P, n_layers=n_layers, out_channels=(width, width // 2, width), in_channels=width)
+    m64 = STGODE(ap, "cpu", width, dim_out)
     gu.xavier_redraw_(m64)
     m64 = m64.double().train()
-    x = torch.randn(B, T, N, 64, dtype=torch.float64)
+    x = torch.randn(B, T, N, width, dtype=torch.float64)
     return m64, x, torch.randn(B, m64.horizon, N, dim_out, dtype=torch.float64)
 
 
@@ -220,24 +278,27 @@ def _run(m, x, w):
     return out
 
 
-# (dim_out, seed) for which the fp64 reference is unambiguous: no max gap <= g, no step pre-activation and no block input within g of zero, g =
-# 1e-5 of the largest magnitude.  Searched on the CPU over the seeds 0 .. 39 of this shape (n_layers 1, B 1, N 20, T 4:
-# 5120 elements per block, 4 blocks): `_ref(20, 4, 1, dim_out, seed)` then `gu.unambiguous(gu.model_manual(m64, x), x)`; one seed in five to ten
-# comes out clean here: (0, 0, 0) for dim_out 1 at the seeds 8, 15, 26, 34, for dim_out 2 at 3, 7, 19, 21, 24, 33, 36; the first are taken.  The
-# test asserts the condition on the reference alone, before anything runs on the GPU.
-SMALL = [(1, 8), (2, 3)]
+# (dim_out, seed, width) for which the fp64 reference is unambiguous: no max gap <= g, no step pre-activation and no block input within g of
+# zero, g = 1e-5 of the largest magnitude.  Searched on the CPU over the seeds 0 .. 39 of this shape (n_layers 1, B 1, N 20,
+# T 4: 80 width elements per block, 4 blocks): `_ref(20, 4, 1, dim_out, seed, width=width)` then `gu.unambiguous(gu.model_manual(m64, x), x)`;
+# one seed in five to ten comes out clean at width 64: (0, 0, 0) for dim_out 1 at the seeds 8, 15, 26, 34, for dim_out 2 at 3, 7, 19, 21, 24, 33,
+# 36.  At the other widths, dim_out 1: 128 (twice the elements: fewer clean seeds) at 24, 33; 48 at 1, 3, 16, 23, 24, 29, 35; 32 at 3, 5, 6, 7,
+# 8, ...  The first of each are taken.  The test asserts the condition on the reference alone, before anything runs on the GPU.
+SMALL = [pytest.param(1, 8, 64, id="1-8"), pytest.param(2, 3, 64, id="2-3"), pytest.param(1, 24, 128, id="1-24-w128"),
+         pytest.param(1, 1, 48, id="1-1-w48"), pytest.param(1, 3, 32, id="1-3-w32")]
 
 
-@pytest.mark.parametrize("dim_out,seed", SMALL)
-def test_small_model_against_fp64_torch(dim_out, seed, parity):
-    m64, mh, x, w = _pair(20, 4, 1, dim_out, seed)
+@pytest.mark.parametrize("dim_out,seed,width", SMALL)
+def test_small_model_against_fp64_torch(dim_out, seed, width, parity):
+    m64, mh, x, w = _pair(20, 4, 1, dim_out, seed, width=width)
+    assert m64.out_channels == [width, width // 2, width] and x.shape[3] == width
     res = gu.model_manual(m64, x)
     assert gu.unambiguous(res, x) == (0, 0, 0)
     for bn in (b.batch_norm for s, _ in m64.branches() for b in s):
         assert int(bn.num_batches_tracked) == 0                              # (model_manual ran no module)
     want = _run(m64, x, w)
     got = _run(mh, _d(x), _d(w))
-    assert m64.backend_used == "torch" and mh.backend_used == "hip" and set(got) == set(want) and len(want) == 4 * 7 + 4 + 2      # 4 blocks x (5 ode + 2 bn), the heads, y and dx
+    assert m64.backend_used == "torch" and mh.backend_used == "hip" and set(got) == set(want) and len(want) == 4 * 7 + 4 + 2      # 4 blocks x (5 ode + 2 bn), the heads, y and dx: at every width
     assert all(float(v.abs().max()) > 0 for v in want.values())
     dead = [k for k, p in mh.named_parameters() if gu.is_dead(k)]
     assert len(dead) == 48 and all(p.grad is None for k, p in mh.named_parameters() if gu.is_dead(k))
@@ -265,6 +326,19 @@ def test_shipped_configuration_forward_against_fp64_torch(ds, parity):
     sp, se = gu.graphs(N)
     m64, mh, x, w = _pair(N, 12, None, dim_out, seed=pa.seed, B=1, ap=SimpleNamespace(**vars(pa), A_sp_wave=sp, A_se_wave=se))
     assert len(m64.state_dict()) == 316 and m64.horizon == 12
+    _forward_and_one_backward(m64, mh, x, w, N, dim_out, parity)
+
+
+def test_width_128_forward_at_a_shipped_node_count(parity):
+    """what the C = 128 pretraining configuration hands the predictor: a 128-wide embedding over 170 nodes and 12 frames (one layer: four
+    blocks, each with four channel groups and the 64 KB W), in the same form as the confs above"""
+    N = 170
+    m64, mh, x, w = _pair(N, 12, 1, 1, seed=0, B=1, P=12, width=128)
+    assert H.supported(mh, _d(x)) and x.shape == (1, 12, N, 128)
+    _forward_and_one_backward(m64, mh, x, w, N, 1, parity)
+
+
+def _forward_and_one_backward(m64, mh, x, w, N, dim_out, parity):
     with torch.no_grad():
         want = m64(x)
     xd = _d(x).requires_grad_(True)

@@ -1,6 +1,10 @@
 """The TGCN predictor on HIP (``TGCN(..., backend="hip")``, csrc/tgcn.hip, predictors/tgcn_hip.py) on the GPU.  The reference of every comparison
 is the torch TGCN module (pinned to the reference implementation's vectors by tests/test_predictor_tgcn.py) or the step's formula, in fp64 on the
-CPU; the bound is the project's element-wise one, 1e-4 of the reference tensor's largest magnitude, for every output, dX and parameter gradient."""
+CPU; the bound is the project's element-wise one, 1e-4 of the reference tensor's largest magnitude, for every output, dX and parameter gradient.
+
+Step shapes: padded widths Hp 16 (one column tile: three waves skip the mix, K below one k-block), 32, 48, 112 and 128 (two full slabs), each
+with one and two row tiles per workgroup forced; the launch's own choice between the two (tiles = 0) is crossed at its boundary, 37 nodes at
+B = 128 and 129, where it must be bit-equal to the forced count it names.  Every launch is run twice and must repeat bit for bit."""
 import logging
 from types import SimpleNamespace
 
@@ -25,8 +29,11 @@ def _g(t):
 
 # ---- 1. the four step launches, each alone -------------------------------------------------------------------------------------------------
 # (1, 461, 112): 464 padded nodes, a slab of 126 208 bytes plus the M tile: every one of the four launches asks for more than the 64 KB of dynamic
-# LDS a launch gets by default, up to 155 392 bytes (backward state, two tiles), just under the 160 KB a workgroup can have
-STEP_SHAPES = [(1, 16, 32), (3, 37, 112), (2, 170, 112), (1, 461, 112)]
+# LDS a launch gets by default, up to 155 392 bytes (backward state, two tiles), just under the 160 KB a workgroup can have.
+# Widths: (1, 16, 16): one column tile, so three of the four waves skip the mix, and K = 16 (32 in the backward state) is less than one
+# 64-wide k-block of the GEMM; (3, 37, 48): three column tiles, one wave idle; 112: a second slab pass with a wave idle and a partial k-block;
+# (2, 37, 128): two full 64-column slabs, K up to 256
+STEP_SHAPES = [(1, 16, 32), (3, 37, 112), (2, 170, 112), (1, 461, 112), (1, 16, 16), (3, 37, 48), (2, 37, 128)]
 T2, T1 = 2, 1                # two steps in the seq tensors, the launch works on the second: a wrong (b, t) row offset shows
 
 
@@ -34,6 +41,9 @@ def test_step_shapes_reach_beyond_64_kb_of_lds():
     v = _C.lib().value
     assert v("gptst_tgcn_lds_bytes", 461, 112, 1) == (464 * 68 + 16 * 228) * 4 > 126208 > 64 * 1024        # (one tile: the plan for B = 1)
     assert all(v("gptst_tgcn_lds_bytes", N, Hp, B) <= 64 * 1024 for B, N, Hp in STEP_SHAPES[:3])
+    # the widest rows at a small graph: served, and on the near side of 64 KB whichever tile count is forced (13 056 + 16 640 a tile)
+    assert 0 < v("gptst_tgcn_lds_bytes", 37, 128, 2) == (48 * 68 + 16 * 260) * 4 == 29696 <= 64 * 1024 and 29696 + 16 * 260 * 4 <= 64 * 1024
+    assert all(0 < v("gptst_tgcn_lds_bytes", N, Hp, B) <= 64 * 1024 for B, N, Hp in STEP_SHAPES[4:])
 
 
 def _step_inputs(B, N, Hp, seed):
@@ -48,9 +58,8 @@ def _step_inputs(B, N, Hp, seed):
                            mix=lambda x: torch.matmul(L, x.view(B, N, -1)).reshape(B * N, -1))
 
 
-@pytest.mark.parametrize("tiles", [1, 2])
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_fwd_gates(B, N, Hp, tiles, parity):
+# each launch at one shape and tile count -> (what it wrote, its errors against the fp64 formula); a repeated launch is bit-equal
+def _fwd_gates(B, N, Hp, tiles):
     s = _step_inputs(B, N, Hp, N + Hp)
     W, h, Gx = s.rn(2 * Hp, Hp) / Hp ** 0.5, s.rn(s.S, Hp), s.rn(s.rows, 2 * Hp)
     M = s.mix(h)
@@ -60,15 +69,14 @@ def test_step_fwd_gates(B, N, Hp, tiles, parity):
     ops.tgcn_fwd_gates(s.Lp, _g(W), _g(h), _g(Gx), T1, u, q, B, T2, N, r=r, z=z, zoff=16, tiles=tiles)
     zz = z.view(B, T2, N, -1)
     assert bool((zz[:, 0] == 7).all()) and bool((zz[:, T1, :, :16] == 7).all())            # only its own block of z is written
-    _check(parity, {"r": _err(r, g[:, :Hp]), "u": _err(u, g[:, Hp:]), "q": _err(q, g[:, :Hp] * h), "m1": _err(s.seq(z.cpu())[:, 16:], M)})
+    errs = {"r": _err(r, g[:, :Hp]), "u": _err(u, g[:, Hp:]), "q": _err(q, g[:, :Hp] * h), "m1": _err(s.seq(z.cpu())[:, 16:], M)}
     u2, q2 = torch.empty_like(u), torch.empty_like(q)
     ops.tgcn_fwd_gates(s.Lp, _g(W), _g(h), _g(Gx), T1, u2, q2, B, T2, N, tiles=tiles)       # nothing kept: the same u and q
     assert torch.equal(u2, u) and torch.equal(q2, q)
+    return (u, q, r, z), errs
 
 
-@pytest.mark.parametrize("tiles", [1, 2])
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_fwd_state(B, N, Hp, tiles, parity):
+def _fwd_state(B, N, Hp, tiles):
     s = _step_inputs(B, N, Hp, N + Hp + 1)
     W, h, q, Gx, u = s.rn(Hp, Hp) / Hp ** 0.5, s.rn(s.S, Hp), s.rn(s.S, Hp), s.rn(s.rows, Hp), torch.sigmoid(s.rn(s.S, Hp))
     M = s.mix(q)
@@ -76,36 +84,78 @@ def test_step_fwd_state(B, N, Hp, tiles, parity):
     hn, ck = (torch.full((s.S, Hp), 7.0, device=DEV) for _ in range(2))
     z = torch.full((s.rows, 16 + Hp), 7.0, device=DEV)
     ops.tgcn_fwd_state(s.Lp, _g(W), _g(q), _g(Gx), T1, _g(u), _g(h), hn, B, T2, N, c=ck, z=z, zoff=16, tiles=tiles)
-    _check(parity, {"c": _err(ck, c), "h": _err(hn, u * h + (1 - u) * c), "m2": _err(s.seq(z.cpu())[:, 16:], M)})
+    errs = {"c": _err(ck, c), "h": _err(hn, u * h + (1 - u) * c), "m2": _err(s.seq(z.cpu())[:, 16:], M)}
     hn2 = torch.empty_like(hn)
     ops.tgcn_fwd_state(s.Lp, _g(W), _g(q), _g(Gx), T1, _g(u), _g(h), hn2, B, T2, N, tiles=tiles)
     assert torch.equal(hn2, hn)
+    return (hn, ck, z), errs
 
 
-@pytest.mark.parametrize("tiles", [1, 2])
-@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
-def test_step_bwd_cand(B, N, Hp, tiles, parity):
+def _bwd_cand(B, N, Hp, tiles):
     s = _step_inputs(B, N, Hp, N + Hp + 2)
     Wt, dh, h = s.rn(Hp, Hp) / Hp ** 0.5, s.rn(s.S, Hp), s.rn(s.S, Hp)
     u, r, c = torch.sigmoid(s.rn(s.S, Hp)), torch.sigmoid(s.rn(s.S, Hp)), torch.tanh(s.rn(s.S, Hp))
     d1 = dh * (1 - u) * (1 - c * c)
     dq = s.mix(d1) @ Wt.t()                                                      # (the launch is handed L^T; here "L" plays that part)
     d0 = torch.cat([dq * h * r * (1 - r), dh * (h - c) * u * (1 - u)], 1)
-    dp1, dp0 = torch.full((s.rows, Hp), 7.0, device=DEV), torch.full((s.rows, 2 * Hp), 7.0, device=DEV)
-    part = torch.empty(s.S, Hp, device=DEV)
-    ops.tgcn_bwd_cand(s.Lp, _g(Wt), _g(dh), _g(u), _g(c), _g(r), _g(h), T1, dp1, dp0, part, B, T2, N, tiles=tiles)
+
+    def run():
+        dp1, dp0 = torch.full((s.rows, Hp), 7.0, device=DEV), torch.full((s.rows, 2 * Hp), 7.0, device=DEV)
+        part = torch.empty(s.S, Hp, device=DEV)
+        ops.tgcn_bwd_cand(s.Lp, _g(Wt), _g(dh), _g(u), _g(c), _g(r), _g(h), T1, dp1, dp0, part, B, T2, N, tiles=tiles)
+        return dp1, dp0, part
+    (dp1, dp0, part), again = run(), run()
+    assert all(torch.equal(x, y) for x, y in zip((dp1, dp0, part), again))
     assert bool((dp1.view(B, T2, N, -1)[:, 0] == 7).all()) and bool((dp0.view(B, T2, N, -1)[:, 0] == 7).all())
-    _check(parity, {"dpre1": _err(s.seq(dp1.cpu()), d1), "dpre0": _err(s.seq(dp0.cpu()), d0), "dh_part": _err(part, dh * u + dq * r)})
+    return (dp1, dp0, part), {"dpre1": _err(s.seq(dp1.cpu()), d1), "dpre0": _err(s.seq(dp0.cpu()), d0), "dh_part": _err(part, dh * u + dq * r)}
+
+
+def _bwd_state(B, N, Hp, tiles):
+    s = _step_inputs(B, N, Hp, N + Hp + 3)
+    Wt, d0, part = s.rn(Hp, 2 * Hp) / Hp ** 0.5, s.rn(s.rows, 2 * Hp), s.rn(s.S, Hp)
+    out, out2 = torch.empty(s.S, Hp, device=DEV), torch.empty(s.S, Hp, device=DEV)
+    ops.tgcn_bwd_state(s.Lp, _g(Wt), _g(d0), _g(part), T1, out, B, T2, N, tiles=tiles)
+    ops.tgcn_bwd_state(s.Lp, _g(Wt), _g(d0), _g(part), T1, out2, B, T2, N, tiles=tiles)
+    assert torch.equal(out, out2)
+    return (out,), {"dh": _err(out, part + s.mix(s.seq(d0)) @ Wt.t())}
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_fwd_gates(B, N, Hp, tiles, parity):
+    _check(parity, _fwd_gates(B, N, Hp, tiles)[1])
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_fwd_state(B, N, Hp, tiles, parity):
+    _check(parity, _fwd_state(B, N, Hp, tiles)[1])
+
+
+@pytest.mark.parametrize("tiles", [1, 2])
+@pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
+def test_step_bwd_cand(B, N, Hp, tiles, parity):
+    _check(parity, _bwd_cand(B, N, Hp, tiles)[1])
 
 
 @pytest.mark.parametrize("tiles", [1, 2])
 @pytest.mark.parametrize("B,N,Hp", STEP_SHAPES)
 def test_step_bwd_state(B, N, Hp, tiles, parity):
-    s = _step_inputs(B, N, Hp, N + Hp + 3)
-    Wt, d0, part = s.rn(Hp, 2 * Hp) / Hp ** 0.5, s.rn(s.rows, 2 * Hp), s.rn(s.S, Hp)
-    out = torch.empty(s.S, Hp, device=DEV)
-    ops.tgcn_bwd_state(s.Lp, _g(Wt), _g(d0), _g(part), T1, out, B, T2, N, tiles=tiles)
-    _check(parity, {"dh": _err(out, part + s.mix(s.seq(d0)) @ Wt.t())})
+    _check(parity, _bwd_state(B, N, Hp, tiles)[1])
+
+
+@pytest.mark.parametrize("B,rule", [(128, 1), (129, 2)])
+def test_the_kernel_s_own_tile_count_at_its_boundary(B, rule, parity):
+    """tiles = 0 leaves the rows per workgroup to the launch: two 16-node tiles once B ceil(tiles / 2) exceeds 256.  37 nodes are 3 tiles, so
+    B = 128 gives 256 (one tile a workgroup) and B = 129 gives 258 (two).  The LDS entry plans with the same rule: it shows which side was
+    taken; and every launch of a step, left to the rule, writes bit for bit what it writes with that tile count forced, within TOL of fp64"""
+    N, Hp = 37, 16
+    assert _C.lib().value("gptst_tgcn_lds_bytes", N, Hp, B) == (48 * 68 + 16 * rule * (2 * Hp + 4)) * 4
+    for launch in (_fwd_gates, _fwd_state, _bwd_cand, _bwd_state):
+        own, errs = launch(B, N, Hp, 0)
+        forced, _ = launch(B, N, Hp, rule)
+        assert all(torch.equal(x, y) for x, y in zip(own, forced)), launch.__name__
+        _check(parity, {launch.__name__[1:] + "." + k: v for k, v in errs.items()})
 
 
 # ---- 2. the whole model --------------------------------------------------------------------------------------------------------------------
