@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -37,7 +37,7 @@ def load_series(args, dev):
     return data_root, gdata.get_dataloader(args, root=data_root, device=dev, raw=raw, generator=g)
 
 
-EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR")      # what -mode eval builds
+EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA")      # what -mode eval builds
 
 
 def main():
@@ -49,7 +49,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -169,15 +169,15 @@ def stgode_graphs(args, pargs, data_root, A, csv_path, train):
 
 
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178 and model/MSDR/args.py:84-126 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126 and model/ST_WA/args.py:33-55 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STSGCN, TGCN
+    from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STSGCN, STWA, TGCN
     if str(args.model) not in EVAL_MODELS:
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE and -model MSDR (SURVEY.md §8f rank 4)")
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR and -model STWA (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -214,6 +214,8 @@ def main_eval(args, dev):
     elif str(args.model) == "MSDR":                                              # model/Model.py:79-82, MSDR/args.py:114-123: the raw adjacency
         ap = SimpleNamespace(**vars(pargs), supports=graph.msdr_supports(A, pargs.filter_type))
         predictor = MSDR(ap, dev, args.hidden_dim, backend=str(args.msdr_backend))
+    elif str(args.model) == "STWA":                                              # model/Model.py:76-78: no graph (ST_WA.py:14 builds one nothing reads)
+        predictor = STWA(SimpleNamespace(**vars(pargs)), dev, args.hidden_dim, backend=str(args.stwa_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

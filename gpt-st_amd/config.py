@@ -88,6 +88,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-stgode_backend", default=FINETUNE_DEFAULTS["stgode_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the MSDR predictor (predictors/msdr_hip.py)
     ap.add_argument("-msdr_backend", default=FINETUNE_DEFAULTS["msdr_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the ST-WA predictor (predictors/stwa_hip.py)
+    ap.add_argument("-stwa_backend", default=FINETUNE_DEFAULTS["stwa_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -101,7 +103,7 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
                          astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch", stgode_backend="torch",
-                         msdr_backend="torch")
+                         msdr_backend="torch", stwa_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -172,22 +174,29 @@ _MSDR_KEYS = [("model", "cl_decay_steps", str, "filter_type"), ("model", "cl_dec
               ("model", "output_dim", int), ("model", "rnn_units", int), ("model", "pre_k", int), ("model", "pre_v", int),
               ("model", "use_curriculum_learning", _EVAL), ("model", "construct_type", str), ("model", "l2lambda", int),
               ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+# reference model/ST_WA/args.py:41-55.  ``dynamic`` is a string there (``type=str``): every conf value, "False" included, is truthy, so the
+# static branch of the model is dead; it is parsed the same way and predictors.STWA refuses the one falsy value, the empty string.  `in_dim`
+# is parsed and, as in the reference (Model.py:78 sets dim_in), read by nothing.  The adjacency of args.py:60-71 is read by nothing either.
+_STWA_KEYS = [("data", "num_nodes", int), ("data", "lag", int), ("data", "horizon", int), ("model", "in_dim", int), ("model", "out_dim", int),
+              ("model", "channels", int), ("model", "dynamic", str), ("model", "memory_size", int),
+              ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
 _PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS, "STSGCN": _STSGCN_KEYS,
-              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS, "MSDR": _MSDR_KEYS}
+              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS, "MSDR": _MSDR_KEYS, "STWA": _STWA_KEYS}
+_PRED_DIRS = {"STWA": "ST-WA"}               # the conf directory where it is not the model's name (the reference's own spelling)
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE and MSDR are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR and STWA are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE and MSDR predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR and STWA predictors only, got %r" % (model,))
     cp = configparser.ConfigParser()
     cp.optionxform = str
     cp.read(PRED_CONF)
     ap = argparse.ArgumentParser(prefix_chars="--", description="predictor_based_arguments")
     for key, typ in _PRED_TRAIN:
         ap.add_argument("--" + key, default=typ(cp["train"][key]), type=typ)
-    path = os.path.join(os.path.dirname(CONF_DIR), model, "%s.conf" % dataset)
+    path = os.path.join(os.path.dirname(CONF_DIR), _PRED_DIRS.get(model, model), "%s.conf" % dataset)
     if not os.path.isfile(path):
         raise FileNotFoundError("no %s conf for dataset %r (%s)" % (model, dataset, path))
     cm = configparser.ConfigParser()

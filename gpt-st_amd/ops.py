@@ -1590,3 +1590,79 @@ def msdr_bwd_state(LpT, WhT, w, a, pa, dpre, dH, de, t, B, T, N, tiles=0):
     assert a.shape == de.shape == (T, B, K) and pa.shape == (B, msdr_groups(N, B, tiles), 8)
     _call("gptst_msdr_bwd_state", _p(LpT), LpT.shape[1], ks, _p(WhT), _p(w), _p(a), _p(pa), _p(dpre), _p(dH), _p(de), B, T, N, Hp, K, t, tiles,
           tag="Hp%d ks%d K%d" % (Hp, ks, K), nbytes=_nb(LpT, WhT, w) + (2 * K + 2) * B * N * Hp * 4)
+
+
+# ---- the downstream ST-WA predictor's cuts (csrc/stwa.hip) ----------------------------------------------------------------------------------
+# One cut of a Layer: two launches forward, three backward.  h (B, T, N, C); prox (2 cuts, N, C); Y (B, cuts, N, C) holds out_0 .. out_{cuts-1};
+# co, cb (B, N, 4, 5); V (4, 6, C, C); u (4, 6, C); Wl, WlT (6, C, C); bl (6, C).  Outputs are the caller's buffers (the loop owns them).
+def stwa_lds_bytes(N, C):
+    """the dynamic LDS of the widest of the five launches (negative: the width is not served)"""
+    return _C.lib().value("gptst_stwa_lds_bytes", N, C)
+
+
+def stwa_slab_shape(B, N, C):
+    """(workgroups, floats) of the weight-gradient slab: one row per workgroup, [dV (4, 6, C, C) | du (4, 6, C) | dWl (6, C, C) | dbl (6, C)]"""
+    return B * ((N + 15) // 16), _C.lib().value("gptst_stwa_slab_floats", C)
+
+
+def _stwa_dims(h, prox, Y, co, cb, V, u):
+    B, T, N, C = h.shape
+    cuts = Y.shape[1]
+    assert prox.shape == (2 * cuts, N, C) and Y.shape == (B, cuts, N, C) and co.shape == cb.shape == (B, N, 4, 5)
+    assert V.shape == (4, 6, C, C) and u.shape == (4, 6, C)
+    return B, T, N, C, cuts
+
+
+def stwa_local_fwd(h, prox, Y, co, cb, V, u, WlT, bl, Tq, Ks, Vs, cut, cs):
+    """rows = [prox[2 cut : 2 cut + 2] + Y[:, cut - 1] | h[:, cut cs : (cut + 1) cs]];  Tq = tp2(tanh(tp1(temporal attention of the 2 proxy rows
+    over all rows, keys and values by the generated maps 0, 1)));  Ks, Vs = the generated maps 2, 3 of Tq"""
+    _chk(h, prox, Y, co, cb, V, u, WlT, bl, Tq, Ks, Vs)
+    B, T, N, C, cuts = _stwa_dims(h, prox, Y, co, cb, V, u)
+    assert WlT.shape == (6, C, C) and bl.shape == (6, C) and Tq.shape == Ks.shape == Vs.shape == (B, 2, N, C)
+    _call("gptst_stwa_local_fwd", _p(h), _p(prox), _p(Y), _p(co), _p(cb), _p(V), _p(u), _p(WlT), _p(bl), _p(Tq), _p(Ks), _p(Vs), B, T, N, C, cuts,
+          cut, cs, tag="C%d cs%d" % (C, cs), nbytes=_nb(Tq, Ks, Vs, V, u, WlT) + (3 + cs) * B * N * C * 4)
+
+
+def stwa_spatial_fwd(Tq, Ks, Vs, WlT, bl, Y, cut, S=None, mx=None, sm=None):
+    """Y[:, cut] = sum_p g U with U = sp2(relu(sp1(softmax_nodes(Tq Ks^T / sqrt(C / 8)) Vs))) per (sample, proxy, head), g = sigmoid(ag2(relu(
+    ag1(U))));  kept when given: S (the mixed values), mx, sm (each softmax row's maximum and sum)"""
+    _chk(Tq, Ks, Vs, WlT, bl, Y, S, mx, sm)
+    B, _, N, C = Tq.shape
+    assert Ks.shape == Vs.shape == Tq.shape and Y.shape[0] == B and Y.shape[2:] == (N, C) and (mx is None) == (sm is None)
+    assert (S is None or S.shape == Tq.shape) and (mx is None or mx.shape == sm.shape == (B, 2, N, 8))
+    _call("gptst_stwa_spatial_fwd", _p(Tq), _p(Ks), _p(Vs), _p(WlT), _p(bl), _p(Y), _p(S), _p(mx), _p(sm), B, N, C, Y.shape[1], cut,
+          tag="C%d N%d" % (C, N), nbytes=_nb(Tq, Ks, Vs, S, mx, sm) + B * N * C * 4)
+
+
+def stwa_spatial_bwd_q(Tq, Ks, Vs, S, mx, sm, Wl, WlT, bl, dY, carry, dS, Dq, dTq, slab, cut):
+    """the gradient of Y[:, cut] (dY[:, cut] + carry) back through the gate and the spatial projections -> dS, Dq = <dS, S> per head, and the
+    query side of the spatial attention -> dTq;  slab (may be None) += the four Linears' gradients"""
+    _chk(Tq, Ks, Vs, S, mx, sm, Wl, WlT, bl, dY, carry, dS, Dq, dTq, slab)
+    B, _, N, C = Tq.shape
+    assert Ks.shape == Vs.shape == S.shape == dS.shape == dTq.shape == Tq.shape and mx.shape == sm.shape == Dq.shape == (B, 2, N, 8)
+    assert dY.shape[0] == B and dY.shape[2:] == (N, C) and (carry is None or carry.shape == (B, N, C))
+    assert slab is None or slab.shape == stwa_slab_shape(B, N, C)
+    _call("gptst_stwa_spatial_bwd_q", _p(Tq), _p(Ks), _p(Vs), _p(S), _p(mx), _p(sm), _p(Wl), _p(WlT), _p(bl), _p(dY), _p(carry), _p(dS), _p(Dq),
+          _p(dTq), _p(slab), B, N, C, dY.shape[1], cut, tag="C%d N%d" % (C, N), nbytes=_nb(Tq, Ks, Vs, S, dS, dTq, slab) + 2 * B * N * C * 4)
+
+
+def stwa_spatial_bwd_kv(Tq, Ks, Vs, dS, Dq, mx, sm, dKs, dVs):
+    """the key / value side of the spatial attention: a key's gradient summed over the query nodes of its sample in index order"""
+    _chk(Tq, Ks, Vs, dS, Dq, mx, sm, dKs, dVs)
+    B, _, N, C = Tq.shape
+    assert Ks.shape == Vs.shape == dS.shape == dKs.shape == dVs.shape == Tq.shape and mx.shape == sm.shape == Dq.shape == (B, 2, N, 8)
+    _call("gptst_stwa_spatial_bwd_kv", _p(Tq), _p(Ks), _p(Vs), _p(dS), _p(Dq), _p(mx), _p(sm), _p(dKs), _p(dVs), B, N, C, tag="C%d N%d" % (C, N),
+          nbytes=_nb(Tq, Ks, Vs, dS, dKs, dVs))
+
+
+def stwa_local_bwd(h, prox, Y, co, cb, V, u, Wl, WlT, bl, dTq, dKs, dVs, dh, dPb, carry, dco, dcb, slab, cut, cs):
+    """the node-local half backwards (its forward recomputed): dh rows of the cut, dPb[:, 2 cut : 2 cut + 2] (the proxies' gradient per sample),
+    carry = the gradient of Y[:, cut - 1] — each written when given;  dco, dcb +=;  slab (may be None) += dV, du, the temporal Linears"""
+    _chk(h, prox, Y, co, cb, V, u, Wl, WlT, bl, dTq, dKs, dVs, dh, dPb, carry, dco, dcb, slab)
+    B, T, N, C, cuts = _stwa_dims(h, prox, Y, co, cb, V, u)
+    assert dTq.shape == dKs.shape == dVs.shape == (B, 2, N, C) and dco.shape == dcb.shape == co.shape
+    assert (dh is None or dh.shape == h.shape) and (dPb is None or dPb.shape == (B, 2 * cuts, N, C)) and (carry is None or carry.shape == (B, N, C))
+    assert slab is None or slab.shape == stwa_slab_shape(B, N, C)
+    _call("gptst_stwa_local_bwd", _p(h), _p(prox), _p(Y), _p(co), _p(cb), _p(V), _p(u), _p(Wl), _p(WlT), _p(bl), _p(dTq), _p(dKs), _p(dVs), _p(dh),
+          _p(dPb), _p(carry), _p(dco), _p(dcb), _p(slab), B, T, N, C, cuts, cut, cs, tag="C%d cs%d" % (C, cs),
+          nbytes=_nb(dTq, dKs, dVs, slab, V, u) + (6 + 2 * cs) * B * N * C * 4)

@@ -12,10 +12,10 @@ def check(model_name, backend):
     return backend
 
 
-def hip_forward(model, hip_module, x):
+def hip_forward(model, hip_module, x, **extra):
     """-> the output of ``<hip_module>.forward`` where ``model.backend`` is "hip" and that module (imported here, on first use) serves the
     call; None where the caller's torch path has to.  Records which in ``model.backend_used``.  Outside train mode, or with gradients
-    disabled, the HIP path runs under ``no_grad`` and keeps nothing for a backward."""
+    disabled, the HIP path runs under ``no_grad`` and keeps nothing for a backward.  ``extra`` is handed to that forward as it is (ST-WA: the noise)."""
     if model.backend == "hip":
         hip = _HIP.get(hip_module)
         if hip is None:
@@ -23,8 +23,8 @@ def hip_forward(model, hip_module, x):
         if hip.supported(model, x):
             model.backend_used = "hip"
             if model.training and torch.is_grad_enabled():
-                return hip.forward(model, x, keep=True)
+                return hip.forward(model, x, keep=True, **extra)
             with torch.no_grad():
-                return hip.forward(model, x, keep=False)
+                return hip.forward(model, x, keep=False, **extra)
     model.backend_used = "torch"
     return None

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 26  /* 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 27  /* 27: + gptst_stwa_* (the downstream ST-WA predictor on HIP: one cut of a Layer in two launches forward and three backward, generated per-node weights folded from their rank-5 factors, the spatial attention over the nodes of a sample without its N x N scores: csrc/stwa.hip); 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -747,6 +747,38 @@ int gptst_msdr_bwd_pre(const float* W, const float* R, const float* Hs, const fl
                        int N, int Hp, int Kk, int t, int tiles, void* stream);
 int gptst_msdr_bwd_state(const float* LT, int Np, int ks, const float* WhT, const float* w, const float* a, const float* pa, const float* dpre,
                          float* dH, float* de, int B, int T, int N, int Hp, int Kk, int t, int tiles, void* stream);
+
+/* ---- the downstream ST-WA predictor's cuts (stwa.hip; reference model/ST_WA/ST_WA.py:138-164, attention.py, gpt-st_amd/predictors/stwa_hip.py) ----
+ * C = 16 or 32 channels, 8 heads of C / 8.  A Layer has `cuts` sequential cuts of `cs` <= 6 data rows; cut i reads R = clamp(T - i cs, 0, cs) rows of
+ * h (B, T, N, C) from row i cs, the proxies prox (2 cuts, N, C)[2 i, 2 i + 1] and out_{i-1} = slot i - 1 of Y (B, cuts, N, C) (cut 0: nothing).
+ * The four generated maps (0 temporal key, 1 temporal value, 2 spatial key, 3 spatial value) come factored: V (4, 6, C, C) with x V[g][k] = sum_i
+ * x_i V[g][k][i][.], u (4, 6, C), and the per-(sample, node) coefficients co, cb (B, N, 4, 5) of entries 1 .. 5 (entry 0 has coefficient 1).  The six
+ * shared Linears (temporal projection1, projection2, spatial projection1, projection2, aggregator 0, 2) are Wl (6, C, C) [out][in], WlT their
+ * transposes, bl (6, C).  Tq, Ks, Vs, S, dS, dTq, dKs, dVs are (B, 2, N, C); mx, sm, Dq (B, 2, N, 8).
+ * local_fwd: -> Tq (the temporal attention's output), Ks, Vs.   spatial_fwd: -> slot `cut` of Y; S, mx, sm are written when not NULL (mx, sm: both
+ *   or neither).   spatial_bwd_q: dY (B, cuts, N, C) slot `cut` + carry (B, N, C; NULL: none) -> dS, Dq, dTq.   spatial_bwd_kv: -> dKs, dVs.
+ * local_bwd: -> rows [cut cs, cut cs + R) of dh (B, T, N, C), slots 2 cut, 2 cut + 1 of dPb (B, 2 cuts, N, C) (the proxies' gradient per sample) and
+ *   carry = the gradient of out_{cut-1} — each written when not NULL — and ADDS to dco, dcb (B, N, 4, 5).
+ * slab (NULL: no weight gradient is computed): (B ceil(N / 16), gptst_stwa_slab_floats(C)), one row per workgroup, ADDED to by spatial_bwd_q and
+ *   local_bwd: [dV (4, 6, C, C) | du (4, 6, C) | dWl (6, C, C) | dbl (6, C)]; the caller zeroes it and sums its rows.  du of map 0 stays 0 (a bias
+ *   common to all keys of a softmax), and so does its share of dcb.
+ * lds_bytes: the dynamic LDS of the widest of the five launches at this shape (above 160 KB they return GPTST_ESHAPE). */
+int gptst_stwa_lds_bytes(int N, int C);
+int gptst_stwa_slab_floats(int C);
+int gptst_stwa_local_fwd(const float* h, const float* prox, const float* Y, const float* co, const float* cb, const float* V, const float* u,
+                         const float* WlT, const float* bl, float* Tq, float* Ks, float* Vs, int B, int T, int N, int C, int cuts, int cut, int cs,
+                         void* stream);
+int gptst_stwa_spatial_fwd(const float* Tq, const float* Ks, const float* Vs, const float* WlT, const float* bl, float* Y, float* S, float* mx,
+                           float* sm, int B, int N, int C, int cuts, int cut, void* stream);
+int gptst_stwa_spatial_bwd_q(const float* Tq, const float* Ks, const float* Vs, const float* S, const float* mx, const float* sm, const float* Wl,
+                             const float* WlT, const float* bl, const float* dY, const float* carry, float* dS, float* Dq, float* dTq, float* slab,
+                             int B, int N, int C, int cuts, int cut, void* stream);
+int gptst_stwa_spatial_bwd_kv(const float* Tq, const float* Ks, const float* Vs, const float* dS, const float* Dq, const float* mx, const float* sm,
+                              float* dKs, float* dVs, int B, int N, int C, void* stream);
+int gptst_stwa_local_bwd(const float* h, const float* prox, const float* Y, const float* co, const float* cb, const float* V, const float* u,
+                         const float* Wl, const float* WlT, const float* bl, const float* dTq, const float* dKs, const float* dVs, float* dh,
+                         float* dPb, float* carry, float* dco, float* dcb, float* slab, int B, int T, int N, int C, int cuts, int cut, int cs,
+                         void* stream);
 
 /* ---- communication (comm.hip): RCCL over xGMI with an explicit stream — a collective can sit inside a captured hipGraph -------------
  * The reference has no distributed code; these carry the data-parallel gradient exchange (one all-reduce of [flat gradient | statistics])
