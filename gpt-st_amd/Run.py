@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -37,7 +37,7 @@ def load_series(args, dev):
     return data_root, gdata.get_dataloader(args, root=data_root, device=dev, raw=raw, generator=g)
 
 
-EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA")      # what -mode eval builds
+EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA", "STMGCN")      # what -mode eval builds
 
 
 def main():
@@ -49,7 +49,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -168,16 +168,35 @@ def stgode_graphs(args, pargs, data_root, A, csv_path, train):
     return graph.stgode_graphs(dist["spatial"], dist["dtw"], pargs.sigma1, pargs.sigma2, pargs.thres1, pargs.thres2)
 
 
+def stmgcn_graphs(args, data_root, A, train):
+    """ST-MGCN's two Chebyshev support stacks (reference model/STMGCN_demand/args.py:35-53): the distance graph and the correlation graph of
+    ``<data_root>/STMGCN_demand/{dis,pcc}_{tt|bb}.csv`` (comma-separated, no header) where those files exist.  Where one is absent — this
+    fallback is the project's own, the reference has none — the distance graph is the adjacency at hand and the correlation graph the
+    Pearson correlation between the nodes of the training series' first channel."""
+    from gptst_amd import graph
+    tag = {"NYC_TAXI": "tt", "NYC_BIKE": "bb"}[args.dataset]
+    raw = {}
+    for kind in ("dis", "pcc"):
+        path = os.path.join(data_root, "STMGCN_demand", "%s_%s.csv" % (kind, tag))
+        if os.path.exists(path):
+            raw[kind] = np.loadtxt(path, delimiter=",", dtype=np.float32, ndmin=2)
+            continue
+        print("gpt-st_amd: %s not found -> built from the %s" % (path, "adjacency" if kind == "dis" else "training series"), flush=True)
+        raw[kind] = (np.asarray(A, dtype=np.float32) if kind == "dis"
+                     else graph.stmgcn_correlation(train.series[:, :, 0].detach().cpu().numpy()))
+    return graph.stmgcn_supports(raw["dis"]), graph.stmgcn_supports(raw["pcc"])
+
+
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126 and model/ST_WA/args.py:33-55 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126, model/ST_WA/args.py:33-55 and model/STMGCN_demand/args.py:7-56 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STSGCN, STWA, TGCN
+    from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STMGCN, STSGCN, STWA, TGCN
     if str(args.model) not in EVAL_MODELS:
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR and -model STWA (SURVEY.md §8f rank 4)")
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR, -model STWA and -model STMGCN (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -216,6 +235,10 @@ def main_eval(args, dev):
         predictor = MSDR(ap, dev, args.hidden_dim, backend=str(args.msdr_backend))
     elif str(args.model) == "STWA":                                              # model/Model.py:76-78: no graph (ST_WA.py:14 builds one nothing reads)
         predictor = STWA(SimpleNamespace(**vars(pargs)), dev, args.hidden_dim, backend=str(args.stwa_backend))
+    elif str(args.model) == "STMGCN":                                            # model/Model.py, STMGCN_demand/args.py:35-53: the two support stacks
+        dis, pcc = stmgcn_graphs(args, data_root, A, train)
+        ap = SimpleNamespace(**vars(pargs), dis_graph=dis, pcc_graph=pcc)
+        predictor = STMGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stmgcn_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

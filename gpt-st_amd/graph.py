@@ -340,3 +340,31 @@ def stgode_dtw_distances(series, day_slots=288, chunk=16384):
     prof = data[:days * day_slots].double().reshape(days, day_slots, -1).mean(0)
     d = dtw_distances(prof[None], band=day_slots, chunk=chunk, normalise=False)
     return (d + d.t()).cpu().numpy()
+
+
+def stmgcn_supports(adj):
+    """The (3, N, N) fp32 Chebyshev supports [I, L~, 2 L~^2 - I] ``predictors.STMGCN`` multiplies by, from one raw graph as the reference
+    builds them (model/STMGCN_demand/GCN.py ``Adj_Preprocessor('chebyshev', K=2)``, args.py:43-51), in fp32 torch ops as there:
+
+        A_norm = D^-1/2 A D^-1/2 with D the row sums;  L = I - A_norm;  L~ = (2 / lambda_max) L - I with lambda_max = 2
+
+    lambda_max is 2 always: the reference asks ``torch.eig`` for it inside a bare ``except``, a call every torch this project runs on
+    refuses, so its fallback is what runs (the line it prints there is dropped).  ``rowsum ** -0.5`` is taken as it comes: a zero row sum
+    gives inf, a negative one (a correlation graph has them) NaN, both spread through the products, and ``nan_to_num`` at the very end turns
+    what is left of them into fp32's largest value and 0."""
+    a = torch.as_tensor(np.asarray(adj, dtype=np.float32))
+    eye = torch.eye(a.shape[0])
+    d = torch.diag(torch.pow(a.sum(dim=1), -0.5))
+    lap = eye - torch.mm(torch.mm(d, a), d)
+    lt = (2 / 2) * lap - eye
+    return torch.nan_to_num(torch.stack([eye, lt, 2 * torch.mm(lt, lt) - eye], dim=0))
+
+
+def stmgcn_correlation(series):
+    """(N, N) fp32 Pearson correlation between the nodes of a (L, N) series, the diagonal zeroed; a constant node correlates 0 with all"""
+    s = np.asarray(series, dtype=np.float64)
+    s = s - s.mean(0, keepdims=True)
+    sd = np.sqrt((s * s).sum(0))
+    c = (s.T @ s) / np.maximum(np.outer(sd, sd), 1e-30)
+    np.fill_diagonal(c, 0.0)
+    return c.astype(np.float32)

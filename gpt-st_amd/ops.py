@@ -1666,3 +1666,49 @@ def stwa_local_bwd(h, prox, Y, co, cb, V, u, Wl, WlT, bl, dTq, dKs, dVs, dh, dPb
     _call("gptst_stwa_local_bwd", _p(h), _p(prox), _p(Y), _p(co), _p(cb), _p(V), _p(u), _p(Wl), _p(WlT), _p(bl), _p(dTq), _p(dKs), _p(dVs), _p(dh),
           _p(dPb), _p(carry), _p(dco), _p(dcb), _p(slab), B, T, N, C, cuts, cut, cs, tag="C%d cs%d" % (C, cs),
           nbytes=_nb(dTq, dKs, dVs, slab, V, u) + (6 + 2 * cs) * B * N * C * 4)
+
+
+# ---- the downstream ST-MGCN predictor's stacked LSTM (csrc/stmgcn.hip) ------------------------------------------------------------------------
+# TIME-major: Gx0 (T, rows, 4H);  W the flat [W_hh0 (4H, H) | [W_ih_l | W_hh_l] (4H, 2H) ..], WT the transposes in the same order;  bias (L, 4H)
+def stmgcn_lds_bytes(H, L, tiles):
+    """the larger dynamic LDS of the two launches with `tiles` (1 or 2) 16-row tiles per workgroup"""
+    return _C.lib().value("gptst_stmgcn_lds_bytes", H, L, tiles)
+
+
+def stmgcn_tiles(rows, H, L, forced=0):
+    """16-row tiles per workgroup of both launches (negative: the shape is not served)"""
+    return _C.lib().value("gptst_stmgcn_tiles", rows, H, L, forced)
+
+
+def stmgcn_wsize(H, L):
+    return 4 * H * H + (L - 1) * 8 * H * H
+
+
+def stmgcn_lstm_fwd(Gx0, W, bias, L, keep, tiles=0):
+    """all T steps of all L layers in ONE launch -> (top (T, rows, H), gates, c, h): keep False: the top ring alone (the rest None); keep True:
+    gates (L, T, rows, 4H), c (L, T, rows, H), h (L, T + 1, rows, H) with slot 0 zero, and top = h[L - 1, 1:]"""
+    _chk(Gx0, W, bias)
+    T, rows, H4 = Gx0.shape
+    H = H4 // 4
+    assert H4 == 4 * H and W.numel() == stmgcn_wsize(H, L) and bias.shape == (L, H4)
+    top = gates = c = h = None
+    if keep:
+        gates, c, h = Gx0.new_empty(L, T, rows, H4), Gx0.new_empty(L, T, rows, H), Gx0.new_empty(L, T + 1, rows, H)
+        h[:, 0] = 0
+    else:
+        top = Gx0.new_empty(T, rows, H)
+    _call("gptst_stmgcn_lstm_fwd", _p(Gx0), _p(W), _p(bias), _p(top), _p(gates), _p(c), _p(h), rows, T, L, H, tiles, tag="H%d L%d T%d" % (H, L, T),
+          nbytes=_nb(Gx0, W, bias, top, gates, c, h))
+    return (h[L - 1, 1:] if keep else top), gates, c, h
+
+
+def stmgcn_lstm_bwd(dTop, WT, gates, c, dG_layers, tiles=0):
+    """ONE launch -> dG (dG_layers, T, rows, 4H): the gradient of the pre-activations of layers 0 .. dG_layers - 1 (dG[0] is dGx0)"""
+    _chk(dTop, WT, gates, c)
+    L, T, rows, H4 = gates.shape
+    H = H4 // 4
+    assert dTop.shape == (T, rows, H) and c.shape == (L, T, rows, H) and WT.numel() == stmgcn_wsize(H, L) and 1 <= dG_layers <= L
+    dG = dTop.new_empty(dG_layers, T, rows, H4)
+    _call("gptst_stmgcn_lstm_bwd", _p(dTop), _p(WT), _p(gates), _p(c), _p(dG), dG_layers, rows, T, L, H, tiles, tag="H%d L%d T%d" % (H, L, T),
+          nbytes=_nb(dTop, WT, gates, c, dG))
+    return dG
