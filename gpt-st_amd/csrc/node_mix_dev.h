@@ -1,6 +1,7 @@
-// The slab product sg_nodemix_kernel (stgcn.hip) and ss_mix_kernel (stsgcn.hip) share: a wave's 16-node tile of L (rows n0 .. n0 + 15 of an
-// (Np, Np) matrix read from L2) times the 32-channel slab of a unit's Np rows in LDS, added into two 16 x 16 accumulators (channels j, j + 16).
-// Filling the slab and the epilogue are the kernels' own.  ag_attmix_kernel (astgcn.hip: per-sample masked tiles of L, a 64-channel slab,
+// The slab product sg_nodemix_kernel (stgcn.hip), st_step_kernel (stgode.hip) and win_mix_body (win_mix_dev.h: ss_mix_kernel of stsgcn.hip and
+// sf_mix_kernel of stfgnn.hip) share: a wave's 16-node tile of L (rows n0 .. n0 + 15 of an (Np, Np) matrix read from L2) times the 32-channel
+// slab of a unit's Np rows in LDS, added into two 16 x 16 accumulators (channels j, j + 16).  Filling the slab and the epilogue are the callers'
+// own: the two window mixes have theirs in common, in win_mix_body; the other two differ from it and from each other.  ag_attmix_kernel (astgcn.hip: per-sample masked tiles of L, a 64-channel slab,
 // the next tile of L prefetched into registers) is a different loop and stays apart; so does the recurrences' 64-column loop (tgcn.hip, msdr.hip: a slab
 // at pitch 68, a wave owning one column tile for NT row tiles, L prefetched one step ahead): recur_step_dev.h's recur_mix_tiles.
 #pragma once

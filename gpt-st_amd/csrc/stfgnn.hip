@@ -23,34 +23,20 @@
 //        phase 0:  S^T (G[t-1, 1] + G[t-2, 2]),  phase 1:  D^T (G[t, 0] + G[t, 3] + G[t-3, 0] + G[t-3, 3])  (blocks gathered in this order) —
 //        plus the unmixed blocks, in this order:  G[t-1, 0], G[t-1, 3], G[t-2, 0], G[t-2, 3], G[t, 1], G[t-2, 1], G[t-3, 1], G[t, 2], G[t-1, 2],
 //        G[t-3, 2]; every block whose window exists.
-// The slab-in-LDS product is node_mix_slab (node_mix_dev.h), as in ss_mix_kernel (stsgcn.hip) and sg_nodemix_kernel (stgcn.hip).
+// sf_plan below writes the plan of a unit; what runs it is win_mix_body (win_mix_dev.h), the body ss_mix_kernel (stsgcn.hip) runs with its
+// one-phase plans.
 //
 // fp32 MFMA 16x16x4 (exact fp32).  Plain launches only: no workgroup waits on another, nothing is accumulated with float atomics, the order of
 // every sum is fixed.  No launch asks for more than the 64 KB of dynamic LDS a launch gets by default: N <= 448 (GPTST_ESHAPE beyond).
 #include "common.h"
 #include "gptst_hip.h"
-#include "node_mix_dev.h"
-
-#define SF_MAX_NP 448       // 448 * NODE_MIX_P * 4 = 64 512 bytes of slab + the plan below: under 64 KB
-
-#define SF_F2E 0
-#define SF_E2E 1
-#define SF_E2M 2
-#define SF_M2E 3
-#define SF_E2F 4
+#include "win_mix_dev.h"
 
 struct SfMix { const float* S; const float* D; int Np; const float* In; float* Out; int c; int mode; int B; int T; int N; };
 
-// first rows (of N) in In / Out.  Phase h: acc += graph[gsel[h]] (sum of its nsrc[h] source blocks); output o = [useacc[o]] acc + the sum of
-// its nadd[o] blocks of In
-struct SfPlan {
-    int nph, nout;
-    int gsel[2], nsrc[2];
-    long src[2][4];
-    long out[4];
-    int useacc[4], nadd[4];
-    long add[4][10];
-};
+// what a workgroup's unit does (WinMixPlan, win_mix_dev.h): up to two phases of up to four source blocks, up to four outputs of up to ten adds;
+// a phase without sources is skipped
+using SfPlan = WinMixPlan<2, 4, 4, 10>;
 
 __device__ __forceinline__ void sf_plan(const SfMix& p, int u, SfPlan& q) {
     const int T = p.T, W = p.T - 3;
@@ -59,9 +45,9 @@ __device__ __forceinline__ void sf_plan(const SfMix& p, int u, SfPlan& q) {
     auto blk = [&](int b, int w, int k) { return (((long)b * W + w) * 4 + k) * N; };
     auto mid = [&](int b, int w) { return ((long)b * W + w) * N; };
     auto win = [&](int w) { return w >= 0 && w < W; };
-    q.nph = 1; q.nout = 0;
+    q.nout = 0;
     q.gsel[0] = q.gsel[1] = 0; q.nsrc[0] = q.nsrc[1] = 0;
-    if (p.mode == SF_F2E) {
+    if (p.mode == WIN_MIX_F2E) {
         if (u < p.B * T) {                                          // S^ H_t -> the blocks k = 1, 2 with w + k = t
             const int b = u / T, t = u % T;
             q.src[0][q.nsrc[0]++] = frame(b, t);
@@ -85,7 +71,7 @@ __device__ __forceinline__ void sf_plan(const SfMix& p, int u, SfPlan& q) {
                 q.add[o][0] = frame(b, w + 1); q.add[o][1] = frame(b, w + 2); q.nadd[o] = 2;
             }
         }
-    } else if (p.mode == SF_E2E) {
+    } else if (p.mode == WIN_MIX_E2E) {
         const int b = u / (3 * W), w = (u / 3) % W, r = u % 3;
         if (r == 0) {
             q.gsel[0] = 1;
@@ -103,21 +89,21 @@ __device__ __forceinline__ void sf_plan(const SfMix& p, int u, SfPlan& q) {
                 if (k2 != r) q.add[0][na++] = blk(b, w, k2);
             q.nadd[0] = na;
         }
-    } else if (p.mode == SF_E2M) {
+    } else if (p.mode == WIN_MIX_E2M) {
         const int b = u / W, w = u % W;
         q.src[0][0] = blk(b, w, 1); q.nsrc[0] = 1;
         q.out[0] = mid(b, w); q.useacc[0] = 1; q.nout = 1;
         q.add[0][0] = blk(b, w, 0); q.add[0][1] = blk(b, w, 2); q.add[0][2] = blk(b, w, 3); q.nadd[0] = 3;
-    } else if (p.mode == SF_M2E) {
+    } else if (p.mode == WIN_MIX_M2E) {
         const int b = u / W, w = u % W;
         q.src[0][0] = mid(b, w); q.nsrc[0] = 1;
         q.nout = 4;
         for (int k = 0; k < 4; ++k) {
             q.out[k] = blk(b, w, k); q.useacc[k] = k == 1; q.nadd[k] = k == 1 ? 0 : 1; q.add[k][0] = mid(b, w);
         }
-    } else {                                                        // SF_E2F
+    } else {                                                        // WIN_MIX_E2F
         const int b = u / T, t = u % T;
-        q.nph = 2; q.gsel[1] = 1;
+        q.gsel[1] = 1;
         if (win(t - 1)) q.src[0][q.nsrc[0]++] = blk(b, t - 1, 1);
         if (win(t - 2)) q.src[0][q.nsrc[0]++] = blk(b, t - 2, 2);
         if (win(t)) { q.src[1][q.nsrc[1]++] = blk(b, t, 0); q.src[1][q.nsrc[1]++] = blk(b, t, 3); }
@@ -131,68 +117,24 @@ __device__ __forceinline__ void sf_plan(const SfMix& p, int u, SfPlan& q) {
     }
 }
 
-// one unit and four 16-node tiles per workgroup; 32 channels of the unit's source rows in LDS at a time, the graph (Np, Np) read from L2
+// a unit's plan by thread 0, then win_mix_body (win_mix_dev.h) runs it: graph 0 = S^, graph 1 = D
 __global__ __launch_bounds__(256) void sf_mix_kernel(SfMix p) {
     extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][NODE_MIX_P]
     __shared__ SfPlan q;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
-    const int n0 = (blockIdx.y * 4 + wave) * 16;
-    const bool active = n0 < p.Np;
-    if (tid == 0) sf_plan(p, blockIdx.x, q);
+    if (threadIdx.x == 0) sf_plan(p, blockIdx.x, q);
     __syncthreads();
-    const int nout = q.nout, nph = q.nph;
-    if (nout == 0) return;                                                  // (F2E: the first and the last frame are in no block 1 or 2)
-    for (int cg = 0; cg * 32 < p.c; ++cg) {
-        f32x4 acc[2];
-        acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        for (int h = 0; h < nph; ++h) {
-            const int nsrc = q.nsrc[h];
-            if (nsrc == 0) continue;                                        // (the same for every thread of the workgroup)
-            __syncthreads();                                                // the previous product's reads of the slab are done
-            for (int f = tid; f < p.Np * 8; f += 256) {
-                const int m = f >> 3, c4 = f & 7;
-                float4 v = f4zero();
-                if (m < p.N && 32 * cg + 4 * c4 < p.c) {
-                    for (int s = 0; s < nsrc; ++s) {
-                        const float4 a = ld4(p.In + (size_t)(q.src[h][s] + m) * p.c + 32 * cg + 4 * c4);
-                        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-                    }
-                }
-                st4(slab + m * NODE_MIX_P + 4 * c4, v);
-            }
-            __syncthreads();
-            if (active) node_mix_slab(acc, (q.gsel[h] ? p.D : p.S) + (size_t)(n0 + j) * p.Np + 4 * kk, slab, p.Np, j, kk);
-        }
-        if (!active) continue;
-        // ---- epilogue in the accumulator layout: reg r = (node n0 + kk*4 + r, channel 32 cg + 16 ct + j) ----
-        for (int o = 0; o < nout; ++o) {
-            const long ob = q.out[o];
-            const int useacc = q.useacc[o], na = q.nadd[o];
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                const int ch = 32 * cg + 16 * ct + j;
-                if (ch >= p.c) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = n0 + kk * 4 + r;
-                    if (n >= p.N) continue;
-                    float v = useacc ? acc[ct][r] : 0.f;
-                    for (int a = 0; a < na; ++a) v += p.In[(size_t)(q.add[o][a] + n) * p.c + ch];
-                    p.Out[(size_t)(ob + n) * p.c + ch] = v;
-                }
-            }
-        }
-    }
+    const float* const graph[2] = {p.S, p.D};
+    win_mix_body(q, graph, p.Np, p.N, p.c, p.In, p.Out, slab);            // (F2E: the first and the last frame are in no block 1 or 2: no output)
 }
 
 extern "C" int gptst_stfgnn_mix(const float* S, const float* D, int Np, const float* In, float* Out, int c, int mode, int B, int T, int N,
                                 void* stream) {
     if (!S || !D || !In || !Out || In == Out || B <= 0 || T < 4 || N <= 0 || mode < 0 || mode > 4) return GPTST_EARG;
-    if (Np != 16 * ((N + 15) / 16) || Np > SF_MAX_NP || c < 16 || c % 16) return GPTST_ESHAPE;
+    if (Np != 16 * ((N + 15) / 16) || Np > WIN_MIX_MAX_NP || c < 16 || c % 16) return GPTST_ESHAPE;
     const long W = T - 3;
-    const long units = mode == SF_F2E ? (long)B * (T + W) : mode == SF_E2F ? (long)B * T : mode == SF_E2E ? (long)B * W * 3 : (long)B * W;
+    const long units = mode == WIN_MIX_F2E ? (long)B * (T + W) : mode == WIN_MIX_E2F ? (long)B * T : mode == WIN_MIX_E2E ? (long)B * W * 3 : (long)B * W;
     if (units > 0x7fffffffL) return GPTST_ESHAPE;
-    static_assert(SF_MAX_NP * NODE_MIX_P * sizeof(float) + sizeof(SfPlan) <= 64 * 1024, "slab + plan exceed the default dynamic LDS");
+    static_assert(WIN_MIX_MAX_NP * NODE_MIX_P * sizeof(float) + sizeof(SfPlan) <= 64 * 1024, "slab + plan exceed the default dynamic LDS");
     const size_t smem = (size_t)Np * NODE_MIX_P * sizeof(float);
     SfMix p{S, D, Np, In, Out, c, mode, B, (int)T, N};
     hipLaunchKernelGGL(sf_mix_kernel, dim3((unsigned)units, (Np / 16 + 3) / 4), dim3(256), smem, (hipStream_t)stream, p);

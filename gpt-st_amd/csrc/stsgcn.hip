@@ -12,8 +12,8 @@
 //              w + k = t; no expanded copy of the input exists), expanded -> expanded, expanded -> middle (the last operation needs only
 //              k = 1).  Adjoints, called with A^T: expanded -> expanded (the same expression), middle -> expanded (blocks 0 and 2 take
 //              the gradient unmixed), expanded -> frames (frame t gathers the blocks with w + k = t, in the order k = 0, 1, 2, before
-//              the product, and its neighbour terms after it).  The slab-in-LDS product is node_mix_slab (node_mix_dev.h), which
-//              sg_nodemix_kernel (stgcn.hip) runs too; the fill of the slab and the epilogue are this kernel's own.
+//              the product, and its neighbour terms after it).  Each form is a plan (ss_plan below) that win_mix_body (win_mix_dev.h)
+//              runs: the body sf_mix_kernel (stfgnn.hip) runs too, with plans of its own.
 //   wingemm    grouped GEMM: row (b, w, ., n) multiplies the weight of window w (stacked (W, cw, ci); one for all: stride 0).  A 16-row
 //              tile never straddles two windows: tiles are counted inside each (b, w) group.  Epilogue GLU (S = sigma(Q) and A = P + b
 //              kept when asked) or none; on the middle block the GLU epilogue also updates the running max `best` and the winner
@@ -27,26 +27,19 @@
 // No launch asks for more than the 64 KB of dynamic LDS a launch gets by default: the mix serves N <= 448.
 #include "common.h"
 #include "gptst_hip.h"
-#include "node_mix_dev.h"
 #include "row_gemm_dev.h"
 #include "tap_wgrad_dev.h"
+#include "win_mix_dev.h"
 
 #define SS_ACT_NONE 0
 #define SS_ACT_GLU 3
-#define SS_MAX_NP 448       // 448 * NODE_MIX_P * 4 = 64 512 bytes
-
-#define SS_F2E 0
-#define SS_E2E 1
-#define SS_E2M 2
-#define SS_M2E 3
-#define SS_E2F 4
 
 // ---- the mix --------------------------------------------------------------------------------------------------------------------------
 struct SsMix { const float* L; int Np; const float* In; float* Out; int c; int mode; int T; int N; };
 
-// what a workgroup's unit does, as first rows (of N) in In / Out: slab = sum of the nsrc source blocks; output o = [acc[o]] L slab + the
-// sum of its nadd[o] blocks of In
-struct SsPlan { int nsrc, nout; long src[3]; long out[3]; int acc[3]; int nadd[3]; long add[3][4]; };
+// what a workgroup's unit does (WinMixPlan, win_mix_dev.h): one phase, slab = sum of up to three source blocks; up to three outputs, each
+// [useacc[o]] L slab + the sum of up to four blocks of In
+using SsPlan = WinMixPlan<1, 3, 3, 4>;
 
 __device__ __forceinline__ void ss_plan(const SsMix& p, int u, SsPlan& q) {
     const int T = p.T, W = p.T - 2;
@@ -54,48 +47,50 @@ __device__ __forceinline__ void ss_plan(const SsMix& p, int u, SsPlan& q) {
     auto frame = [&](int b, int t) { return ((long)b * T + t) * N; };
     auto blk = [&](int b, int w, int k) { return (((long)b * W + w) * 3 + k) * N; };
     auto mid = [&](int b, int w) { return ((long)b * W + w) * N; };
-    q.nsrc = q.nout = 0;
-    if (p.mode == SS_F2E) {
+    int& nsrc = q.nsrc[0];
+    long (&src)[3] = q.src[0];
+    q.gsel[0] = 0; nsrc = q.nout = 0;
+    if (p.mode == WIN_MIX_F2E) {
         const int b = u / T, t = u % T;
-        q.src[q.nsrc++] = frame(b, t);
+        src[nsrc++] = frame(b, t);
         for (int k = 0; k < 3; ++k) {
             const int w = t - k;
             if (w < 0 || w >= W) continue;
             const int o = q.nout++;
             int na = 0;
-            q.out[o] = blk(b, w, k); q.acc[o] = 1;
+            q.out[o] = blk(b, w, k); q.useacc[o] = 1;
             if (k >= 1) q.add[o][na++] = frame(b, t - 1);
             if (k <= 1) q.add[o][na++] = frame(b, t + 1);
             q.nadd[o] = na;
         }
-    } else if (p.mode == SS_E2E) {
+    } else if (p.mode == WIN_MIX_E2E) {
         const int b = u / (3 * W), w = (u / 3) % W, k = u % 3;
         int na = 0;
-        q.src[q.nsrc++] = blk(b, w, k);
-        q.out[0] = blk(b, w, k); q.acc[0] = 1; q.nout = 1;
+        src[nsrc++] = blk(b, w, k);
+        q.out[0] = blk(b, w, k); q.useacc[0] = 1; q.nout = 1;
         if (k >= 1) q.add[0][na++] = blk(b, w, k - 1);
         if (k <= 1) q.add[0][na++] = blk(b, w, k + 1);
         q.nadd[0] = na;
-    } else if (p.mode == SS_E2M) {
+    } else if (p.mode == WIN_MIX_E2M) {
         const int b = u / W, w = u % W;
-        q.src[q.nsrc++] = blk(b, w, 1);
-        q.out[0] = mid(b, w); q.acc[0] = 1; q.nout = 1;
+        src[nsrc++] = blk(b, w, 1);
+        q.out[0] = mid(b, w); q.useacc[0] = 1; q.nout = 1;
         q.add[0][0] = blk(b, w, 0); q.add[0][1] = blk(b, w, 2); q.nadd[0] = 2;
-    } else if (p.mode == SS_M2E) {
+    } else if (p.mode == WIN_MIX_M2E) {
         const int b = u / W, w = u % W;
-        q.src[q.nsrc++] = mid(b, w);
+        src[nsrc++] = mid(b, w);
         q.nout = 3;
         for (int k = 0; k < 3; ++k) {
-            q.out[k] = blk(b, w, k); q.acc[k] = k == 1; q.nadd[k] = k == 1 ? 0 : 1; q.add[k][0] = mid(b, w);
+            q.out[k] = blk(b, w, k); q.useacc[k] = k == 1; q.nadd[k] = k == 1 ? 0 : 1; q.add[k][0] = mid(b, w);
         }
-    } else {                                                    // SS_E2F
+    } else {                                                    // WIN_MIX_E2F
         const int b = u / T, t = u % T;
         for (int k = 0; k < 3; ++k) {
             const int w = t - k;
-            if (w >= 0 && w < W) q.src[q.nsrc++] = blk(b, w, k);
+            if (w >= 0 && w < W) src[nsrc++] = blk(b, w, k);
         }
         int na = 0;
-        q.out[0] = frame(b, t); q.acc[0] = 1; q.nout = 1;
+        q.out[0] = frame(b, t); q.useacc[0] = 1; q.nout = 1;
         if (t < W) q.add[0][na++] = blk(b, t, 1);                           // forward: Z[w, k] took H[w + k - 1] for k >= 1
         if (t - 1 >= 0 && t - 1 < W) q.add[0][na++] = blk(b, t - 1, 2);
         if (t - 1 >= 0 && t - 1 < W) q.add[0][na++] = blk(b, t - 1, 0);     // and H[w + k + 1] for k <= 1
@@ -104,53 +99,14 @@ __device__ __forceinline__ void ss_plan(const SsMix& p, int u, SsPlan& q) {
     }
 }
 
-// one unit and four 16-node tiles per workgroup; 32 channels of the unit's source rows in LDS at a time, L (Np, Np) read from L2
+// a unit's plan by thread 0, then win_mix_body (win_mix_dev.h) runs it: one graph, one phase
 __global__ __launch_bounds__(256) void ss_mix_kernel(SsMix p) {
     extern __shared__ __attribute__((aligned(16))) float slab[];            // [Np][NODE_MIX_P]
     __shared__ SsPlan q;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, j = lane & 15, kk = lane >> 4;
-    const int n0 = (blockIdx.y * 4 + wave) * 16;
-    const bool active = n0 < p.Np;
-    if (tid == 0) ss_plan(p, blockIdx.x, q);
+    if (threadIdx.x == 0) ss_plan(p, blockIdx.x, q);
     __syncthreads();
-    const int nsrc = q.nsrc, nout = q.nout;
-    for (int cg = 0; cg * 32 < p.c; ++cg) {
-        __syncthreads();                                                    // the previous group's reads of the slab are done
-        for (int f = tid; f < p.Np * 8; f += 256) {
-            const int m = f >> 3, c4 = f & 7;
-            float4 v = f4zero();
-            if (m < p.N && 32 * cg + 4 * c4 < p.c) {
-                for (int s = 0; s < nsrc; ++s) {
-                    const float4 a = ld4(p.In + (size_t)(q.src[s] + m) * p.c + 32 * cg + 4 * c4);
-                    v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-                }
-            }
-            st4(slab + m * NODE_MIX_P + 4 * c4, v);
-        }
-        __syncthreads();
-        if (!active) continue;
-        f32x4 acc[2];
-        acc[0] = acc[1] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        node_mix_slab(acc, p.L + (size_t)(n0 + j) * p.Np + 4 * kk, slab, p.Np, j, kk);
-        // ---- epilogue in the accumulator layout: reg r = (node n0 + kk*4 + r, channel 32 cg + 16 ct + j) ----
-        for (int o = 0; o < nout; ++o) {
-            const long ob = q.out[o];
-            const int useacc = q.acc[o], na = q.nadd[o];
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                const int ch = 32 * cg + 16 * ct + j;
-                if (ch >= p.c) continue;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int n = n0 + kk * 4 + r;
-                    if (n >= p.N) continue;
-                    float v = useacc ? acc[ct][r] : 0.f;
-                    for (int a = 0; a < na; ++a) v += p.In[(size_t)(q.add[o][a] + n) * p.c + ch];
-                    p.Out[(size_t)(ob + n) * p.c + ch] = v;
-                }
-            }
-        }
-    }
+    const float* const graph[2] = {p.L, p.L};
+    win_mix_body(q, graph, p.Np, p.N, p.c, p.In, p.Out, slab);
 }
 
 // ---- the grouped GEMM -----------------------------------------------------------------------------------------------------------------
@@ -284,10 +240,11 @@ __global__ __launch_bounds__(256) void ss_winwgrad_kernel(SsWgrad p) {
 // ---- entry points ----
 extern "C" int gptst_stsgcn_mix(const float* L, int Np, const float* In, float* Out, int c, int mode, int B, int T, int N, void* stream) {
     if (!L || !In || !Out || In == Out || B <= 0 || T < 3 || N <= 0 || mode < 0 || mode > 4) return GPTST_EARG;
-    if (Np != 16 * ((N + 15) / 16) || Np > SS_MAX_NP || c < 16 || c % 16) return GPTST_ESHAPE;
+    if (Np != 16 * ((N + 15) / 16) || Np > WIN_MIX_MAX_NP || c < 16 || c % 16) return GPTST_ESHAPE;
     const long W = T - 2;
-    const long units = mode == SS_F2E || mode == SS_E2F ? (long)B * T : mode == SS_E2E ? (long)B * W * 3 : (long)B * W;
+    const long units = mode == WIN_MIX_F2E || mode == WIN_MIX_E2F ? (long)B * T : mode == WIN_MIX_E2E ? (long)B * W * 3 : (long)B * W;
     if (units > 0x7fffffffL) return GPTST_ESHAPE;
+    static_assert(WIN_MIX_MAX_NP * NODE_MIX_P * sizeof(float) + sizeof(SsPlan) <= 64 * 1024, "slab + plan exceed the default dynamic LDS");
     const size_t smem = (size_t)Np * NODE_MIX_P * sizeof(float);
     SsMix p{L, Np, In, Out, c, mode, T, N};
     hipLaunchKernelGGL(ss_mix_kernel, dim3((unsigned)units, (Np / 16 + 3) / 4), dim3(256), smem, (hipStream_t)stream, p);

@@ -1401,17 +1401,22 @@ MIX_F2E, MIX_E2E, MIX_E2M, MIX_M2E, MIX_E2F = 0, 1, 2, 3, 4
 _MIX_ROWS = {MIX_F2E: ("f", "e"), MIX_E2E: ("e", "e"), MIX_E2M: ("e", "m"), MIX_M2E: ("m", "e"), MIX_E2F: ("e", "f")}
 
 
+def _win_mix(entry, graphs, In, mode, span, B, T, N):
+    """what stsgcn_mix and stfgnn_mix share: the row counts by layout for windows of ``span`` frames, the output, the tag and the byte count"""
+    _chk(*graphs, In)
+    W, c, Np = T - span + 1, In.shape[1], graphs[0].shape[0]
+    rows = {"f": B * T * N, "e": B * W * span * N, "m": B * W * N}
+    src, dst = _MIX_ROWS[mode]
+    assert In.shape[0] == rows[src] and graphs[0].dim() == 2 and all(g.shape == graphs[0].shape for g in graphs), (In.shape, mode, B, T, N)
+    Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
+    _call(entry, *(_p(g) for g in graphs), Np, _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
+    return Out
+
+
 def stsgcn_mix(Lp, In, mode, B, T, N):
     """mix(S)_k = L S_k + [k >= 1] S_{k-1} + [k <= 1] S_{k+1} without the (3N, 3N) matrix; Lp (Np, Np) = A^ zero-padded (its transpose for the
     adjoints).  mode: MIX_F2E frames -> expanded, MIX_E2E, MIX_E2M (the middle block only), MIX_M2E (adjoint of E2M), MIX_E2F (adjoint of F2E)."""
-    _chk(Lp, In)
-    W, c = T - 2, In.shape[1]
-    rows = {"f": B * T * N, "e": B * W * 3 * N, "m": B * W * N}
-    src, dst = _MIX_ROWS[mode]
-    assert In.shape[0] == rows[src] and Lp.dim() == 2, (In.shape, mode, B, T, N)
-    Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
-    _call("gptst_stsgcn_mix", _p(Lp), Lp.shape[0], _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
-    return Out
+    return _win_mix("gptst_stsgcn_mix", (Lp,), In, mode, 3, B, T, N)
 
 
 def stsgcn_wingemm(X, Wt, bias, act, B, W, R, N, keep=False, best=None, which=None, opj=0):
@@ -1464,14 +1469,7 @@ def stfgnn_mix(Sp, Dp, In, mode, B, T, N):
     """the product with the (4N, 4N) fusion graph as blocks: mix(X)_0 = mix(X)_3 = D (X_0 + X_3) + X_1 + X_2, mix(X)_k = S X_k + the other three
     for k = 1, 2.  Sp, Dp (Np, Np) = S^ and D zero-padded (their transposes for the adjoints).  mode: MIX_F2E frames -> expanded, MIX_E2E,
     MIX_E2M (block 1 only), MIX_M2E (adjoint of E2M), MIX_E2F (adjoint of F2E)."""
-    _chk(Sp, Dp, In)
-    W, c = T - 3, In.shape[1]
-    rows = {"f": B * T * N, "e": B * W * 4 * N, "m": B * W * N}
-    src, dst = _MIX_ROWS[mode]
-    assert In.shape[0] == rows[src] and Sp.dim() == 2 and Sp.shape == Dp.shape, (In.shape, mode, B, T, N)
-    Out = torch.empty(rows[dst], c, device=In.device, dtype=torch.float32)
-    _call("gptst_stfgnn_mix", _p(Sp), _p(Dp), Sp.shape[0], _p(In), _p(Out), c, mode, B, T, N, tag="m%d c%d T%d" % (mode, c, T), nbytes=_nb(In, Out))
-    return Out
+    return _win_mix("gptst_stfgnn_mix", (Sp, Dp), In, mode, 4, B, T, N)
 
 
 # ---- the downstream STGODE predictor (csrc/stgode.hip) ----------------------------------------------------------------------------------

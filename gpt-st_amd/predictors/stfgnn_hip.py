@@ -15,8 +15,8 @@ w + k, and the last operation's output, the running max and the gated branch are
                     T -> T - 3 frames) over the weight [conv2; conv1] stacked tap-major — the kernel's gate is tanh(P) sigmoid(Q), so tanh takes
                     conv2.  The stacking is torch's, which carries the gradient of the stacked weight back onto conv1 and conv2 in their
                     (Cout, C, 1, 2) shape.  The sum of the two branches is a torch add.
-    backward        windows, per operation, last to first: dPre (ops.stsgcn_gate_bwd: the upstream gradient plus dOut where this operation
-                    won), dW and db per window (ops.stsgcn_winwgrad), dZ = dPre W (the grouped GEMM with the mirrored weights), then the
+    backward        windows (windows_hip.LayerFn, the layer function stsgcn_hip.py runs too), per operation, last to first: dPre
+                    (ops.stsgcn_gate_bwd: the upstream gradient plus dOut where this operation won), dW and db per window (ops.stsgcn_winwgrad), dZ = dPre W (the grouped GEMM with the mirrored weights), then the
                     adjoint mix with S^T and D^T: middle -> expanded, expanded -> expanded, and for the first operation expanded -> frames.
                     Gate: dPre (ops.mtgnn_gate_bwd), dW and db (ops.mtgnn_wgrad), dX = the mirrored tap GEMM with offsets (0, -3).
     kept in torch   the position-embedding add (a broadcast add: autograd gives its gradients), the sum of the branches and the heads, stacked:
@@ -28,61 +28,17 @@ backward to serve (no_grad, eval mode: keep = False) nothing is kept.
 import torch
 
 from .. import _C, ops
-from ..ops import ACT_GLU, ACT_NONE, ACT_RELU
-from . import rows_hip
-from .rows_hip import TapFn, is_hip_input, mirror, widths_ok
+from ..ops import ACT_RELU
+from . import rows_hip, windows_hip
+from .rows_hip import TapFn, mirror
+from .windows_hip import MAX_NODES, LayerFn, Mix            # noqa: F401  (MAX_NODES: the bound of the mix's slab, under this module's name too)
 
-MAX_NODES = 448            # the mix keeps a (Np, 36) slab of a block in the 64 KB of LDS a launch gets by default
+SPAN = 4                   # frames of a window
 GATE_OFFS = (0, 3)         # the two taps of conv1 / conv2: dilation 3 along T
 
 
-class _LayerFn(torch.autograd.Function):
-    """best (B W N, co) = max over the J operations of a layer; H (B T N, ci) with the embeddings added; wb = W_0, b_0, W_1, b_1, ...: the stacked
-    weights (W, 2 co, ci) and biases"""
-
-    @staticmethod
-    def forward(ctx, H, sp, dp, spt, dpt, B, T, N, keep, *wb):
-        keep = keep and any(ctx.needs_input_grad)
-        W, J = T - 3, len(wb) // 2
-        co = wb[0].shape[1] // 2
-        best = torch.empty(B * W * N, co, device=H.device, dtype=torch.float32)
-        which = torch.empty(B * W * N, co, device=H.device, dtype=torch.int32) if keep else None
-        cur, saved = H, []
-        for j in range(J):
-            last = j == J - 1
-            Z = ops.stfgnn_mix(sp, dp, cur, ops.MIX_F2E if j == 0 else ops.MIX_E2M if last else ops.MIX_E2E, B, T, N)       # (J >= 2: supported())
-            R = N if last else 4 * N
-            out = ops.stsgcn_wingemm(Z, wb[2 * j], wb[2 * j + 1], ACT_GLU, B, W, R, N, keep=keep, best=best, which=which, opj=j)
-            if keep:
-                cur, S, A = out
-                saved += [Z, S, A]
-            else:
-                cur = out
-        if keep:
-            ctx.cfg = (B, T, N, J)
-            ctx.save_for_backward(spt, dpt, which, *wb[0::2], *saved)
-        return best
-
-    @staticmethod
-    def backward(ctx, dBest):
-        B, T, N, J = ctx.cfg
-        spt, dpt, which = ctx.saved_tensors[:3]
-        Ws, saved = ctx.saved_tensors[3:3 + J], ctx.saved_tensors[3 + J:]
-        W = T - 3
-        dBest = dBest.contiguous()
-        grads, up = [None] * (2 * J), None
-        for j in range(J - 1, -1, -1):
-            Z, S, A = saved[3 * j:3 * j + 3]
-            R = N if j == J - 1 else 4 * N
-            dPre = ops.stsgcn_gate_bwd(up, dBest, which, j, S, A, B, W, R, N)
-            if ctx.needs_input_grad[9 + 2 * j] or ctx.needs_input_grad[10 + 2 * j]:
-                grads[2 * j], grads[2 * j + 1] = ops.stsgcn_winwgrad(dPre, Z, B, W, R)
-            if j == 0 and not ctx.needs_input_grad[0]:
-                up = None
-                break
-            dZ = ops.stsgcn_wingemm(dPre, Ws[j].transpose(1, 2).contiguous(), None, ACT_NONE, B, W, R, N)
-            up = ops.stfgnn_mix(spt, dpt, dZ, ops.MIX_E2F if j == 0 else ops.MIX_M2E if j == J - 1 else ops.MIX_E2E, B, T, N)
-        return (up, None, None, None, None, None, None, None, None) + tuple(grads)
+def _mix(graphs, X, mode, B, T, N):
+    return ops.stfgnn_mix(*graphs, X, mode, B, T, N)
 
 
 class _GateFn(torch.autograd.Function):
@@ -128,17 +84,9 @@ def supported(model, x):
     """the HIP path serves: CUDA fp32 4-D input of the module's window and node count, GLU, no mask, an adjacency that graph.stfgnn_blocks
     recognises as a fusion graph, at least two operations per layer of equal widths, channel widths that are multiples of 16 up to 128, and a
     node count whose slab fits the default LDS of a launch (N <= 448)"""
-    if not is_hip_input(x) or model.activation != "GLU" or model.use_mask or model.s_hat is None or model.d_hat is None:
+    if model.s_hat is None or model.d_hat is None:
         return False
-    fe = model.First_FC
-    if x.shape[1] != model.window or x.shape[2] != model.num_nodes or x.shape[3] != fe.in_features or model.num_nodes > MAX_NODES:
-        return False
-    widths = [fe.in_features, fe.out_features]
-    for f in model.hidden_dims:
-        if len(f) < 2 or len(set(f)) != 1:
-            return False
-        widths += f
-    return widths_ok(widths)
+    return windows_hip.supported(model, x, model.First_FC, model.window, model.hidden_dims)
 
 
 def forward(model, x, keep=True):
@@ -147,14 +95,12 @@ def forward(model, x, keep=True):
     _C.lib()
     B, T, N, _ = x.shape
     sp, dp, spt, dpt = padded_graphs(model)
+    mix = Mix(_mix, (sp, dp), (spt, dpt))
     fe = model.First_FC
     h = TapFn.apply(x.contiguous().view(B * T * N, -1), fe.weight.contiguous(), fe.bias.contiguous(), None, (0,), ACT_RELU, 0, T, N, keep)
     for lay in model.STSGCLS:
         H = lay.embed(h.view(B, T, N, -1)).reshape(B * T * N, -1)
-        wb = []
-        for j in range(len(lay.out_dims)):
-            wb += lay.stacked(j)
         Wg, bg = gate_weight(lay)
-        h = _LayerFn.apply(H, sp, dp, spt, dpt, B, T, N, keep, *wb) + _GateFn.apply(H, Wg, bg, B, T, N, keep)
-        T -= 3
+        h = LayerFn.apply(H, mix, SPAN, B, T, N, keep, *windows_hip.stacked_weights(lay, len(lay.out_dims))) + _GateFn.apply(H, Wg, bg, B, T, N, keep)
+        T -= SPAN - 1
     return model.head(h.view(B, T, N, -1))

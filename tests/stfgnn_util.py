@@ -118,7 +118,7 @@ def gate_manual(lay, H, dG):
 
 
 def layer_manual(lay, S, D, H, dBest):
-    """the window branch of one layer (H: embeddings added) launch by launch as predictors/stfgnn_hip._LayerFn runs it, forward and the
+    """the window branch of one layer (H: embeddings added) launch by launch as predictors/windows_hip.LayerFn runs it, forward and the
     hand-written backward -> (best, which, dH, [dW_j], [db_j]) with dW_j (W, cw, ci) per window"""
     J, saved = len(lay.out_dims), []
     cur, best, which = H, None, None

@@ -80,7 +80,7 @@ def mix_e2f(a_t, G):
 
 
 def layer_manual(lay, a_hat, H, dBest):
-    """one layer (H: embeddings added) launch by launch as predictors/stsgcn_hip._LayerFn runs it, forward and the hand-written backward
+    """one layer (H: embeddings added) launch by launch as predictors/windows_hip.LayerFn runs it, forward and the hand-written backward
     -> (best, which, dH, [dW_j], [db_j]) with dW_j (W, cw, ci) per window"""
     J, saved = len(lay.filters), []
     cur, best, which = H, None, None

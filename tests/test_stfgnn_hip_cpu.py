@@ -93,7 +93,7 @@ def test_block_algebra_is_the_module(T, layers, dim_out):
 
 @pytest.mark.parametrize("T", [4, 7, 12])
 def test_hand_written_backward_of_a_layer(T):
-    """the launch sequence of _LayerFn — gate backward with the winner index, weight gradient per window, mirrored GEMM, the three adjoint forms
+    """the launch sequence of LayerFn — gate backward with the winner index, weight gradient per window, mirrored GEMM, the three adjoint forms
     of the mix — and of _GateFn, against autograd through the module's layer"""
     m = _model(T, 1)
     lay = m.STSGCLS[0]

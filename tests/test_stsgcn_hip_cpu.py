@@ -41,7 +41,7 @@ def test_block_algebra_is_the_module(T, layers, module_type, dim_out):
 
 @pytest.mark.parametrize("T,module_type", [(5, "individual"), (12, "individual"), (6, "sharing")])
 def test_hand_written_backward_of_a_layer(T, module_type):
-    """the launch sequence of _LayerFn — gate backward with the winner index, weight gradient per window, mirrored GEMM, the three adjoint forms
+    """the launch sequence of LayerFn — gate backward with the winner index, weight gradient per window, mirrored GEMM, the three adjoint forms
     of the mix — against autograd through the module's layer"""
     m = _model(T, 1, module_type)
     lay, a_hat = m.stsgcl_layers[0].layer, m.a_hat

@@ -3,8 +3,11 @@
 the protocol of profiles/downstream_rowgemm_ab.txt.  The library is chosen with GPTST_LIB; the timing is the tools' own (mb_downstream.ab_predictor,
 mb_tgcn.ab_tiles, device events around each launch through ops.TIMER).
 usage (GPU box, repo root):
-    GPTST_LIB=... python tools/ab_recurrence.py --measure OUT.json [tgcn] [msdr] [tiles]     one process: the lines below (default: all) ->
+    GPTST_LIB=... python tools/ab_recurrence.py --measure OUT.json [tgcn] [msdr] [tiles]     one process: the lines below (default: these three) ->
                                                                         {line: [median, min, max]}
+    GPTST_LIB=... python tools/ab_recurrence.py --measure OUT.json stsgcn stfgnn             the same for the two window predictors (csrc/stsgcn.hip,
+                                                                        csrc/stfgnn.hip, win_mix_dev.h) at mb_stsgcn.py's / mb_stfgnn.py's two shapes
+                                                                        each; in-pass: the median launch of the mix entry, per mode
     python tools/ab_recurrence.py --table parent=A.json,B.json,C.json refactor=D.json,E.json,F.json       (no GPU) -> the table, on stdout
 Lines of a process: the TGCN predictor (mb_tgcn.py's shape) and the MSDR predictor (mb_msdr.py's two shapes), HIP backend, forward + backward and
 forward under no_grad, ms; per pass the median launch of each step entry inside 10 forward + backward passes ("in-pass"), us; the four TGCN step
@@ -22,11 +25,19 @@ def measure(out_path, parts):
     import torch
     import mb_downstream as mb
     import mb_msdr
+    import mb_stfgnn
+    import mb_stsgcn
     import mb_tgcn
     from gptst_amd import ops
     res = {}
 
-    def predictor_lines(label, predictor, shape, **kw):
+    def recurrence(name, tag):
+        return name if "_tgcn_" in name or "_msdr_" in name else None
+
+    def mix_by_mode(name, tag):                              # tag "m<mode> c<width> T<frames>": one line per mode, the layers' launches together
+        return name + " " + tag.split()[0] if name.endswith("_mix") else None
+
+    def predictor_lines(label, predictor, shape, inpass=recurrence, **kw):
         m, x, w, _ = mb.ab_predictor(predictor, shape, verdicts=False, **kw)
         hip = next(s for s in reversed(mb.LINES) if s.startswith("  hip "))
         v = [float(g) for g in re.search("forward \\+ backward " + NUM + " +forward only \\(no_grad\\) " + NUM, hip).groups()]
@@ -37,9 +48,10 @@ def measure(out_path, parts):
             mb.fb(m, x, w)
             torch.cuda.synchronize()
             acc = {}
-            for name, _tag, e0, e1, _n in ops.TIMER:
-                if "_tgcn_" in name or "_msdr_" in name:
-                    acc.setdefault(name, []).append(e0.elapsed_time(e1) * 1e3)
+            for name, tag, e0, e1, _n in ops.TIMER:
+                key = inpass(name, tag)
+                if key is not None:
+                    acc.setdefault(key, []).append(e0.elapsed_time(e1) * 1e3)
             ops.TIMER = None
             for name, t in acc.items():
                 per.setdefault((name, len(t)), []).append(statistics.median(t))
@@ -52,6 +64,9 @@ def measure(out_path, parts):
         predictor_lines("tgcn", mb_tgcn.predictor, mb_tgcn.SHAPE)
     for ds, shape in mb_msdr.SHAPES if "msdr" in parts else ():
         predictor_lines("msdr %s" % ds, mb_msdr.make_predictor(ds), shape, warm=3, reps=5)
+    for part, tool in (("stsgcn", mb_stsgcn), ("stfgnn", mb_stfgnn)):
+        for ds, shape in tool.SHAPES if part in parts else ():
+            predictor_lines("%s %s" % (part, ds), tool.make_predictor(ds), shape, inpass=mix_by_mode, warm=3, reps=5)
     if "tiles" in parts:
         mb_tgcn.ab_tiles()
     for s in mb.LINES:
