@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -37,7 +37,7 @@ def load_series(args, dev):
     return data_root, gdata.get_dataloader(args, root=data_root, device=dev, raw=raw, generator=g)
 
 
-EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA", "STMGCN")      # what -mode eval builds
+EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA", "STMGCN", "CCRNN")      # what -mode eval builds
 
 
 def main():
@@ -49,7 +49,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -187,16 +187,37 @@ def stmgcn_graphs(args, data_root, A, train):
     return graph.stmgcn_supports(raw["dis"]), graph.stmgcn_supports(raw["pcc"])
 
 
+CCRNN_HOLDOUT = 1700                 # reference CCRNN_demand/args.py:113,116: _len = [850, 850], the frames kept away from the support
+
+
+def ccrnn_support(args, pargs, data_root, loaders, scaler, holdout=CCRNN_HOLDOUT):
+    """CCRNN's (N, N) support (reference model/CCRNN_demand/args.py:40-76, 112-120) from the dataset's raw first two channels (pick-up and
+    drop-off: the arrays the reference reads from its h5 files), all but the last ``holdout`` frames.  ``<data_root>/<ds>/<file>.npz`` where it
+    exists; otherwise, or where the series is too short for that holdout — this fallback is the project's own, the reference has none — the
+    training split of the loaded series put back to real values, whole."""
+    from gptst_amd import graph
+    path = os.path.join(data_root, gdata.DATASETS[args.dataset][0])
+    series = None
+    if os.path.exists(path):
+        series = np.load(path)["data"][..., :2].astype(np.float64)
+    if series is None or series.ndim != 3 or series.shape[-1] < 2 or series.shape[0] <= holdout:
+        tr = loaders[0].series[:, :, :2].detach().cpu().double().numpy() * float(scaler.std) + float(scaler.mean)
+        print("gpt-st_amd: CCRNN support from the %s training split %s alone (no raw series of more than %d frames at %s)"
+              % (args.dataset, tuple(tr.shape), holdout, path), flush=True)
+        return torch.tensor(graph.ccrnn_support(tr, pargs.hidden_size_data, pargs.normalized_category, 0), dtype=torch.float32)
+    return torch.tensor(graph.ccrnn_support(series, pargs.hidden_size_data, pargs.normalized_category, holdout), dtype=torch.float32)
+
+
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126, model/ST_WA/args.py:33-55 and model/STMGCN_demand/args.py:7-56 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126, model/ST_WA/args.py:33-55, model/STMGCN_demand/args.py:7-56 and model/CCRNN_demand/args.py:79-121 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STMGCN, STSGCN, STWA, TGCN
+    from gptst_amd.predictors import ASTGCN, CCRNN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STMGCN, STSGCN, STWA, TGCN
     if str(args.model) not in EVAL_MODELS:
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR, -model STWA and -model STMGCN (SURVEY.md §8f rank 4)")
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR, -model STWA, -model STMGCN and -model CCRNN (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -239,6 +260,9 @@ def main_eval(args, dev):
         dis, pcc = stmgcn_graphs(args, data_root, A, train)
         ap = SimpleNamespace(**vars(pargs), dis_graph=dis, pcc_graph=pcc)
         predictor = STMGCN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.stmgcn_backend))
+    elif str(args.model) == "CCRNN":                                             # model/Model.py:86-88, CCRNN_demand/args.py:112-120: the support
+        ap = SimpleNamespace(**vars(pargs), support=ccrnn_support(args, pargs, data_root, (train, val, test), scaler))
+        predictor = CCRNN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.ccrnn_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

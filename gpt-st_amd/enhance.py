@@ -63,5 +63,8 @@ class EnhanceFrontEnd(nn.Module):
         eb = fusion_gate(x_pretrain_flow, source, self.fusion, self.lin_test, self.input_base_dim)
         if self.predictor is None:
             return eb
-        x = self.predictor(eb)
+        if getattr(self.predictor, "takes_targets", False):                # :110-114 (CCRNN): the labels feed the decoder's teacher forcing
+            x = self.predictor(eb, None if label is None else label[..., :self.input_base_dim], None)
+        else:
+            x = self.predictor(eb)
         return x, x, x, x, x

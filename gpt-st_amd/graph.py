@@ -368,3 +368,40 @@ def stmgcn_correlation(series):
     c = (s.T @ s) / np.maximum(np.outer(sd, sd), 1e-30)
     np.fill_diagonal(c, 0.0)
     return c.astype(np.float32)
+
+
+def ccrnn_support(series, hidden_size_data, normalized_category="randomwalk", holdout=1700):
+    """The (N, N) float64 support ``predictors.CCRNN`` takes its node vectors from, as the reference builds it (model/CCRNN_demand/args.py:33-76
+    ``preprocessing_for_metric``, ``random_walk_matrix``; normalization.py ``Standard``), in numpy as there.  series (T, N, 2): the pick-up and
+    drop-off channels.
+
+        z = (series - mean) / std over the whole array;  as (T, 2, N), the last ``holdout`` frames dropped, rows (t, channel)
+        u, s, v = svd(rows);  w = (diag(s[:h]) v[:h]).T            (N, h): every node's coordinates on the first h right singular vectors
+        d = pairwise Euclidean distances of w;  support = exp(-d / std(d)^2) - I;  'randomwalk': D^-1 support (an empty row stays 0)
+
+    A sign flip of a right singular vector flips a column of w, which the distances do not see.  ``'laplacian'`` is refused: the reference's
+    ``normalized_laplacian`` multiplies the identity by the SHAPE TUPLE of the degree vector, not by its inverse square roots, so what it
+    returns is I - N^2 support; no shipped conf selects it and the slip is not reproduced.  Any other category leaves the matrix as it is,
+    as the reference does."""
+    if normalized_category == "laplacian":
+        raise ValueError("ccrnn_support: normalized_category 'laplacian' is not built: the reference's normalized_laplacian scales by the shape of "
+                         "the degree vector instead of its inverse square roots (args.py:17-23); use 'randomwalk'")
+    x = np.asarray(series, dtype=np.float64)
+    if x.ndim != 3 or x.shape[2] != 2:
+        raise ValueError("ccrnn_support: series must be (T, N, 2), got %r" % (x.shape,))
+    if not 0 <= holdout < x.shape[0]:                                          # (0: nothing is held out — the reference's own slice cannot say that)
+        raise ValueError("ccrnn_support: holdout %r leaves nothing of %d frames" % (holdout, x.shape[0]))
+    z = (1. * (x - np.mean(x)) / np.std(x)).transpose(0, 2, 1)[:x.shape[0] - holdout]
+    rows = z.reshape(-1, z.shape[2])
+    _, s, v = np.linalg.svd(rows, full_matrices=False)
+    h = int(hidden_size_data)
+    w = np.diag(s[:h]).dot(v[:h, :]).T
+    d = np.sqrt(((w[:, None, :] - w[None, :, :]) ** 2).sum(-1))
+    support = np.exp(d * -1 / np.std(d) ** 2) - np.identity(d.shape[0])
+    if normalized_category == "randomwalk":
+        deg = support.sum(1)
+        with np.errstate(divide="ignore"):
+            d_inv = np.power(deg, -1)
+        d_inv[np.isinf(d_inv)] = 0.
+        support = (np.eye(d_inv.shape[0]) * d_inv).dot(support)
+    return support

@@ -1280,6 +1280,69 @@ def tgcn_bwd_state(LpT, W0hT, dpre0, dh_part, t, dh_out, B, T, N, tiles=0):
           nbytes=_tg_nb(LpT, W0hT, dh_part, 4))      # dpre0 (2), dh_part, dh_out
 
 
+# ---- the downstream CCRNN predictor's graph-GRU cell (csrc/ccrnn.hip) ------------------------------------------------------------------------
+# P (ks, Np, Np) the polynomial stack; step tensors (B*N, width), seq tensors (B*T*N, width) as for TGCN; Cp = the width of the cell's input
+# inside the slab (0: the input half is hoisted into g)
+def _cc_g(g, NO):
+    """(Gx, bias) of a launch: g is the hoisted seq tensor (2-D) or the bias vector (1-D)"""
+    assert g.shape[-1] == NO
+    return (g, None) if g.dim() == 2 else (None, g)
+
+
+def ccrnn_fwd_gates(P, W0, h, g, t, u, q, B, T, N, inp=None, fb=None, inp_out=None, r=None, z=None, tiles=0):
+    """[r, u] = sigmoid([z | P_j z]_j W0^T + g), z = [h | inp] -> u, q = r h, and when given r and z (seq, W0.shape[1]).  fb = (h_top, W, b):
+    inp = h_top W^T + b formed on load and stored in inp_out"""
+    Hp = h.shape[1]
+    Gx, bias = _cc_g(g, 2 * Hp)
+    fh, fW, fbias = fb if fb is not None else (None, None, None)
+    Cp = inp.shape[1] if inp is not None else (fW.shape[0] if fb is not None else 0)
+    _chk(P, W0, h, g, u, q, r, z, inp, fh, fW, fbias, inp_out)
+    assert W0.shape == (2 * Hp, (P.shape[0] + 1) * (Hp + Cp)) and h.shape[0] == B * N and u.shape == q.shape == h.shape
+    assert (Gx is None or Gx.shape[0] == B * T * N) and (z is None or z.shape == (B * T * N, W0.shape[1]))
+    assert fb is None or (fh.shape == h.shape and fW.shape == (Cp, Hp) and fbias.shape == (Cp,) and inp_out.shape == (B * N, Cp))
+    assert inp is None or inp.shape == (B * N, Cp)
+    _call("gptst_ccrnn_fwd_gates", _p(P), P.shape[1], P.shape[0], _p(W0), _p(h), _p(inp), Cp, _p(fh), _p(fW), _p(fbias), _p(inp_out), _p(Gx), _p(bias),
+          _p(u), _p(r), _p(q), _p(z), B, T, N, Hp, t, tiles, tag="Hp%d Cp%d k%d" % (Hp, Cp, P.shape[0]),
+          nbytes=_tg_nb(P, W0, h, 5 + (r is not None)) + (z.shape[1] * B * N * 4 if z is not None else 0))
+
+
+def ccrnn_fwd_state(P, W1, q, g, t, u, h, h_out, B, T, N, inp=None, c=None, z=None, tiles=0):
+    """c = tanh([z | P_j z]_j W1^T + g), z = [q | inp] -> h_out = u h + (1 - u) c, and when given c and z"""
+    Hp = h.shape[1]
+    Gx, bias = _cc_g(g, Hp)
+    Cp = inp.shape[1] if inp is not None else 0
+    _chk(P, W1, q, g, u, h, h_out, c, z, inp)
+    assert W1.shape == (Hp, (P.shape[0] + 1) * (Hp + Cp)) and h.shape[0] == B * N and u.shape == q.shape == h_out.shape == h.shape
+    assert (Gx is None or Gx.shape[0] == B * T * N) and (z is None or z.shape == (B * T * N, W1.shape[1])) and (inp is None or inp.shape[0] == B * N)
+    _call("gptst_ccrnn_fwd_state", _p(P), P.shape[1], P.shape[0], _p(W1), _p(q), _p(inp), Cp, _p(Gx), _p(bias), _p(u), _p(h), _p(h_out), _p(c), _p(z),
+          B, T, N, Hp, t, tiles, tag="Hp%d Cp%d k%d" % (Hp, Cp, P.shape[0]),
+          nbytes=_tg_nb(P, W1, h, 5 + (c is not None)) + (z.shape[1] * B * N * 4 if z is not None else 0))
+
+
+def ccrnn_bwd_cand(PT, W1T, dh, u, c, r, h, t, dpre1, dpre0, dh_part, B, T, N, dh2=None, dinp=None, tiles=0):
+    """dpre1[:, t] = (dh + dh2)(1 - u)(1 - c^2);  [dq | dinp] = [dpre1 | P_j^T dpre1]_j W1T^T;  dpre0[:, t] = [dq h r (1 - r) | (dh + dh2)(h - c) u (1 - u)];
+    dh_part = (dh + dh2) u + dq r"""
+    _chk(PT, W1T, dh, dh2, u, c, r, h, dpre1, dpre0, dh_part, dinp)
+    Hp = h.shape[1]
+    Cp = dinp.shape[1] if dinp is not None else 0
+    assert W1T.shape == (Hp + Cp, (PT.shape[0] + 1) * Hp) and h.shape[0] == B * N and dpre1.shape == (B * T * N, Hp) and dpre0.shape == (B * T * N, 2 * Hp)
+    assert dh.shape == u.shape == c.shape == r.shape == dh_part.shape == h.shape and (dh2 is None or dh2.shape == h.shape)
+    assert dinp is None or dinp.shape[0] == B * N
+    _call("gptst_ccrnn_bwd_cand", _p(PT), PT.shape[1], PT.shape[0], _p(W1T), Cp, _p(dh), _p(dh2), _p(u), _p(c), _p(r), _p(h), _p(dpre1), _p(dpre0),
+          _p(dh_part), _p(dinp), B, T, N, Hp, t, tiles, tag="Hp%d Cp%d k%d" % (Hp, Cp, PT.shape[0]), nbytes=_tg_nb(PT, W1T, h, 9 + (dh2 is not None)))
+
+
+def ccrnn_bwd_state(PT, W0T, dpre0, dh_part, t, dh_out, B, T, N, dinp=None, tiles=0):
+    """dh_out = dh_part + dstate, dinp += dinput of [dpre0[:, t] | P_j^T dpre0[:, t]]_j W0T^T"""
+    _chk(PT, W0T, dpre0, dh_part, dh_out, dinp)
+    Hp = dh_part.shape[1]
+    Cp = dinp.shape[1] if dinp is not None else 0
+    assert W0T.shape == (Hp + Cp, (PT.shape[0] + 1) * 2 * Hp) and dh_part.shape[0] == B * N and dpre0.shape == (B * T * N, 2 * Hp)
+    assert dh_out.shape == dh_part.shape and (dinp is None or dinp.shape[0] == B * N)
+    _call("gptst_ccrnn_bwd_state", _p(PT), PT.shape[1], PT.shape[0], _p(W0T), Cp, _p(dpre0), _p(dh_part), _p(dh_out), _p(dinp), B, T, N, Hp, t, tiles,
+          tag="Hp%d Cp%d k%d" % (Hp, Cp, PT.shape[0]), nbytes=_tg_nb(PT, W0T, dh_part, 4))
+
+
 # ---- the downstream MTGNN predictor (csrc/mtgnn.hip): tensors are (B * T * N rows, width) with T the tensor's own frame ----------------------
 def mtgnn_tapgemm(X, W, bias, offs, B, Tsrc, Tdst, N, gated=False, xmask=None, omask=None, res=None, res_frame=None, res_off=0, out=None,
                   keep=False):
@@ -1326,14 +1389,15 @@ def mtgnn_wgrad(D, X, offs, B, Tsrc, Tdst, N, xmask=None, want_bias=True):
 
 
 def mtgnn_graphgrad(D, X, N, c, ks, dcol0=0):
-    """-> dM (ks, N, N), dM_k[v, w] = sum_{unit, ch} D[unit N + v, dcol0 + k c + ch] X[unit N + w, ch]: unit-split partials summed in a fixed order"""
+    """-> dM (ks, N, N), dM_k[v, w] = sum_{unit, ch} D[unit N + v, dcol0 + k c + ch] X[unit N + w, ch]: unit-split partials summed in a fixed order.
+    X may be wider than c: its first c columns are read at its own row pitch (no copy of a column slice)"""
     _chk(D, X)
     rows = X.shape[0]
-    assert D.shape[0] == rows and rows % N == 0 and X.shape[1] == c and D.shape[1] >= dcol0 + ks * c
+    assert D.shape[0] == rows and rows % N == 0 and X.shape[1] >= c and D.shape[1] >= dcol0 + ks * c
     units = rows // N
     ns = _C.lib().value("gptst_mtgnn_graphgrad_nsplit", units, N, ks)
     part = torch.empty(ns, ks, N, N, device=D.device, dtype=torch.float32)
-    _call("gptst_mtgnn_graphgrad", _p(D), D.shape[1], dcol0, _p(X), c, c, ks, _p(part), ns, units, N, tag="c%d ks%d" % (c, ks),
+    _call("gptst_mtgnn_graphgrad", _p(D), D.shape[1], dcol0, _p(X), X.shape[1], c, ks, _p(part), ns, units, N, tag="c%d ks%d" % (c, ks),
           nbytes=rows * (ks + 1) * c * 4 + part.numel() * 4)
     return part.sum(0)
 

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 28  /* 28: + gptst_stmgcn_* (the stacked LSTM of the downstream ST-MGCN predictor on HIP: all T steps of all L layers in ONE launch forward and ONE backward, states in LDS, rows local to their workgroup: csrc/stmgcn.hip); 27: + gptst_stwa_* (the downstream ST-WA predictor on HIP: one cut of a Layer in two launches forward and three backward, generated per-node weights folded from their rank-5 factors, the spatial attention over the nodes of a sample without its N x N scores: csrc/stwa.hip); 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 29  /* 29: + gptst_ccrnn_* (the graph-GRU cell of the downstream CCRNN predictor on HIP: TGCN's GRU step with a multi-polynomial mix, the cell's input in the operand slab, the decoder's feedback formed while the slab is filled: csrc/ccrnn.hip); 28: + gptst_stmgcn_* (the stacked LSTM of the downstream ST-MGCN predictor on HIP: all T steps of all L layers in ONE launch forward and ONE backward, states in LDS, rows local to their workgroup: csrc/stmgcn.hip); 27: + gptst_stwa_* (the downstream ST-WA predictor on HIP: one cut of a Layer in two launches forward and three backward, generated per-node weights folded from their rank-5 factors, the spatial attention over the nodes of a sample without its N x N scores: csrc/stwa.hip); 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -798,6 +798,32 @@ int gptst_stmgcn_lstm_fwd(const float* Gx0, const float* W, const float* bias, f
                           int H, int tiles, void* stream);
 int gptst_stmgcn_lstm_bwd(const float* dTop, const float* WT, const float* gates, const float* c, float* dG, int dG_layers, int rows, int T, int L,
                           int H, int tiles, void* stream);
+
+/* ---- the downstream CCRNN predictor's graph-GRU cell (ccrnn.hip; reference model/CCRNN_demand/CCRNN.py:39-60,198-233, gpt-st_amd/predictors/ccrnn_hip.py) ---
+ * One cell step at one graph-conv layer on one support: P (ks, Np, Np) = [T_1(S) .. T_ks(S)] zero-padded (PT: their transposes), ks <= 3; the
+ * operand slab of sample b is [state part (Hp) | input part (Cp)], Hp in {16, 32}, Cp a multiple of 16, Hp + Cp <= 64; M = [slab | P_j slab]_j.
+ * Step tensors are (B*N, width) with row b N + n, seq tensors (B*T*N, width) with row (b T + t) N + n.  Weights are matrix-major:
+ *   W0 (2 Hp, (ks + 1)(Hp + Cp)) rows [r | u], W1 (Hp, (ks + 1)(Hp + Cp));  W1T (Hp + Cp, (ks + 1) Hp), W0T (Hp + Cp, (ks + 1) 2 Hp): rows [dstate | dinput].
+ * fwd_gates: [r, u] = sigmoid(M([h | inp]) W0^T + g) -> u, q = r h, and when given r and z (seq, (ks + 1)(Hp + Cp)) = M.  g: exactly one of Gx0
+ *   (seq, 2 Hp: the hoisted input half with the bias, Cp = 0) and bias (2 Hp).  With Cp > 0 exactly one of inp (B*N, Cp) and fb_h: then the
+ *   input is fb_h fb_W^T + fb_b (fb_h (B*N, Hp), fb_W (Cp, Hp), fb_b (Cp)) formed on load and stored in inp_out (B*N, Cp).
+ * fwd_state: c = tanh(M([q | inp]) W1^T + g) -> h_out = u h + (1 - u) c, and when given c and z.
+ * bwd_cand: dpre1[:, t] = (dh + dh2)(1 - u)(1 - c^2) (dh2 may be NULL);  [dq | dinp] = M^T-side product with W1T;  dpre0[:, t] = [dq h r (1 - r) |
+ *   (dh + dh2)(h - c) u (1 - u)];  dh_part = (dh + dh2) u + dq r;  dinp (B*N, Cp) = the candidate's share.
+ * bwd_state: dh_out = dh_part + dstate(dpre0[:, t]);  dinp += dinput(dpre0[:, t]).
+ * lds_bytes: the largest dynamic LDS of the four launches; above 160 KB they return GPTST_ESHAPE.  tiles as in gptst_tgcn_*. */
+int gptst_ccrnn_lds_bytes(int N, int Hp, int Cp, int ks, int B);
+int gptst_ccrnn_fwd_gates(const float* P, int Np, int ks, const float* W0, const float* h, const float* inp, int Cp, const float* fb_h,
+                          const float* fb_W, const float* fb_b, float* inp_out, const float* Gx0, const float* bias, float* u, float* r,
+                          float* q, float* z, int B, int T, int N, int Hp, int t, int tiles, void* stream);
+int gptst_ccrnn_fwd_state(const float* P, int Np, int ks, const float* W1, const float* q, const float* inp, int Cp, const float* Gx1,
+                          const float* bias, const float* u, const float* h, float* h_out, float* c, float* z, int B, int T, int N,
+                          int Hp, int t, int tiles, void* stream);
+int gptst_ccrnn_bwd_cand(const float* PT, int Np, int ks, const float* W1T, int Cp, const float* dh, const float* dh2, const float* u,
+                         const float* c, const float* r, const float* h, float* dpre1, float* dpre0, float* dh_part, float* dinp, int B,
+                         int T, int N, int Hp, int t, int tiles, void* stream);
+int gptst_ccrnn_bwd_state(const float* PT, int Np, int ks, const float* W0T, int Cp, const float* dpre0, const float* dh_part,
+                          float* dh_out, float* dinp, int B, int T, int N, int Hp, int t, int tiles, void* stream);
 
 /* ---- communication (comm.hip): RCCL over xGMI with an explicit stream — a collective can sit inside a captured hipGraph -------------
  * The reference has no distributed code; these carry the data-parallel gradient exchange (one all-reduce of [flat gradient | statistics])
