@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN``: a downstream predictor on the
+"""``python Run.py -dataset PEMS08 -mode pretrain [-key value ...]`` (and ``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN | DMVSTNET``: a downstream predictor on the
 enhanced embedding) — same flags as the reference model/Run.py for the
 pretrain mode (reference Run.py:35,49,55-58,63-69,72-74,79-85,115-117,132-143,153-156).  Data: the reference's layout
 ``<root>/<DATASET>/<file>.npz`` with ``['data']`` of shape (L, N, F) under ``-data_root`` (default ../data, as in the reference),
@@ -37,7 +37,7 @@ def load_series(args, dev):
     return data_root, gdata.get_dataloader(args, root=data_root, device=dev, raw=raw, generator=g)
 
 
-EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA", "STMGCN", "CCRNN")      # what -mode eval builds
+EVAL_MODELS = ("STGCN", "TGCN", "MTGNN", "ASTGCN", "STSGCN", "STFGNN", "STGODE", "MSDR", "STWA", "STMGCN", "CCRNN", "DMVSTNET")      # what -mode eval builds
 
 
 def main():
@@ -49,7 +49,7 @@ def main():
     if args.mode == "eval":
         return main_eval(args, dev)
     if args.mode != "pretrain":
-        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN")
+        raise SystemExit("gpt-st_amd implements -mode pretrain and -mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN | DMVSTNET")
     if args.shard == "nodes":
         return main_shard(args, dev)
     dp = None
@@ -208,16 +208,27 @@ def ccrnn_support(args, pargs, data_root, loaders, scaler, holdout=CCRNN_HOLDOUT
     return torch.tensor(graph.ccrnn_support(series, pargs.hidden_size_data, pargs.normalized_category, holdout), dtype=torch.float32)
 
 
+def dmvstnet_adjacency(args, csv_path, A):
+    """DMVSTNET's graph (reference model/DMVSTNET_demand/args.py:32-33): the header-less N x N matrix of ``<data_root>/<DS>/<DS>.csv`` as it is,
+    neither normalised nor thresholded.  Where the file is absent — this fallback is the project's own, the reference has none — the adjacency
+    at hand."""
+    from gptst_amd import graph
+    if os.path.exists(csv_path):
+        return torch.tensor(graph.dmvstnet_adjacency(csv_path, args.num_nodes))
+    print("gpt-st_amd: %s not found -> DMVSTNET runs on the adjacency at hand" % csv_path, flush=True)
+    return torch.tensor(np.asarray(A, dtype=np.float32))
+
+
 def main_eval(args, dev):
-    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
-    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126, model/ST_WA/args.py:33-55, model/STMGCN_demand/args.py:7-56 and model/CCRNN_demand/args.py:79-121 with the values of conf/<model>/<dataset>.conf)."""
+    """``-mode eval -model STGCN | TGCN | MTGNN | ASTGCN | STSGCN | STFGNN | STGODE | MSDR | STWA | STMGCN | CCRNN | DMVSTNET``: train the predictor on the enhanced embedding of the frozen pretrained encoder (reference Run.py
+    mode 'eval', model/Model.py:20-107, model/STGCN/args.py:52-88, model/TGCN/args.py:7-41, model/MTGNN/args.py:6-39, model/STSGCN/args.py:6-51, model/STFGNN/args.py:154-211, model/STGODE/args.py:10-178, model/MSDR/args.py:84-126, model/ST_WA/args.py:33-55, model/STMGCN_demand/args.py:7-56, model/CCRNN_demand/args.py:79-121 and model/DMVSTNET_demand/args.py:6-34 with the values of conf/<model>/<dataset>.conf)."""
     from types import SimpleNamespace
     from gptst_amd import graph
     from gptst_amd.enhance import EnhanceFrontEnd, xavier_downstream_
     from gptst_amd.eval_trainer import EvalTrainer
-    from gptst_amd.predictors import ASTGCN, CCRNN, MSDR, MTGNN, STFGNN, STGCN, STGODE, STMGCN, STSGCN, STWA, TGCN
+    from gptst_amd.predictors import ASTGCN, CCRNN, DMVSTNET, MSDR, MTGNN, STFGNN, STGCN, STGODE, STMGCN, STSGCN, STWA, TGCN
     if str(args.model) not in EVAL_MODELS:
-        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR, -model STWA, -model STMGCN and -model CCRNN (SURVEY.md §8f rank 4)")
+        raise SystemExit("gpt-st_amd -mode eval implements -model STGCN, -model TGCN, -model MTGNN, -model ASTGCN, -model STSGCN, -model STFGNN, -model STGODE, -model MSDR, -model STWA, -model STMGCN, -model CCRNN and -model DMVSTNET (SURVEY.md §8f rank 4)")
     pargs = predictor_args(args.dataset, str(args.model), [a for a in sys.argv[1:] if a.startswith("--") or not a.startswith("-")])
     apply_predictor_overrides(args, pargs)       # reference Run.py:36-43: the predictor's schedule replaces the pretrain conf's (epochs 100, ...)
     if str(args.model) == "ASTGCN" and not args.xavier:
@@ -263,6 +274,9 @@ def main_eval(args, dev):
     elif str(args.model) == "CCRNN":                                             # model/Model.py:86-88, CCRNN_demand/args.py:112-120: the support
         ap = SimpleNamespace(**vars(pargs), support=ccrnn_support(args, pargs, data_root, (train, val, test), scaler))
         predictor = CCRNN(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.ccrnn_backend))
+    elif str(args.model) == "DMVSTNET":                                          # model/Model.py, DMVSTNET_demand/args.py:32-33: the raw adjacency
+        ap = SimpleNamespace(**vars(pargs), adj_mx=dmvstnet_adjacency(args, csv_path, A))
+        predictor = DMVSTNET(ap, dev, args.hidden_dim, args.output_dim, backend=str(args.dmvstnet_backend))
     else:
         ap = SimpleNamespace(Ks=pargs.Ks, Kt=pargs.Kt, num_nodes=args.num_nodes, G=graph.stgcn_graph(A), blocks1=list(pargs.blocks1),
                              drop_prob=pargs.drop_prob, outputl_ks=pargs.outputl_ks)

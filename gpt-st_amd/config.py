@@ -94,6 +94,8 @@ def parse_args(device, argv=None):
     ap.add_argument("-stmgcn_backend", default=FINETUNE_DEFAULTS["stmgcn_backend"], choices=["torch", "hip"], type=str)
     # not a reference option: the same choice for the CCRNN predictor (predictors/ccrnn_hip.py)
     ap.add_argument("-ccrnn_backend", default=FINETUNE_DEFAULTS["ccrnn_backend"], choices=["torch", "hip"], type=str)
+    # not a reference option: the same choice for the DMVSTNET predictor (predictors/dmvstnet_hip.py)
+    ap.add_argument("-dmvstnet_backend", default=FINETUNE_DEFAULTS["dmvstnet_backend"], choices=["torch", "hip"], type=str)
     args, _ = ap.parse_known_args(argv)
     args.interval, args.week_day = DATASET_TIME.get(args.dataset, (5, 7))
     return args
@@ -107,7 +109,8 @@ STEPS_PER_REPLAY = int(os.environ.get("GPTST_STEPS_PER_REPLAY", "4"))
 CKPT_DEFAULTS = dict(ckpt_every=0, ckpt_path="", resume="")
 FINETUNE_DEFAULTS = dict(finetune_encoder=False, encoder_lr_scale=1.0, stgcn_backend="torch", tgcn_backend="torch", mtgnn_backend="torch",
                          astgcn_backend="torch", stsgcn_backend="torch", stfgnn_backend="torch", stgode_backend="torch",
-                         msdr_backend="torch", stwa_backend="torch", stmgcn_backend="torch", ccrnn_backend="torch")
+                         msdr_backend="torch", stwa_backend="torch", stmgcn_backend="torch", ccrnn_backend="torch",
+                         dmvstnet_backend="torch")
 
 
 def make_args(dataset="PEMS08", mode="pretrain", device="cpu", **overrides):
@@ -199,19 +202,28 @@ _CCRNN_KEYS = [("data", "Normal_Method", str), ("data", "normalized_category", s
                ("model", "input_dim", int), ("model", "output_dim", int), ("model", "cl_decay_steps", int),
                ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
 CCRNN_DATASETS = ("NYC_TAXI", "NYC_BIKE")
+# reference model/DMVSTNET_demand/args.py:16-26.  `output_window` is parsed and, as in the reference, read by nothing in the model: the output has
+# input_window steps.  The reference's confs carry nine more [model] keys (cnn_hidden_dim_first, local_image_size, ...) that its args.py never parses.
+_DMVSTNET_KEYS = [("data", "input_window", int), ("data", "output_window", int), ("data", "num_nodes", int), ("model", "hidden_dim", int),
+                  ("model", "topo_embedded_dim", int),
+                  ("train", "seed", int), ("train", "seed_mode", _EVAL), ("train", "xavier", _EVAL), ("train", "loss_func", str)]
+DMVSTNET_DATASETS = ("NYC_TAXI", "NYC_BIKE")
 _PRED_KEYS = {"STGCN": _STGCN_KEYS, "TGCN": _TGCN_KEYS, "MTGNN": _MTGNN_KEYS, "ASTGCN": _ASTGCN_KEYS, "STSGCN": _STSGCN_KEYS,
-              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS, "MSDR": _MSDR_KEYS, "STWA": _STWA_KEYS, "STMGCN": _STMGCN_KEYS, "CCRNN": _CCRNN_KEYS}
-_PRED_DIRS = {"STWA": "ST-WA", "STMGCN": "STMGCN_demand", "CCRNN": "CCRNN_demand"}               # the conf directory where it is not the model's name (the reference's own spelling)
+              "STFGNN": _STFGNN_KEYS, "STGODE": _STGODE_KEYS, "MSDR": _MSDR_KEYS, "STWA": _STWA_KEYS, "STMGCN": _STMGCN_KEYS, "CCRNN": _CCRNN_KEYS,
+              "DMVSTNET": _DMVSTNET_KEYS}
+_PRED_DIRS = {"STWA": "ST-WA", "STMGCN": "STMGCN_demand", "CCRNN": "CCRNN_demand", "DMVSTNET": "DMVSTNET_demand"}               # the conf directory where it is not the model's name (the reference's own spelling)
 
 
 def predictor_args(dataset, model="STGCN", argv=None):
     """The predictor's own argument set (double-dash flags as in the reference): the shared training schedule of
-    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR, STWA, STMGCN and CCRNN are built."""
+    params_predictors.conf, then conf/<model>/<dataset>.conf.  STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR, STWA, STMGCN, CCRNN and DMVSTNET are built."""
     if model not in _PRED_KEYS:
-        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR, STWA, STMGCN and CCRNN predictors only, got %r" % (model,))
+        raise ValueError("gpt-st_amd builds the STGCN, TGCN, MTGNN, ASTGCN, STSGCN, STFGNN, STGODE, MSDR, STWA, STMGCN, CCRNN and DMVSTNET predictors only, got %r" % (model,))
     if model == "STMGCN" and dataset not in STMGCN_DATASETS:                      # reference model/STMGCN_demand/args.py:8-9, before any conf is read
         raise ValueError("Demand prediction baseline. Please select NYC_TAXI or NYC_BIKE dataset!")
     if model == "CCRNN" and dataset not in CCRNN_DATASETS:                        # reference model/CCRNN_demand/args.py:80-81, likewise
+        raise ValueError("Demand prediction baseline. Please select NYC_TAXI or NYC_BIKE dataset!")
+    if model == "DMVSTNET" and dataset not in DMVSTNET_DATASETS:                  # reference model/DMVSTNET_demand/args.py:7-8, likewise
         raise ValueError("Demand prediction baseline. Please select NYC_TAXI or NYC_BIKE dataset!")
     cp = configparser.ConfigParser()
     cp.optionxform = str

@@ -405,3 +405,12 @@ def ccrnn_support(series, hidden_size_data, normalized_category="randomwalk", ho
         d_inv[np.isinf(d_inv)] = 0.
         support = (np.eye(d_inv.shape[0]) * d_inv).dot(support)
     return support
+
+
+def dmvstnet_adjacency(path, num_nodes):
+    """The (N, N) fp32 graph ``predictors.DMVSTNET`` multiplies by: the header-less, comma-separated N x N matrix of ``path`` as it is — the
+    reference (model/DMVSTNET_demand/args.py:32-33) neither normalises nor thresholds it.  Any other shape is refused."""
+    a = np.loadtxt(path, delimiter=",", dtype=np.float32, ndmin=2)
+    if a.shape != (num_nodes, num_nodes):
+        raise ValueError("DMVSTNET reads a header-less %d x %d matrix, %s holds %r" % (num_nodes, num_nodes, path, a.shape))
+    return a

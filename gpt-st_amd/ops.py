@@ -1774,3 +1774,29 @@ def stmgcn_lstm_bwd(dTop, WT, gates, c, dG_layers, tiles=0):
     _call("gptst_stmgcn_lstm_bwd", _p(dTop), _p(WT), _p(gates), _p(c), _p(dG), dG_layers, rows, T, L, H, tiles, tag="H%d L%d T%d" % (H, L, T),
           nbytes=_nb(dTop, WT, gates, c, dG))
     return dG
+
+
+# ---- the downstream DMVSTNET predictor's semantic view (csrc/dmvstnet.hip) -----------------------------------------------------------------------
+def dmvst_sen_fwd(x, V, c, N):
+    """z (rows, O) = x[r] V[r mod N] + c[r mod N];  x (rows = units N, C), V (N, C, O), c (N, O)"""
+    _chk(x, V, c)
+    rows, C = x.shape
+    O = V.shape[2]
+    assert rows % N == 0 and V.shape == (N, C, O) and c.shape == (N, O)
+    z = x.new_empty(rows, O)
+    _call("gptst_dmvst_sen_fwd", _p(x), _p(V), _p(c), _p(z), rows // N, N, C, O, tag="C%d O%d" % (C, O), nbytes=_nb(x, V, c, z))
+    return z
+
+
+def dmvst_sen_bwd(x, V, dz, N):
+    """-> (dx (rows, C) = dz V[n]^T, dV (N, C, O) = sum over the units of x^T dz, dc (N, O) = that of dz): unit-split partials summed in a
+    fixed order"""
+    _chk(x, V, dz)
+    rows, C = x.shape
+    O = V.shape[2]
+    assert rows % N == 0 and V.shape == (N, C, O) and dz.shape == (rows, O)
+    ns = _C.lib().value("gptst_dmvst_sen_nsplit", rows // N, N)
+    dx, pV, pc = torch.empty_like(x), x.new_empty(ns, N, C, O), x.new_empty(ns, N, O)
+    _call("gptst_dmvst_sen_bwd", _p(x), _p(V), _p(dz), _p(dx), _p(pV), _p(pc), ns, rows // N, N, C, O, tag="C%d O%d" % (C, O),
+          nbytes=_nb(x, V, dz, dx, pV, pc))
+    return dx, pV.sum(0), pc.sum(0)

@@ -26,7 +26,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define GPTST_ABI_VERSION 29  /* 29: + gptst_ccrnn_* (the graph-GRU cell of the downstream CCRNN predictor on HIP: TGCN's GRU step with a multi-polynomial mix, the cell's input in the operand slab, the decoder's feedback formed while the slab is filled: csrc/ccrnn.hip); 28: + gptst_stmgcn_* (the stacked LSTM of the downstream ST-MGCN predictor on HIP: all T steps of all L layers in ONE launch forward and ONE backward, states in LDS, rows local to their workgroup: csrc/stmgcn.hip); 27: + gptst_stwa_* (the downstream ST-WA predictor on HIP: one cut of a Layer in two launches forward and three backward, generated per-node weights folded from their rank-5 factors, the spatial attention over the nodes of a sample without its N x N scores: csrc/stwa.hip); 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
+#define GPTST_ABI_VERSION 30  /* 30: + gptst_dmvst_sen_* (the downstream DMVSTNET predictor on HIP: its semantic view as a per-node thin projection of x, forward and backward: csrc/dmvstnet.hip); 29: + gptst_ccrnn_* (the graph-GRU cell of the downstream CCRNN predictor on HIP: TGCN's GRU step with a multi-polynomial mix, the cell's input in the operand slab, the decoder's feedback formed while the slab is filled: csrc/ccrnn.hip); 28: + gptst_stmgcn_* (the stacked LSTM of the downstream ST-MGCN predictor on HIP: all T steps of all L layers in ONE launch forward and ONE backward, states in LDS, rows local to their workgroup: csrc/stmgcn.hip); 27: + gptst_stwa_* (the downstream ST-WA predictor on HIP: one cut of a Layer in two launches forward and three backward, generated per-node weights folded from their rank-5 factors, the spatial attention over the nodes of a sample without its N x N scores: csrc/stwa.hip); 26: + gptst_msdr_* (the multi-state recurrence of the downstream MSDR predictor on HIP: one launch per cell step forward, two backward, the attention logits from per-workgroup partials folded in a fixed order: csrc/msdr.hip); 25: + gptst_stgode_* (the downstream STGODE predictor on HIP: the fused Euler step forward and backward, its weight gradient and dW2 / dalpha reductions, batch norm over the node channel with the running max over the branches: csrc/stgode.hip); 24: + gptst_encin_ht1_bwd_jobs, gptst_gram_bwd_jobs, gptst_timefeat_jobs_bwd_jobs (the three launches at the end of the backward carry the gradient-reduction jobs as further workgroups: csrc/poolgen_dev.h pj_reduce_block); 23: + gptst_stfgnn_mix (the downstream STFGNN predictor on HIP: the product with the 4N x 4N spatial-temporal fusion graph as three N x N products per window: csrc/stfgnn.hip); gptst_stsgcn_wingemm / gptst_stsgcn_gate_bwd admit groups of R = 4N rows; 22: + gptst_stsgcn_* (the downstream STSGCN predictor on HIP: the localized window mix without its 3N x 3N matrix, a GEMM grouped by window with the running max, its gate backward and per-window weight gradient: csrc/stsgcn.hip); 21: + gptst_astgcn_* (the downstream ASTGCN predictor on HIP: node mixing with a per-sample masked graph, the gradient with respect to that graph, LayerNorm over the channels of a row: csrc/astgcn.hip); 20: + gptst_mtgnn_* (the downstream MTGNN predictor on HIP: tap GEMM between frames of different length, its weight gradient, the gate's backward, the gradient of the node mix with respect to its graphs: csrc/mtgnn.hip); 19: + gptst_tgcn_* (the recurrence of the downstream TGCN predictor on HIP, forward and backward: csrc/tgcn.hip); 18: + gptst_stgcn_* (the downstream STGCN predictor on HIP, forward and backward: csrc/stgcn.hip); 17: + gptst_fusion_gate_bwd_df (the gate's backward with the gradient of the embedding: fine-tuning the encoder downstream), gptst_deterministic_state; 16: + gptst_hypertem_chain_fwd_kl, gptst_kl_guest_blocks (the KL path's backward as guest workgroups of the forward's hyperTem chains); 15 (r06): + gptst_cap_split_units, gptst_cap_cross_route_lin_bwd_split (the last (b,t) units of the routing backward as two node halves: 384 units on 256 CUs -> one whole unit + one half per CU; measured, opt-in), gptst_clip_adam: stats_out[6] = updates skipped since gptst_handoff_reset; + gptst_mask_cooperative_state (the switch is thread-local now); + gptst_guide_head_fwd, gptst_guide_uc_floats (the guide classifier's forward in two launches); 14 (r05, late): + gptst_cap_cross_route_lin_bwd_jobs (gradient-reduction jobs as a role of the routing backward); 13 (r05, late): + gptst_mask_u24_fwd_jobs (forward generation jobs inside the cooperative mask launch); 12 (r05, late): + gptst_mask_cooperative (gptst_mask_*_u24 with 8192 < M <= 65536 cells and a workspace: ONE cooperative launch); 11 (r05): + gptst_cap_cross_route_lin_bwd, gptst_comm_available, gptst_handoff_reset, gptst_set_handoff_guard (gptst_clip_adam: stats_out[5] = expiries on record); - gptst_cap_rec_cross_route_bwd (three-role form, measured slower); 9, 10 (r04, late): + gptst_hypertem_bwd_pair, gptst_cap_rec_cross_route_bwd, gptst_mask_*_u24, gptst_pool_jobs_gram_rows, gptst_handoff_timeouts; gptst_fusion_gate_fwd/bwd */
 int gptst_abi_version(void);
 /* 1: bit-reproducible steps — the two reductions that end in float atomics by default (embedding gradients of gptst_pool_jobs kind 2,
  * weight gradients of gptst_timefeat_jobs) run as single-owner kernels with a fixed summation order (slower).  Everything else is
@@ -824,6 +824,16 @@ int gptst_ccrnn_bwd_cand(const float* PT, int Np, int ks, const float* W1T, int 
                          int T, int N, int Hp, int t, int tiles, void* stream);
 int gptst_ccrnn_bwd_state(const float* PT, int Np, int ks, const float* W0T, int Cp, const float* dpre0, const float* dh_part,
                           float* dh_out, float* dinp, int B, int T, int N, int Hp, int t, int tiles, void* stream);
+
+/* ---- the downstream DMVSTNET predictor's semantic view (dmvstnet.hip; reference model/DMVSTNET_demand/DMVSTNET.py:57-61, gpt-st_amd/predictors/dmvstnet_hip.py) ---
+ * z[r, :] = x[r, :] V[n] + c[n], n = r mod N; x (units, N, C), V (N, C, O), c (N, O), C a multiple of 16 up to 128, 1 <= O <= 4, else GPTST_ESHAPE.
+ * sen_fwd: z (units, N, O).   sen_bwd: dx (units, N, C) = dz V[n]^T, and pV (nsplit, N, C, O), pc (nsplit, N, O) = unit-split partials of
+ *   dV[n] = sum_units x^T dz and dc[n] = sum_units dz, each over its units in ascending order; nsplit = gptst_dmvst_sen_nsplit(units, N) (else
+ *   GPTST_EARG); the caller sums the splits (fixed order, no atomics). */
+int gptst_dmvst_sen_nsplit(int units, int N);
+int gptst_dmvst_sen_fwd(const float* x, const float* V, const float* c, float* z, int units, int N, int C, int O, void* stream);
+int gptst_dmvst_sen_bwd(const float* x, const float* V, const float* dz, float* dx, float* pV, float* pc, int nsplit, int units, int N, int C, int O,
+                        void* stream);
 
 /* ---- communication (comm.hip): RCCL over xGMI with an explicit stream — a collective can sit inside a captured hipGraph -------------
  * The reference has no distributed code; these carry the data-parallel gradient exchange (one all-reduce of [flat gradient | statistics])
